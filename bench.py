@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: trajectories/sec, forward + backward (+ gradient all-reduce + Adam), 3-layer SCoNe.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, takes W untimed and K timed optimiser steps, and prints the headline (`value`, `ms_per_step`: the wall time of
+one timed step); the measurements below (kernel timing and roofline, self-validation, CPU baselines, side configurations) run only
+with --full.  --dump-outputs DIR writes what the last timed step left a caller of Scone_GCN.grad_step_staged, right after the timed
+steps, as DIR/<name>.npy: `loss` (float64, the data term of the batch, summed over ranks), `weights` (the flat fp32 weights after
+its optimiser update), `weight_grad` (its all-reduced flat gradient), `adam_m` / `adam_v` (the optimiser moments).  The complex,
+the batch (seed 1030) and the initial weights are seeded, so the same arguments give the same inputs in every run.
 
 With --gpus N > 1 and no launcher environment the script starts N fresh ranks itself through torch.distributed.run
 (before anything touches the GPU) and exits with their code; launched by `python -m torch.distributed.run ... bench.py
@@ -15,7 +22,7 @@ that is already resident in HBM: forward, loss, backward, RCCL all-reduce of the
 ridge + Adam.  Rank 0 prints the full record as `DETAIL {...}` (also written to bench_full.json / --out) and then, as the
 LAST stdout line, ONE compact JSON line of at most 6000 characters (compact_line): the driver keeps an 8 KB tail.
 
-Extra objects in the full record (N = 1 only, unless noted; the compact line carries their flat summaries):
+Extra objects in the full record (--full; N = 1 only, unless noted; the compact line carries their flat summaries):
   roofline      the kernel FAMILY (template variants summed: the plain and the fused-first backward are one family) that takes
                 the most time in the step, timed live with events on the launch stream: algorithmic bytes of its launches /
                 their duration vs the 8 TB/s HBM peak, every variant's own fraction in `variants`; `traffic` = HBM bytes per
@@ -63,12 +70,20 @@ def parse():
                     help="> 0: weak scaling instead -- this many trajectories per GPU (global batch = N x this)")
     ap.add_argument("--cpu-sample", type=int, default=4, help="trajectories in the sparse CPU-baseline sample (0 = skip)")
     ap.add_argument("--parity-sample", type=int, default=4, help="trajectories of the full-size oracle comparison (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0: headline only (no other configs, no SpMM, no skipping modes)")
+    ap.add_argument("--extras", type=int, default=1, help="with --full, 0: no other configs, no SpMM, no skipping modes")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal: ranks may share one GPU)")
     ap.add_argument("--skip-modes", default="zeros,field",
                     help="also time the 512-per-GPU step in these zero-skipping modes ('' = none)")
     ap.add_argument("--out", default="", help="also write the FULL record to this file (e.g. profiles/rNN_bench_1gpu.json)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: kernel table and roofline, self-validation, CPU baselines, "
+                         "parity, the weak-scaling, zero-skipping and side configurations (--extras)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -198,20 +213,41 @@ def oracle_parity(cx, sc, net, inputs, flows, choice, last, hidden, n_sample):
 # one timed configuration
 # ----------------------------------------------------------------------------------------------------------------
 
-def time_config(net, inputs, staged, total, steps, warmup, sync, all_max):
-    """W untimed + K timed optimiser steps on resident micro-batches; returns (seconds over ranks (max), kernel table)."""
-    from scone_gcn_amd import ops
+def time_steps(net, inputs, staged, total, steps, warmup, sync, all_max):
+    """W untimed + K timed optimiser steps on resident micro-batches; returns (seconds over ranks (max), the last step's loss)."""
     for _ in range(warmup):
         net.grad_step_staged(inputs, staged, total)
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        net.grad_step_staged(inputs, staged, total)
+        loss = net.grad_step_staged(inputs, staged, total)
     sync()
-    dt = all_max(time.perf_counter() - t0)
+    return all_max(time.perf_counter() - t0), loss
+
+
+def time_config(net, inputs, staged, total, steps, warmup, sync, all_max):
+    """time_steps, then one more step under the kernel timer; returns (seconds over ranks (max), kernel table)."""
+    from scone_gcn_amd import ops
+    dt, _ = time_steps(net, inputs, staged, total, steps, warmup, sync, all_max)
     with ops.KernelTimer() as kt:                      # separate pass: the events do not sit in the timed region
         net.grad_step_staged(inputs, staged, total)
     return dt, kt.table()
+
+
+DUMP_LIMIT = 64 << 20                                   # bytes over all the files of --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """name -> float32 / float64 array as path/<name>.npy; an array beyond its share of DUMP_LIMIT is replaced by a sample of its
+    flat entries at fixed, seeded indices (they depend on the size only)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def family(key):
@@ -304,10 +340,28 @@ def make_net(model, hidden, sc, flows, last, y, B, skip="dense", layers=None):
     return net, inputs
 
 
+def with_edge_keys(cx):
+    """A copy of cx whose edge_index builds the sorted edge keys once: Complex.edge_index builds them on every call, and
+    path_dataset calls it once per trajectory (4096 x |E| = 1M keys: seconds of the set-up).  Same search on the same keys."""
+    import copy
+    keys = cx.edges[:, 0] * cx.n_nodes + cx.edges[:, 1]
+
+    def edge_index(a, b):
+        a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+        key = np.minimum(a, b) * cx.n_nodes + np.maximum(a, b)
+        idx = np.searchsorted(keys, key)
+        if np.any(idx >= len(keys)) or np.any(keys[np.minimum(idx, len(keys) - 1)] != key):
+            raise KeyError("edge not in complex")
+        return idx
+    out = copy.copy(cx)
+    out.edge_index = edge_index
+    return out
+
+
 def dataset(cx, sc, n, seed):
     from scone_gcn_amd import synthetic_data_gen as g
     paths = g.generate_random_walks(cx, m=n, seed=seed, waypoint_pool=8, metric="euclid")
-    flows, choice, last, _, _ = g.path_dataset(cx, paths, seed=seed + 7)
+    flows, choice, last, _, _ = g.path_dataset(with_edge_keys(cx), paths, seed=seed + 7)
     y = np.zeros((n, sc.max_degree, 1))
     y[np.arange(n), choice, 0] = 1.0
     return flows, choice, last, y
@@ -546,45 +600,17 @@ def main():
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t_setup
 
-    dt, table = time_config(net, inputs, staged, total, args.steps, args.warmup, sync, all_max)
+    dt, last_loss = time_steps(net, inputs, staged, total, args.steps, args.warmup, sync, all_max)
     value = total * args.steps / dt
-    roofline = roofline_of(table, mb)
-    # HBM bytes per launch from the committed rocprofv3 --pmc passes (same |E|, hidden and launch size only; dropped when the
-    # kernel sources have changed since the passes were taken)
-    if roofline and E == 996634 and mb == 128 and C == 32:
-        for section in ("main_bench", "main"):          # on the benchmark's own trajectories (what launch_ms is measured on), else dense random
-            roofline["traffic"], roofline["traffic_source"] = measured_traffic(section, list(roofline["variants"]))
-            if roofline["traffic"]:
-                break
-    # ---- self-validation of the data-parallel step (every N): the loss of one more step on the same batch, summed over the
-    # ranks, and the replicas' weights against rank 0's (identical Adam on identical reduced gradients => bitwise equal)
-    part = net.grad_step_staged(inputs, staged, total, apply=False)        # this rank's share of the data term, weights untouched
     red_dev = "cuda" if (world == 1 or args.backend == "nccl") else "cpu"
-    loss_t = part.detach().double().reshape(1).to(red_dev)
-    w0 = net._flat_w.detach().clone().to(red_dev)
-    if world > 1:
-        dist.all_reduce(loss_t, op=dist.ReduceOp.SUM)
-        dist.broadcast(w0, src=0)
-    dev_w = (net._flat_w.detach().to(red_dev) - w0).abs().max().double().reshape(1)
-    if world > 1:
-        dist.all_reduce(dev_w, op=dist.ReduceOp.MAX)
-    wf = net._flat_w.detach().double()
-    validation = {"loss": float(loss_t.item()), "replicas_identical": bool(float(dev_w.item()) == 0.0),
-                  "max_abs_weight_deviation_from_rank0": float(dev_w.item()),
-                  "weights_sum": float(wf.sum().item()), "weights_l2": float(wf.norm().item()),
-                  "optimiser_steps_taken": args.steps + args.warmup,
-                  "note": "loss = batch cross-entropy (data term, STM:54) after the warm-up and timed steps, summed over ranks; the global "
-                          "batch is seed-1030's for every N, so N = 1 and N > 1 lines agree to summation order"}
-
-    alg_step = sum(r["alg_bytes"] * r["launches"] for r in table.values() if r["alg_bytes"])
-    survey_bytes = 4.0 * E * (15 * C + 2)
-    step_model = {"survey_model_bytes_per_trajectory": survey_bytes,
-                  "survey_model_bytes_rate_not_achieved_bandwidth_frac_of_hbm_peak": value / world * survey_bytes / HBM_PEAK,
-                  "kernel_algorithmic_bytes_per_trajectory": alg_step / B,
-                  "kernel_model_frac_of_hbm_peak_whole_step": value / world * (alg_step / B) / HBM_PEAK,
-                  "note": "survey model = SURVEY.md section 8d (4*E*(15*C+2): every activation tensor once per pass) -- the fused "
-                          "kernels move FEWER bytes than that model, so its rate is a model-bytes rate, not achieved bandwidth; "
-                          "kernel model = sum of the timed kernels' own algorithmic bytes (what `roofline` and `kernels` price)"}
+    if args.dump_outputs:
+        loss_t = last_loss.detach().double().reshape(1).to(red_dev)
+        if world > 1:
+            dist.all_reduce(loss_t, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loss": loss_t.cpu().numpy(), "weights": net._flat_w.cpu().numpy(),
+                                             "weight_grad": net._flat_g.cpu().numpy(), "adam_m": net._m.cpu().numpy(),
+                                             "adam_v": net._v.cpu().numpy()})
     collective = None
     if world > 1:
         ver = ""
@@ -610,9 +636,56 @@ def main():
                    "arithmetic": "fp32 tensors and accumulation; dense products on the f16 MFMA as hi+lo splits of both operands under "
                                  "power-of-two row scales (3 of 4 cross products, dot-product error <= ~3*2^-22*sum|ab|, DESIGN.md 3.2)",
                    "nnz_lower": plan.nnz_lower, "nnz_upper": plan.nnz_upper, "nnz_pattern": plan.nnz_pattern},
-        "roofline": roofline, "cpu_baseline": None, "replicas_identical": validation["replicas_identical"],
-        "loss": validation["loss"], "validation": validation, "step_model": step_model, "kernels": slim(table), "setup_s": t_setup,
+        "roofline": None, "cpu_baseline": None, "replicas_identical": None, "loss": None, "setup_s": t_setup,
     }
+    if not args.full:
+        if rank == 0:
+            emit(line, args.out)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    with ops.KernelTimer() as kt:                          # separate pass: the events do not sit in the timed region
+        net.grad_step_staged(inputs, staged, total)
+    table = kt.table()
+    roofline = roofline_of(table, mb)
+    # HBM bytes per launch from the committed rocprofv3 --pmc passes (same |E|, hidden and launch size only; dropped when the
+    # kernel sources have changed since the passes were taken)
+    if roofline and E == 996634 and mb == 128 and C == 32:
+        for section in ("main_bench", "main"):          # on the benchmark's own trajectories (what launch_ms is measured on), else dense random
+            roofline["traffic"], roofline["traffic_source"] = measured_traffic(section, list(roofline["variants"]))
+            if roofline["traffic"]:
+                break
+    # ---- self-validation of the data-parallel step (every N): the loss of one more step on the same batch, summed over the
+    # ranks, and the replicas' weights against rank 0's (identical Adam on identical reduced gradients => bitwise equal)
+    part = net.grad_step_staged(inputs, staged, total, apply=False)        # this rank's share of the data term, weights untouched
+    loss_t = part.detach().double().reshape(1).to(red_dev)
+    w0 = net._flat_w.detach().clone().to(red_dev)
+    if world > 1:
+        dist.all_reduce(loss_t, op=dist.ReduceOp.SUM)
+        dist.broadcast(w0, src=0)
+    dev_w = (net._flat_w.detach().to(red_dev) - w0).abs().max().double().reshape(1)
+    if world > 1:
+        dist.all_reduce(dev_w, op=dist.ReduceOp.MAX)
+    wf = net._flat_w.detach().double()
+    validation = {"loss": float(loss_t.item()), "replicas_identical": bool(float(dev_w.item()) == 0.0),
+                  "max_abs_weight_deviation_from_rank0": float(dev_w.item()),
+                  "weights_sum": float(wf.sum().item()), "weights_l2": float(wf.norm().item()),
+                  "optimiser_steps_taken": args.steps + args.warmup,
+                  "note": "loss = batch cross-entropy (data term, STM:54) after the warm-up and timed steps, summed over ranks; the global "
+                          "batch is seed-1030's for every N, so N = 1 and N > 1 lines agree to summation order"}
+
+    alg_step = sum(r["alg_bytes"] * r["launches"] for r in table.values() if r["alg_bytes"])
+    survey_bytes = 4.0 * E * (15 * C + 2)
+    step_model = {"survey_model_bytes_per_trajectory": survey_bytes,
+                  "survey_model_bytes_rate_not_achieved_bandwidth_frac_of_hbm_peak": value / world * survey_bytes / HBM_PEAK,
+                  "kernel_algorithmic_bytes_per_trajectory": alg_step / B,
+                  "kernel_model_frac_of_hbm_peak_whole_step": value / world * (alg_step / B) / HBM_PEAK,
+                  "note": "survey model = SURVEY.md section 8d (4*E*(15*C+2): every activation tensor once per pass) -- the fused "
+                          "kernels move FEWER bytes than that model, so its rate is a model-bytes rate, not achieved bandwidth; "
+                          "kernel model = sum of the timed kernels' own algorithmic bytes (what `roofline` and `kernels` price)"}
+    line.update({"roofline": roofline, "replicas_identical": validation["replicas_identical"], "loss": validation["loss"],
+                 "validation": validation, "step_model": step_model, "kernels": slim(table)})
 
     # ---- weak-scaling companion: 512 trajectories per GPU (every N), + the zero-skipping modes on the same batch
     if args.extras and not weak:

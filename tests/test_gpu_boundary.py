@@ -448,7 +448,7 @@ def test_bench_lines_of_one_and_two_ranks_agree_on_loss_and_weights():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     lines = {}
     for n in (1, 2):
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--backend", "gloo", "--extras", "0",
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--backend", "gloo", "--full", "--extras", "0",
                "--edges", "50000", "--hidden", "16", "--global-batch", "64", "--steps", "3", "--warmup", "1"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -470,6 +470,35 @@ def test_bench_lines_of_one_and_two_ranks_agree_on_loss_and_weights():
     va, vb = a["validation"], b["validation"]
     assert abs(va["weights_sum"] - vb["weights_sum"]) <= 1e-6 * max(1.0, abs(va["weights_sum"]))
     assert abs(va["weights_l2"] - vb["weights_l2"]) <= 1e-6 * va["weights_l2"]
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line alone, takes exactly --warmup + --steps optimiser steps, and
+    --dump-outputs writes what the last of them computed: the same arguments give bitwise the same files, and moving one step
+    from the timed to the untimed side changes nothing, while one step fewer does."""
+    import json
+    _need_gpu()
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = {"a": (3, 1), "a_again": (3, 1), "moved": (2, 2), "fewer": (2, 1)}
+    for name, (steps, warmup) in runs.items():
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--edges", "50000", "--hidden", "16",
+               "--global-batch", "64", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        last = json.loads(r.stdout.splitlines()[-1])
+        assert last["metric"].startswith("trajectories/sec") and last["unit"] == "trajectories/s" and last["dtype"] == "f32"
+        assert last["higher_is_better"] is True and last["steps"] == steps and last["warmup"] == warmup
+        assert last["ms_per_step"] > 0 and abs(last["value"] - 64 * 1e3 / last["ms_per_step"]) <= 1e-9 * last["value"]
+        assert last["roofline"] is None and last["cpu_baseline"] is None and "configs" not in last
+    names = ("loss", "weights", "weight_grad", "adam_m", "adam_v")
+    out = {run: {n: np.load(tmp_path / run / (n + ".npy")) for n in names} for run in runs}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    a = out["a"]
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == (1,) and 0 < a["loss"][0] < 10
+    assert all(a[n].dtype == np.float32 and a[n].size == a["weights"].size and np.isfinite(a[n]).all() for n in names[1:])
+    for n in names:
+        assert np.array_equal(out["a_again"][n], a[n]) and np.array_equal(out["moved"][n], a[n]), n
+    assert not np.array_equal(out["fewer"]["weights"], a["weights"])
 
 
 def test_evaluation_cache_follows_every_way_the_weights_can_change(cfg1):

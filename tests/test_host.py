@@ -253,14 +253,18 @@ def test_ocean_drifter_dataset_counts():
     assert abs(B1 @ B2).max() == 0
 
 
-def test_jld2_reader_on_reference_file_if_present():
-    path = "/root/reference/ocean_drifters_data/dataBuoys.jld2"
-    if not os.path.exists(path):
-        pytest.skip("reference data file not on this machine")
+def test_jld2_reader_on_reference_file_if_present(tmp_path):
+    """The reader on the reference's dataBuoys.jld2 as stored in tests/golden/dataBuoys_subset.jld2.xz: the file's own bytes
+    wherever the reader looks, zeros elsewhere (tests/golden/make_golden_buoy.py)."""
+    import lzma
     from scone_gcn_amd import buoy_data as bd
-    elist, tlist, coords, trajs = bd.read_buoy_file(path)
+    path = tmp_path / "dataBuoys.jld2"
+    with open(os.path.join(GOLDEN, "dataBuoys_subset.jld2.xz"), "rb") as f:
+        path.write_bytes(lzma.decompress(f.read()))
+    elist, tlist, coords, trajs = bd.read_buoy_file(str(path))
     gld = np.load(os.path.join(GOLDEN, "buoy.npz"))
     assert np.array_equal(elist, gld["elist"]) and np.array_equal(tlist, gld["tlist"]) and len(trajs) == 339
+    assert np.array_equal(coords, gld["coords"]) and np.array_equal(np.concatenate(trajs), gld["traj_nodes"])
     assert bd.strip_paths([[1, 2, 1, 3, 4, 3, 5]]) == [[1, 3, 5]]
 
 
@@ -444,6 +448,23 @@ def test_bench_roofline_is_per_kernel_family_and_cites_traffic_only_for_the_meas
     (prof / "r09_pmc_traffic.json").write_text(json.dumps(doc))
     t, src = bench.measured_traffic("main_bench", list(r["variants"]))
     assert t == 48.5e9 and "r09_pmc_traffic.json" in src
+
+
+def test_bench_dump_outputs_keeps_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (no GPU): float32 / float64 .npy files, at most DUMP_LIMIT bytes in all; an array beyond its share is a
+    sample of its entries at indices that do not change from run to run."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    big = np.arange(10000, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": np.array([1.5]), "big": big})
+    loss, b = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [1.5]
+    assert b.dtype == np.float32 and b.nbytes == 2048 and np.all(np.diff(b) > 0) and np.all(np.isin(b, big))
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), b)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 4096 + 2 * 128   # + the .npy headers
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "c"), {"ids": np.arange(3)})
 
 
 def _synthetic_full_record(n_configs=12, pad=400):

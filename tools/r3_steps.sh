@@ -105,8 +105,8 @@ for s in "$@"; do
     pmc_bunch_mem) step pmc_bunch_mem 400 bash tools/pmc_run.sh $OUT/pmc_bunch fetch,write,tcc,sq1,sq2 tools/prof_bunch.py --reps 2 ;;
     pmc_main_bench) step pmc_main_bench 400 bash tools/pmc_run.sh $OUT/pmc_main_bench fetch,write,tcc tools/skip_step.py dense 2 512 ;;
     bench_prof)  cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-                 step bench_prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_prof -- python3 bench.py --extras 0 ;;
-    gloo2)       step gloo2 600 python3 bench.py --gpus 2 --backend gloo --extras 0 --steps 2 --warmup 1 --global-batch 512 ;;
+                 step bench_prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_prof -- python3 bench.py --full --extras 0 ;;
+    gloo2)       step gloo2 600 python3 bench.py --full --gpus 2 --backend gloo --extras 0 --steps 2 --warmup 1 --global-batch 512 ;;
     tests_durations) step tests_all 1150 python3 -m pytest tests -x -q -m gpu --durations=25 ;;
     pmc_skip)    step pmc_skip 900 bash tools/pmc_skip.sh $OUT/pmc_skip ;;
     cfg0)        step cfg0 300 python3 tools/cfg1_step_time.py dense breakdown ;;
@@ -116,7 +116,7 @@ for s in "$@"; do
                  step small_graph_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/small_graph_prof -- python3 tools/small_step.py
                  step small_eager_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/small_eager_prof -- python3 tools/small_step.py eager ;;
     spmm_ceiling) step spmm_ceiling 600 bash tools/spmm_ceiling.sh $OUT/spmm ;;
-    bench)       step bench 900 python3 bench.py ;;
+    bench)       step bench 900 python3 bench.py --full ;;
     bench_quick) step bench_quick 400 python3 bench.py --extras 0 --steps 5 --warmup 1 ;;
     prof_kernels) step prof_kernels 300 python3 tools/prof_kernels.py --which spmm,fwd,bwd,fwd1 --reps 3 ;;
     bunch_scale) step bunch_scale 300 python3 tools/model_scale.py bunch 1000000 64 32 ;;
