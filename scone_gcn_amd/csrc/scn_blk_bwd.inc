@@ -134,8 +134,9 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             w[j] = !PAIR ? Wg[ca * 32 + cc] : ((ca >> 4) == (cc >> 4) ? Wg[(ca & 15) * 16 + (cc & 15)] : 0.f);
         }
     }
+    bool w_bad;                                               // a weight is NaN / Inf: no zero-tile early-out (scn_blk_fwd.inc)
     const float sW = pow2_scale(block_abs_max<BK_THREADS>(amax3(amax3(amax3(amax3(0.f, w[0], w[1]), w[2], w[3]), w[4], w[5]), w[6], w[7]),
-                                                          (uint32_t*)(isel + 2048)), invW);
+                                                          any_not_finite(w), (uint32_t*)(isel + 2048), w_bad), invW);
     if (threadIdx.x < 3 * 2 * 64) {
         const int f = threadIdx.x, g = f / 128, t = (f >> 6) & 1, l = f & 63;
         const Split2 sp = split2(w, sW);
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             {
                 float mg = 0.f;
 #pragma unroll
-                for (int g = 0; g < 3; ++g) mg = amax_4x4(mg, G[g][0], G[g][1], G[g][2], G[g][3]);
+                for (int g = 0; g < 3; ++g) mg = amaxn_4x4(mg, G[g][0], G[g][1], G[g][2], G[g][3]);     // (NaN counts: scn_blk_fwd.inc)
                 // PAIR: the wave's tile is two slabs -- lanes h = 0 gathered slab A's sixteen channels, lanes h = 1 slab B's, and the
                 // block-diagonal weights keep their products apart (columns / lanes p < 16 and p >= 16 of every D tile) -- so each
                 // slab gets the scales of its own data; everything below is then per lane group instead of per wave
@@ -294,13 +295,13 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 } else {
                     mgb = max_over_wave(__float_as_uint(mg));
                 }
-                const uint32_t mgb_a = mgb;
+                uint32_t mgb_a = mgb;
                 if (PAIR) mgb = umax32(mgb, mgb_b);
                 // ZERO-TILE EARLY-OUT (see fwd_c32_w16_kernel): every gathered gradient of the tile is exactly zero, so its input
                 // gradient is zero (the accumulate form: the partial sum it was given) and it adds nothing to the weight gradients.
                 // The gradient of the readout lives on the edges around the last nodes; k layers down it is supported on their k-hop
                 // neighbourhood -- nearly every tile of a real batch leaves here.  Its share of the staging is still issued.
-                if (mgb == 0) {
+                if (!w_bad && mgb == 0) {
                     const int vdma0 = it + 1;
                     if (vdma0 < n_vis) {
                         const char* Xn0 = src_base(vdma0);
@@ -314,6 +315,17 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                     }
                     STAMP_ADD(4);
                     continue;
+                }
+                if (umax32(mgb_a, mgb_b) > 0x7f800000u) {           // a NaN in the tile (rare): the scales from the NaN-ignoring maximum
+                    asm volatile("; NaN tile: scales without it");
+                    float mf = 0.f;
+#pragma unroll
+                    for (int g = 0; g < 3; ++g) mf = amax_4x4(mf, G[g][0], G[g][1], G[g][2], G[g][3]);
+                    if (PAIR) {
+                        max_over_halves(__float_as_uint(mf), mgb_a, mgb_b);
+                    } else {
+                        mgb_a = max_over_wave(__float_as_uint(mf));
+                    }
                 }
                 float inv_g, inv_g_b = 0.f;
                 sG = pow2_scale(mgb_a, inv_g);

@@ -121,17 +121,48 @@ __device__ __forceinline__ float amax_4x4(float m, const f32x4 a, const f32x4 b,
     return m;
 }
 
+// NON-FINITE DATA.  The amax helpers ignore a NaN (what the scales want), so a tile holding nothing but zeros and NaNs would have
+// m == 0 and take a zero-tile early-out.  The early-outs therefore decide on the NaN-PROPAGATING maximum (v_maximum3_f32, same
+// cost): a NaN counts as non-zero.  A NaN in a point's maximum leaves its per-point scale at the clamp, where all of the point's
+// outputs are NaN anyway; the per-tile scales of the backward take the NaN-ignoring maximum again (rare branch).  A non-finite weight
+// turns the early-outs off altogether (0 * NaN and 0 * Inf are NaN).
+__device__ __forceinline__ float amaxn_2x4(float m, const f32x4 a, const f32x4 b) {
+    asm("v_maximum3_f32 %0, %0, |%1|, |%2|\n\tv_maximum3_f32 %0, %0, |%3|, |%4|\n\tv_maximum3_f32 %0, %0, |%5|, |%6|\n\tv_maximum3_f32 %0, %0, |%7|, |%8|"
+        : "+v"(m) : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
+    return m;
+}
+__device__ __forceinline__ float amaxn_4x4(float m, const f32x4 a, const f32x4 b, const f32x4 c, const f32x4 d) {
+    return amaxn_2x4(amaxn_2x4(m, a, b), c, d);
+}
+__device__ __forceinline__ float amaxn3(float m, float a, float b) {
+    asm("v_maximum3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(a), "v"(b));
+    return m;
+}
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+template <int N>
+__device__ __forceinline__ bool any_not_finite(const float (&w)[N]) {
+    bool r = false;
+#pragma unroll
+    for (int j = 0; j < N; ++j) r |= not_finite(w[j]);
+    return r;
+}
+
 // largest of the threads' non-negative floats `m` as a bit pattern, known to every thread of the workgroup: `red` = one LDS word per
 // wave.  Ends in a barrier.  (The kernels hand in the largest |weight| of the values a thread has just loaded for its fragment: the
-// weights are read from memory once.)
+// weights are read from memory once.)  `bad`: whether any thread handed in nonfinite = true (bit 31 of a wave's word: the maximum
+// of finite or infinite magnitudes stays below it).
 template <int NT>
-__device__ __forceinline__ uint32_t block_abs_max(float m, uint32_t* red) {
-    const uint32_t mw = max_over_wave(__float_as_uint(m));
+__device__ __forceinline__ uint32_t block_abs_max(float m, bool nonfinite, uint32_t* red, bool& bad) {
+    const uint32_t mw = max_over_wave(__float_as_uint(m)) | (__builtin_amdgcn_ballot_w64(nonfinite) != 0 ? 0x80000000u : 0u);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mw;
     __syncthreads();
-    uint32_t r = 0;
+    uint32_t r = 0, f = 0;
 #pragma unroll
-    for (int w = 0; w < NT / 64; ++w) r = umax32(r, red[w]);
+    for (int w = 0; w < NT / 64; ++w) {
+        r = umax32(r, red[w] & 0x7fffffffu);
+        f |= red[w];
+    }
+    bad = (f >> 31) != 0;
     return r;
 }
 
@@ -212,7 +243,9 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) w[j] = Wg[(8 * (l >> 4) + j) * 32 + 16 * ct + (l & 15)];
     }
-    const float sW = pow2_scale(block_abs_max<W16_THREADS>(amax3(amax3(amax3(amax3(0.f, w[0], w[1]), w[2], w[3]), w[4], w[5]), w[6], w[7]), wred), invW);
+    bool w_bad;                                               // a weight is NaN / Inf: no zero-tile early-out (above block_abs_max)
+    const float sW = pow2_scale(block_abs_max<W16_THREADS>(amax3(amax3(amax3(amax3(0.f, w[0], w[1]), w[2], w[3]), w[4], w[5]), w[6], w[7]),
+                                                           any_not_finite(w), wred, w_bad), invW);
     if (tid < 3 * 2 * 64) {
         const int f = tid;
         const int g = f / 128, ct = (f >> 6) & 1, l = f & 63;
@@ -359,13 +392,14 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
                 // the point's scale: largest magnitude among its 96 gathered values (this lane's 24 and its three partner lanes')
                 float inv;
                 float sz;
-                const float m = amax_2x4(amax_4x4(0.f, z[0][0], z[0][1], z[1][0], z[1][1]), z[2][0], z[2][1]);
+                const float m = amaxn_2x4(amaxn_4x4(0.f, z[0][0], z[0][1], z[1][0], z[1][1]), z[2][0], z[2][1]);   // (NaN counts)
                 // ZERO-TILE EARLY-OUT.  No layer of this path has a bias and act(0) = 0, so a tile whose gathered values are all exactly
                 // zero has the output act(partial) -- exactly what the contraction would produce; its split, MFMAs and un-scaling are
                 // skipped (wave-uniform branch), its share of the staging and its pending stores are not.  A trajectory's activations
                 // are supported on the k-hop neighbourhood of its edges after k layers, so most tiles of a real batch are of this kind;
                 // `roofline.dense_random_*` in the bench line is measured on tensors without zeros.
-                if (__builtin_amdgcn_ballot_w64(m != 0.f) == 0) {
+                const bool tile_zero = !w_bad && __builtin_amdgcn_ballot_w64(m != 0.f) == 0;
+                if (tile_zero) {
 #pragma unroll
                     for (int k = 0; k < NDMA; ++k)
                         if (more) dma(k, Xn, nbuf);
@@ -498,6 +532,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
     Split2 wa;
     f16x4 wbh, wbl;
     float invW;
+    bool w_bad;                                               // a weight is NaN / Inf: no zero-tile early-out (above block_abs_max)
     {
         float w[8];
 #pragma unroll
@@ -511,6 +546,8 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
         // (the 64 lanes of a wave hold all 3 x 256 weights between them: the largest is a wave reduction, no barrier, no second read)
         const float mw = amax_f4(amax3(amax3(amax3(amax3(0.f, w[0], w[1]), w[2], w[3]), w[4], w[5]), w[6], w[7]), w2);
         const float sW = pow2_scale(max_over_wave(__float_as_uint(mw)), invW);
+        w_bad = __builtin_amdgcn_ballot_w64(any_not_finite(w) || not_finite(w2[0]) || not_finite(w2[1]) || not_finite(w2[2]) ||
+                                            not_finite(w2[3])) != 0;
         wa = split2(w, sW);
         split2_4(w2, sW, wbh, wbl);
     }
@@ -595,10 +632,11 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
             // the two points' scales: largest magnitude among a point's 48 gathered values (this lane's 12 and its three partner
             // lanes'), both tiles' maxima reduced side by side as the upper halves of their bit patterns (exponent + 7 mantissa bits)
             float sz[2], inv[2];
-            const float m0 = amax3(amax_2x4(0.f, z[0][0], z[1][0]), z[2][0][0], z[2][0][1]);
-            const float m1 = amax3(amax_2x4(0.f, z[0][1], z[1][1]), z[2][1][0], z[2][1][1]);
-            const float m0b = amax3(m0, z[2][0][2], z[2][0][3]), m1b = amax3(m1, z[2][1][2], z[2][1][3]);
-            if (__builtin_amdgcn_ballot_w64(m0b != 0.f || m1b != 0.f) == 0) {       // zero-tile early-out (see fwd_c32_w16_kernel)
+            const float m0 = amaxn3(amaxn_2x4(0.f, z[0][0], z[1][0]), z[2][0][0], z[2][0][1]);    // (NaN counts)
+            const float m1 = amaxn3(amaxn_2x4(0.f, z[0][1], z[1][1]), z[2][1][0], z[2][1][1]);
+            const float m0b = amaxn3(m0, z[2][0][2], z[2][0][3]), m1b = amaxn3(m1, z[2][1][2], z[2][1][3]);
+            const bool tile_zero = !w_bad && __builtin_amdgcn_ballot_w64(m0b != 0.f || m1b != 0.f) == 0;   // zero-tile early-out (see fwd_c32_w16_kernel)
+            if (tile_zero) {
                 if (more) {
 #pragma unroll
                     for (int k = 0; k < NDMA; ++k) dma(k, XnA, XnB, nbuf);

@@ -441,8 +441,8 @@ __global__ __launch_bounds__(256) void split_sign_kernel(int64_t n, const float*
                                                          float* __restrict__ gm) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float v = g[i];
-        gp[i] = fmaxf(v, 0.f);
-        gm[i] = fminf(v, 0.f);
+        gp[i] = relu_nan(v);
+        gm[i] = neg_part_nan(v);
     }
 }
 
@@ -469,8 +469,8 @@ __global__ void fold1_forward_kernel(const float* __restrict__ w1, const float* 
     float sp = 0.f, sm = 0.f;
     for (int a = 0; a < c1; ++a) {
         const float w = w1[a], v = W2[a * c2 + c];
-        sp = fmaf(fmaxf(w, 0.f), v, sp);
-        sm = fmaf(fminf(w, 0.f), v, sm);
+        sp = fmaf(relu_nan(w), v, sp);
+        sm = fmaf(neg_part_nan(w), v, sm);
     }
     Ap[c] = sp;
     Am[c] = sm;
@@ -483,7 +483,7 @@ __global__ void fold1_backward_kernel(const float* __restrict__ w1, const float*
                                       float* __restrict__ dw1) {
     const int a = threadIdx.x;
     if (a >= c1) return;
-    const float w = w1[a], wp = fmaxf(w, 0.f), wm = fminf(w, 0.f);
+    const float w = w1[a], wp = relu_nan(w), wm = neg_part_nan(w);
     float sp = 0.f, sm = 0.f;
     for (int c = 0; c < c2; ++c) {
         const float v = W2[a * c2 + c], p = up[c], m = um[c];

@@ -30,6 +30,10 @@ void set_hip_error(hipError_t e, const char* where);
         }                                                   \
     } while (0)
 
+// relu and its negative-part twin that keep a NaN a NaN, like the reference's np.maximum (fmaxf(z, 0.f) returns 0 for a NaN z)
+__device__ __forceinline__ float relu_nan(float z) { return z <= 0.f ? 0.f : z; }
+__device__ __forceinline__ float neg_part_nan(float z) { return z >= 0.f ? 0.f : z; }
+
 // activation and its derivative expressed through the OUTPUT value y (what the backward has at hand)
 // tanh to ~3e-7 absolute: odd Taylor polynomial below 1/8, 1 - 2/(e^{2|x|}+1) on v_exp_f32 / v_rcp_f32 above
 __device__ __forceinline__ float fast_tanh(float x) {
@@ -42,7 +46,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 __device__ __forceinline__ float act_apply_fast(int act, float z) {
     switch (act) {
         case SCN_ACT_TANH: return fast_tanh(z);
-        case SCN_ACT_RELU: return fmaxf(z, 0.f);
+        case SCN_ACT_RELU: return relu_nan(z);
         case SCN_ACT_LEAKY_RELU: return z >= 0.f ? z : 0.01f * z;
         default: return z;
     }
@@ -50,7 +54,7 @@ __device__ __forceinline__ float act_apply_fast(int act, float z) {
 __device__ __forceinline__ float act_apply(int act, float z) {
     switch (act) {
         case SCN_ACT_TANH: return tanhf(z);
-        case SCN_ACT_RELU: return fmaxf(z, 0.f);
+        case SCN_ACT_RELU: return relu_nan(z);
         case SCN_ACT_LEAKY_RELU: return z >= 0.f ? z : 0.01f * z;
         default: return z;
     }

@@ -152,7 +152,7 @@ __device__ __forceinline__ f32x4 sm_act4(int act, f32x4 z) {
         }
     } else if (act == SCN_ACT_RELU) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaxf(z[j], 0.f);
+        for (int j = 0; j < 4; ++j) o[j] = relu_nan(z[j]);
     } else if (act == SCN_ACT_LEAKY_RELU) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = z[j] >= 0.f ? z[j] : 0.01f * z[j];

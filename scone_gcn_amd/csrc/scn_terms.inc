@@ -42,22 +42,22 @@ static_assert(TK_LDS_BYTES <= 160 * 1024, "weight (+ selection) fragments and th
 
 // largest |W| over the (up to seven) weight matrices of a fused Bunch layer as a bit pattern, known to every thread; ends in a barrier.
 // ONE power-of-two scale serves them all (a wave's three matrices share its accumulator; see scn_blk_fwd.inc for the split).
+// bad: some weight is NaN / Inf (no zero-tile early-out, see block_abs_max).
 template <int NT>
-__device__ __forceinline__ uint32_t terms_weights_abs_max(const float* const (&W)[9], uint32_t* red) {
+__device__ __forceinline__ uint32_t terms_weights_abs_max(const float* const (&W)[9], uint32_t* red, bool& bad) {
     float m = 0.f;
+    bool nf = false;
 #pragma unroll
     for (int sl = 0; sl < 9; ++sl) {
         const float* Wg = W[sl];
         if (!Wg || sl == 2 || sl == 6) continue;
-        for (int i = threadIdx.x; i < 32 * 32; i += NT) m = fmaxf(m, fabsf(Wg[i]));
+        for (int i = threadIdx.x; i < 32 * 32; i += NT) {
+            const float v = Wg[i];
+            m = fmaxf(m, fabsf(v));
+            nf |= not_finite(v);
+        }
     }
-    const uint32_t mw = max_over_wave(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mw;
-    __syncthreads();
-    uint32_t r = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) r = umax32(r, red[w]);
-    return r;
+    return block_abs_max<NT>(m, nf, red, bad);
 }
 
 struct TermsDev {
@@ -408,7 +408,8 @@ __global__ __launch_bounds__(W16_THREADS, 4) void terms_fwd_c32_kernel(TermsDev 
     const int lrow = wrow0 + (pt & 3);
     // the seven weight matrices, split once under one scale: slot cls * 3 + g -> fragment (ct, part, lane) = W[8*kq' + j][16*ct + i] * sW
     float invW;
-    const float sW = pow2_scale(terms_weights_abs_max<W16_THREADS>(A.W, (uint32_t*)(wfrag + 7 * TK_WSLOT_BYTES + 2048)), invW);
+    bool w_bad;
+    const float sW = pow2_scale(terms_weights_abs_max<W16_THREADS>(A.W, (uint32_t*)(wfrag + 7 * TK_WSLOT_BYTES + 2048), w_bad), invW);
     for (int f = tid; f < 9 * 2 * 64; f += W16_THREADS) {
         const int sl = f / 128, ct = (f >> 6) & 1, l = f & 63;
         const float* Wg = A.W[sl];
@@ -611,8 +612,8 @@ __global__ __launch_bounds__(W16_THREADS, 4) void terms_fwd_c32_kernel(TermsDev 
                 float m = 0.f;
 #pragma unroll
                 for (int g = 0; g < 3; ++g)
-                    if (present & (1u << g)) m = amax_2x4(m, z[g][0], z[g][1]);
-                const bool tile_zero = __builtin_amdgcn_ballot_w64(m != 0.f) == 0;   // zero-tile early-out (see fwd_c32_w16_kernel)
+                    if (present & (1u << g)) m = amaxn_2x4(m, z[g][0], z[g][1]);        // (NaN counts: scn_blk_fwd.inc)
+                const bool tile_zero = !w_bad && __builtin_amdgcn_ballot_w64(m != 0.f) == 0;   // zero-tile early-out (see fwd_c32_w16_kernel)
                 {
                     sz = pow2_scale(max_over_rows(__float_as_uint(m)), inv);
                     inv *= invW;
@@ -768,7 +769,8 @@ __global__ __launch_bounds__(BK_THREADS, 2) void terms_bwd_c32_kernel(TermsDev T
     const int lrow = wrow0 + (p >> 2);
     // dgrad B fragments of the seven matrices under one scale: (t, part, lane) holds W[ca = lane&31][c = 16*(lane>>5) + 8t + j] * sW
     float invW;
-    const float sW = pow2_scale(terms_weights_abs_max<BK_THREADS>(A.W, (uint32_t*)(isel + 2048)), invW);
+    bool w_bad;
+    const float sW = pow2_scale(terms_weights_abs_max<BK_THREADS>(A.W, (uint32_t*)(isel + 2048), w_bad), invW);
     for (int f = threadIdx.x; f < 9 * 2 * 64; f += BK_THREADS) {
         const int sl = f / 128, t = (f >> 6) & 1, l = f & 63;
         const float* Wg = A.W[sl];
@@ -935,15 +937,22 @@ __global__ __launch_bounds__(BK_THREADS, 2) void terms_bwd_c32_kernel(TermsDev T
                 float mgv = 0.f;
 #pragma unroll
                 for (int g = 0; g < 3; ++g)
-                    if (present & (1u << g)) mgv = amax_4x4(mgv, G[g][0], G[g][1], G[g][2], G[g][3]);
-                const uint32_t mgb = max_over_wave(__float_as_uint(mgv));
-                if (mgb == 0) {                                // zero-tile early-out (see bwd_c32_bf16_kernel): dx = 0, nothing for the weight gradients
+                    if (present & (1u << g)) mgv = amaxn_4x4(mgv, G[g][0], G[g][1], G[g][2], G[g][3]);     // (NaN counts: scn_blk_fwd.inc)
+                uint32_t mgb = max_over_wave(__float_as_uint(mgv));
+                if (!w_bad && mgb == 0) {                      // zero-tile early-out (see bwd_c32_bf16_kernel): dx = 0, nothing for the weight gradients
                     if (dp) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
                             if (2 * (r >> 2) + h < rows_left) dp[L0 + ((r & 3) + 8 * (r >> 2)) * 32] = 0.f;
                     }
                     continue;
+                }
+                if (mgb > 0x7f800000u) {                       // a NaN in the tile (rare): the scale from the NaN-ignoring maximum
+                    float mf = 0.f;
+#pragma unroll
+                    for (int g = 0; g < 3; ++g)
+                        if (present & (1u << g)) mf = amax_4x4(mf, G[g][0], G[g][1], G[g][2], G[g][3]);
+                    mgb = max_over_wave(__float_as_uint(mf));
                 }
                 float inv_g;
                 sG = pow2_scale(mgb, inv_g);
