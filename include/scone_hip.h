@@ -455,6 +455,41 @@ int scn_adam_step_dev(int64_t n, float* w, const float* g, float* m, float* v,
                       float lr, float b1, float b2, float eps, int32_t* step_dev,
                       float weight_decay, float g_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Multi-hop prediction (STM:110-206): the steps between the batched forwards of a greedy rollout or of a probability tree.
+ * Step tables (built on the host from the caller's nbrhoods and E_lookup, row-major [n_nodes][d]): step_node = the neighbour in
+ * slot j of node v (-1: none), step_edge = the DEVICE row of the edge that step crosses (-1: the pair has no edge), step_sign = the
+ * flow value the step sets there (+1 / -1).  deg[v] = number of slots of v that hold a neighbour.  Flow slabs are [S][n_rows][ns][1].
+ *
+ * scn_hop_select: per trajectory i < n, choice[i] = np.argmax of logp[i][0..d) after slots j >= limit are set to fill (-100 in
+ *   STM:116-117; first maximum, a NaN counts as the maximum); limit = n_limit[i], or deg[cur[i]] when n_limit is NULL.  With step_edge == NULL nothing else
+ *   happens (final hop).  Otherwise u = step_node[cur[i]][choice[i]] goes to next_node[i] (if not NULL), x[i / ns][e][i % ns] is SET
+ *   to step_sign (if x is not NULL, e = step_edge), and with advance != 0 cur[i] = last[i] = u.  A slot without an edge writes
+ *   nothing and lowers err[0] to i (atomicMin: the caller initialises it to INT32_MAX).  x holds at least n trajectories. */
+int scn_hop_select(int32_t n, int32_t d, const float* logp, const int32_t* n_limit, float fill, const int32_t* deg, int32_t* cur,
+                   int32_t* last, int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, const float* step_sign,
+                   int32_t n_rows, int32_t ns, float* x, int32_t advance, int32_t* choice, int32_t* next_node, int32_t* err,
+                   void* stream);
+/* scn_tree_expand: level h -> h + 1 of a probability tree.  Leaf l (root[l], node[l], prob[l], path_row / path_sign [l][h]) with
+ *   log-probabilities logp[l][0..d) gets one child per slot j < deg[node[l]], written at c = offset[l] + j (the exclusive scan of
+ *   deg[node], leaf-major and slot-minor): c_root = root[l], c_node = step_node[v][j], c_prob = prob[l] * exp(logp[l][j]),
+ *   c_path = path + (step_edge[v][j], step_sign[v][j]) ([c][h + 1]).  A slot without an edge lowers err[0] to l * d + j. */
+int scn_tree_expand(int32_t n_leaves, int32_t h, int32_t d, const int32_t* root, const int32_t* node, const float* prob,
+                    const int32_t* path_row, const float* path_sign, const float* logp, const int32_t* offset, const int32_t* deg,
+                    int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows,
+                    int32_t n_children, int32_t* c_root, int32_t* c_node, float* c_prob, int32_t* c_path_row, float* c_path_sign,
+                    int32_t* err, void* stream);
+/* scn_tree_slabs: input slabs x [n_slabs][n_rows][4][1] (16-byte aligned) of n_leaves <= 4 n_slabs leaves: column l = the column
+ *   of trajectory root[l] < n_roots of the resident root slabs root_x, then the leaf's path entries SET in level order (the last
+ *   write wins; an edge already in the root flow is overwritten).  Columns past n_leaves are zero.  ns must be 4. */
+int scn_tree_slabs(int32_t n_leaves, int32_t n_slabs, int32_t h, const int32_t* root, const int32_t* path_row, const float* path_sign,
+                   int32_t n_roots, const float* root_x, int32_t n_rows, int32_t ns, float* x, void* stream);
+/* scn_tree_target: final level.  out[r] = (sum of prob[l] * exp(logp[l][j]) over the leaves l in [leaf_ptr[r], leaf_ptr[r + 1]) and
+ *   slots j < deg[node[l]] with step_node[node[l]][j] == target[r]) / (number of such terms); NaN when there is none (0 / 0,
+ *   STM:199-204).  One wave per root, fixed summation order, no atomics: bitwise repeatable. */
+int scn_tree_target(int32_t n_roots, const int32_t* leaf_ptr, const int32_t* node, const float* prob, const float* logp, int32_t d,
+                    const int32_t* deg, int32_t n_nodes, const int32_t* step_node, const int32_t* target, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

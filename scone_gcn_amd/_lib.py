@@ -127,6 +127,15 @@ SIGNATURES = {
                                            c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_i32,
                                            ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_size_t,
                                            c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32, c_void_p, c_f32, c_void_p]),
+    "scn_hop_select": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                      c_void_p, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_tree_expand": (ctypes.c_int, [c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_tree_slabs": (ctypes.c_int, [c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_void_p,
+                                      c_void_p]),
+    "scn_tree_target": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

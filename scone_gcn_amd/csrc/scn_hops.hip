@@ -1,0 +1,218 @@
+// Multi-hop prediction (STM:110-206): the device steps between the forwards of a greedy rollout or of a probability tree.
+// The forwards themselves are the fused layer kernels; these kernels choose the next node, look up the edge it crosses, build the
+// child flow slabs and reduce the leaf probabilities per trajectory, so that no level of a rollout or of a tree goes through the host.
+#include "scn_internal.h"
+
+#include <climits>
+
+namespace {
+
+// np.argmax over d slots of one row after preds[limit:] = fill (-100 in STM:116-119): the first maximum wins, a NaN counts as the
+// maximum (the first NaN wins)
+__device__ __forceinline__ int masked_argmax(const float* __restrict__ row, int d, int lim, float fill) {
+    float bv = 0 < lim ? row[0] : fill;
+    int best = 0;
+    if (isnan(bv)) return 0;
+    for (int j = 1; j < d; ++j) {
+        const float t = j < lim ? row[j] : fill;
+        if (isnan(t)) return j;
+        if (t > bv) {
+            bv = t;
+            best = j;
+        }
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(256) void hop_select_kernel(int n, int d, const float* __restrict__ logp, const int32_t* __restrict__ n_limit,
+                                                         float fill, const int32_t* __restrict__ deg, int32_t* cur, int32_t* last, int n_nodes,
+                                                         const int32_t* __restrict__ step_node, const int32_t* __restrict__ step_edge,
+                                                         const float* __restrict__ step_sign, int n_rows, int ns, float* x, int advance,
+                                                         int32_t* __restrict__ choice, int32_t* __restrict__ next_node, int32_t* err) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int v = cur[i];
+    const bool v_ok = v >= 0 && v < n_nodes;
+    const int lim = n_limit ? n_limit[i] : (v_ok ? deg[v] : 0);
+    const int c = masked_argmax(logp + (size_t)i * d, d, lim, fill);
+    choice[i] = c;
+    if (!step_edge) return;                                          // final hop of the accuracy: no lookup (STM:121-122)
+    const size_t k = (size_t)v * d + c;
+    const int e = v_ok ? step_edge[k] : -1;
+    const int u = v_ok ? step_node[k] : -1;
+    if (e < 0 || e >= n_rows || u < 0) {                              // the pair has no edge (KeyError in the reference): nothing written
+        atomicMin(err, i);
+        return;
+    }
+    if (next_node) next_node[i] = u;
+    if (x) x[((size_t)(i / ns) * n_rows + e) * ns + (i % ns)] = step_sign[k];     // SET, not add (STM:149-150)
+    if (advance) {
+        cur[i] = u;
+        last[i] = u;
+    }
+}
+
+// one thread per (leaf, slot): the children of leaf l go to offset[l] + j, leaf-major and slot-minor (STM:176-198)
+__global__ __launch_bounds__(256) void tree_expand_kernel(int n_leaves, int h, int d, const int32_t* __restrict__ root,
+                                                          const int32_t* __restrict__ node, const float* __restrict__ prob,
+                                                          const int32_t* __restrict__ path_row, const float* __restrict__ path_sign,
+                                                          const float* __restrict__ logp, const int32_t* __restrict__ offset,
+                                                          const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
+                                                          const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
+                                                          int n_rows, int n_children, int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
+                                                          float* __restrict__ c_prob, int32_t* __restrict__ c_path_row,
+                                                          float* __restrict__ c_path_sign, int32_t* err) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)n_leaves * d) return;
+    const int l = (int)(t / d), j = (int)(t % d);
+    const int v = node[l];
+    if (v < 0 || v >= n_nodes || j >= deg[v]) return;
+    const size_t k = (size_t)v * d + j;
+    const int e = step_edge[k];
+    const int u = step_node[k];
+    const int c = offset[l] + j;
+    if (e < 0 || e >= n_rows || u < 0 || c < 0 || c >= n_children) {
+        atomicMin(err, (int)t);
+        return;
+    }
+    c_root[c] = root[l];
+    c_node[c] = u;
+    c_prob[c] = prob[l] * expf(logp[(size_t)l * d + j]);
+    for (int q = 0; q < h; ++q) {
+        c_path_row[(size_t)c * (h + 1) + q] = path_row[(size_t)l * h + q];
+        c_path_sign[(size_t)c * (h + 1) + q] = path_sign[(size_t)l * h + q];
+    }
+    c_path_row[(size_t)c * (h + 1) + h] = e;
+    c_path_sign[(size_t)c * (h + 1) + h] = step_sign[k];
+}
+
+// one thread per (slab, row) of the output: the ns = 4 leaves' root columns, one 16-byte store
+__global__ __launch_bounds__(256) void tree_copy_kernel(int n_leaves, int64_t n_items, const int32_t* __restrict__ root, int n_roots,
+                                                        const float* __restrict__ root_x, int n_rows, float* __restrict__ x) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_items; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = t / n_rows;
+        const int r = (int)(t % n_rows);
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t l = s * 4 + q;
+            const int rt = l < n_leaves ? root[l] : -1;
+            v[q] = (rt >= 0 && rt < n_roots) ? root_x[((size_t)(rt >> 2) * n_rows + r) * 4 + (rt & 3)] : 0.f;
+        }
+        *reinterpret_cast<float4*>(x + (size_t)t * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// one thread per leaf: its path entries in level order, so the last write of an edge wins and a root entry is overwritten (STM:187)
+__global__ __launch_bounds__(256) void tree_patch_kernel(int n_leaves, int h, const int32_t* __restrict__ path_row,
+                                                         const float* __restrict__ path_sign, int n_rows, float* __restrict__ x) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_leaves) return;
+    for (int q = 0; q < h; ++q) {
+        const int r = path_row[(size_t)l * h + q];
+        if (r >= 0 && r < n_rows) x[((size_t)(l >> 2) * n_rows + r) * 4 + (l & 3)] = path_sign[(size_t)l * h + q];
+    }
+}
+
+// one wave per root over its contiguous leaves; lane partial sums in a fixed order, then a fixed shuffle tree: bitwise repeatable
+__global__ __launch_bounds__(64) void tree_target_kernel(int n_roots, const int32_t* __restrict__ leaf_ptr, const int32_t* __restrict__ node,
+                                                         const float* __restrict__ prob, const float* __restrict__ logp, int d,
+                                                         const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
+                                                         const int32_t* __restrict__ target, float* __restrict__ out) {
+    const int r = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (r >= n_roots) return;
+    const int tg = target[r];
+    float s = 0.f;
+    int cnt = 0;
+    for (int l = leaf_ptr[r] + lane; l < leaf_ptr[r + 1]; l += 64) {
+        const int v = node[l];
+        if (v < 0 || v >= n_nodes) continue;
+        const int dv = deg[v];
+        for (int j = 0; j < dv; ++j) {
+            if (step_node[(size_t)v * d + j] == tg) {
+                s += prob[l] * expf(logp[(size_t)l * d + j]);
+                ++cnt;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_down(s, o, 64);
+        cnt += __shfl_down(cnt, o, 64);
+    }
+    if (lane == 0) out[r] = cnt ? s / (float)cnt : __builtin_nanf("");     // 0 / 0 in the reference (STM:203)
+}
+
+}  // namespace
+
+extern "C" {
+
+int scn_hop_select(int32_t n, int32_t d, const float* logp, const int32_t* n_limit, float fill, const int32_t* deg, int32_t* cur,
+                   int32_t* last, int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, const float* step_sign,
+                   int32_t n_rows, int32_t ns, float* x, int32_t advance, int32_t* choice, int32_t* next_node, int32_t* err,
+                   void* stream) {
+    if (n < 0 || d <= 0 || n_nodes <= 0 || n_rows < 0 || ns <= 0) return SCN_ERR_BAD_SHAPE;
+    if (!logp || !cur || !choice || (!n_limit && !deg)) return SCN_ERR_BAD_ARG;
+    if (step_edge && (!step_node || !step_sign || !err)) return SCN_ERR_BAD_ARG;
+    if (advance && (!step_edge || !last)) return SCN_ERR_BAD_ARG;
+    if (x && !step_edge) return SCN_ERR_BAD_ARG;
+    if (n == 0) return SCN_OK;
+    hipLaunchKernelGGL(hop_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d, logp, n_limit,
+                       fill, deg, cur, last, n_nodes, step_node, step_edge, step_sign, n_rows, ns, x, advance, choice, next_node, err);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_tree_expand(int32_t n_leaves, int32_t h, int32_t d, const int32_t* root, const int32_t* node, const float* prob,
+                    const int32_t* path_row, const float* path_sign, const float* logp, const int32_t* offset, const int32_t* deg,
+                    int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows,
+                    int32_t n_children, int32_t* c_root, int32_t* c_node, float* c_prob, int32_t* c_path_row, float* c_path_sign,
+                    int32_t* err, void* stream) {
+    if (n_leaves < 0 || h < 0 || d <= 0 || n_nodes <= 0 || n_rows <= 0 || n_children < 0) return SCN_ERR_BAD_SHAPE;
+    if ((int64_t)n_leaves * d >= INT_MAX) return SCN_ERR_UNSUPPORTED;
+    if (n_leaves == 0) return SCN_OK;
+    if (!root || !node || !prob || !logp || !offset || !deg || !step_node || !step_edge || !step_sign || !err) return SCN_ERR_BAD_ARG;
+    if (h > 0 && (!path_row || !path_sign)) return SCN_ERR_BAD_ARG;
+    if (n_children > 0 && (!c_root || !c_node || !c_prob || !c_path_row || !c_path_sign)) return SCN_ERR_BAD_ARG;
+    const int64_t items = (int64_t)n_leaves * d;
+    hipLaunchKernelGGL(tree_expand_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_leaves, h, d, root,
+                       node, prob, path_row, path_sign, logp, offset, deg, n_nodes, step_node, step_edge, step_sign, n_rows, n_children,
+                       c_root, c_node, c_prob, c_path_row, c_path_sign, err);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_tree_slabs(int32_t n_leaves, int32_t n_slabs, int32_t h, const int32_t* root, const int32_t* path_row, const float* path_sign,
+                   int32_t n_roots, const float* root_x, int32_t n_rows, int32_t ns, float* x, void* stream) {
+    if (n_leaves < 0 || n_slabs <= 0 || h < 0 || n_roots <= 0 || n_rows <= 0) return SCN_ERR_BAD_SHAPE;
+    if (ns != 4) return SCN_ERR_UNSUPPORTED;
+    if ((int64_t)n_leaves > (int64_t)n_slabs * ns) return SCN_ERR_BAD_SHAPE;
+    if (!x || !root_x || (n_leaves > 0 && !root) || (h > 0 && n_leaves > 0 && (!path_row || !path_sign))) return SCN_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return SCN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t items = (int64_t)n_slabs * n_rows;
+    const int64_t blocks = (items + 255) / 256;
+    hipLaunchKernelGGL(tree_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, n_leaves, items, root,
+                       n_roots, root_x, n_rows, x);
+    SCN_LAUNCH_CHECK();
+    if (h > 0 && n_leaves > 0) {
+        hipLaunchKernelGGL(tree_patch_kernel, dim3((unsigned)((n_leaves + 255) / 256)), dim3(256), 0, st, n_leaves, h, path_row,
+                           path_sign, n_rows, x);
+        SCN_LAUNCH_CHECK();
+    }
+    return SCN_OK;
+}
+
+int scn_tree_target(int32_t n_roots, const int32_t* leaf_ptr, const int32_t* node, const float* prob, const float* logp, int32_t d,
+                    const int32_t* deg, int32_t n_nodes, const int32_t* step_node, const int32_t* target, float* out, void* stream) {
+    if (n_roots < 0 || d <= 0 || n_nodes <= 0) return SCN_ERR_BAD_SHAPE;
+    if (n_roots == 0) return SCN_OK;
+    if (!leaf_ptr || !node || !prob || !logp || !deg || !step_node || !target || !out) return SCN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(tree_target_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, n_roots, leaf_ptr, node, prob, logp,
+                       d, deg, n_nodes, step_node, target, out);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from . import distributed as dp
+from .complex import Bconds
 from .synthetic_data_gen import SparseFlows
 from .trajectory_experiments import MODEL_ACT, MODEL_FUNCS, resolve_operands
 
@@ -346,6 +347,188 @@ class Scone_GCN():
         true_probs = preds[rows, true_choice, 0]
         t, r = true_probs[m], random_probs[m]
         return float((np.sum(t > r) + 0.5 * np.sum(t == r)) / np.sum(m))
+
+    # ------------------------------------------------------------------ multi-hop prediction (STM:110-206)
+    # Each hop / tree level is ONE batched dense forward over all its trajectories / leaves (chunked by ops.forward_micro_batch, or
+    # by multi_hop_micro_batch when set); the steps between -- choose the next node, set the edge it crosses, build the children,
+    # reduce the leaf probabilities -- are csrc/scn_hops.hip.  The caller's flows are never written (the reference writes into them,
+    # STM:149-150) and the evaluation cache is not touched.
+    multi_hop_micro_batch = None
+
+    def _multihop_plan(self, inputs):
+        if self.model_type != 'bunch' and not isinstance(inputs[0], Bconds):
+            raise TypeError("multi-hop prediction needs the Bconds object of SimplicialComplex.bconds() (what data_setup returns) as "
+                            "the readout operand: a plain Bcond_func closure only knows the last nodes it has been probed at")
+        plan = self._plan(inputs)
+        if plan is None:
+            raise TypeError("multi-hop prediction runs the native model functions (scone_func / ebli_func / bunch_func) only")
+        return plan
+
+    def _mb(self, plan, n):
+        mb = self.multi_hop_micro_batch or ops.forward_micro_batch(plan, self.weights, n)
+        return max(ops.NS, ops.pad_count(int(mb)))
+
+    def _forward_all(self, plan, x, last, mb):
+        """logp [S * NS, D] of all slabs x, mb trajectories per launch."""
+        sl = mb // ops.NS
+        outs = [ops.forward_logp(plan, x[s0:s0 + sl], last[s0 * ops.NS:(s0 + sl) * ops.NS], self.weights)
+                for s0 in range(0, x.shape[0], sl)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def _rollout(self, inputs, cur_nodes, n_limit, hops, tab, advance, fill, trace=None):
+        """Greedy rollout on the device: returns (choices [N] of the final hop, nodes [hops, N] or None).  trace: list that gets, per
+        hop, (flows (N, E) in the caller's edge order, readout last nodes, logp (N, D)) as the forward saw them and the choices."""
+        plan = self._multihop_plan(inputs)
+        lib = _lib.load()
+        N = _n_samples(inputs[-1])
+        if len(np.asarray(inputs[1]).reshape(-1)) != N or any(a is not None and len(np.asarray(a).reshape(-1)) != N
+                                                              for a in (cur_nodes, n_limit)):
+            raise ValueError("last nodes and n_nbrs need one entry per trajectory of inputs (%d)" % N)
+        dev = plan.device
+        x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)               # a copy: the caller's flows stay as they are
+        last = ops._last_nodes_dev(inputs[1], x.shape[0] * ops.NS, dev)
+        cur = last[:N].clone() if cur_nodes is None else torch.from_numpy(np.ascontiguousarray(cur_nodes, np.int32)).to(dev)
+        lim = None if n_limit is None else torch.from_numpy(np.ascontiguousarray(n_limit, np.int32)).to(dev)
+        choice = torch.empty((N,), device=dev, dtype=torch.int32)
+        nodes = torch.empty((hops, N), device=dev, dtype=torch.int32) if advance else None
+        err = torch.empty((1,), device=dev, dtype=torch.int32)
+        mb = self._mb(plan, N)
+        for h in range(hops):
+            logp = self._forward_all(plan, x, last, mb)
+            rec = None if trace is None else (ops.slabs_to_batch(x, plan.layout, 1, N)[:, :, 0].cpu().numpy(), last[:N].cpu().numpy(),
+                                              logp[:N].cpu().numpy())
+            final = h == hops - 1
+            lookup = advance or not final                                   # the accuracy's final hop looks nothing up (STM:121-122)
+            err.fill_(ops.INT32_MAX)
+            cur_h = cur.cpu().numpy() if lookup else None
+            _lib.check(lib.scn_hop_select(N, plan.max_deg, ops._dev(logp), ops._dev(lim, torch.int32) if lim is not None else None,
+                                          fill, ops._dev(tab.deg, torch.int32), ops._dev(cur, torch.int32), ops._dev(last, torch.int32),
+                                          tab.n_nodes, ops._dev(tab.node, torch.int32), ops._dev(tab.edge, torch.int32) if lookup else None,
+                                          ops._dev(tab.sign), plan.n_edges, ops.NS, None if final else ops._dev(x),
+                                          1 if (advance and not final) else 0, ops._dev(choice, torch.int32),
+                                          ops._dev(nodes[h], torch.int32) if advance else None, ops._dev(err, torch.int32),
+                                          ops._stream()), "scn_hop_select")
+            if rec is not None:
+                trace.append(rec + (choice.cpu().numpy(),))
+            if lookup:
+                i = int(err.item())
+                if i != ops.INT32_MAX:
+                    v = int(cur_h[i])
+                    c = int(choice[i].item())
+                    raise KeyError((v, int(tab.h_node[v, c]) if 0 <= v < tab.n_nodes else -1))
+        return choice.cpu().numpy(), (nodes.cpu().numpy().astype(np.int64) if advance else None)
+
+    def multi_hop_accuracy_binary(self, shifts, inputs, y, mask, nbrhoods, E_lookup, last_nodes, n_nbrs, hops):
+        """Accuracy of greedy multi-hop predictions (STM:110-152), quirks included: the current node (last_nodes) and the readout's
+        last node (inputs[1]) never advance, and n_nbrs stays that of the original node.  Unlike the reference, the caller's flows
+        are not written, and hops < 1 raises ValueError (the reference returns None).  A step across a pair without an edge raises
+        KeyError((node, neighbour)) like the reference's E_lookup."""
+        if int(hops) < 1:
+            raise ValueError("hops must be at least 1")
+        plan = self._multihop_plan(inputs)
+        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
+        choice, _ = self._rollout(inputs, np.asarray(last_nodes), np.asarray(n_nbrs), int(hops), tab, advance=False, fill=-100.0,
+                                  trace=getattr(self, "_multi_hop_trace", None))
+        m = np.asarray(mask) == 1
+        target = np.argmax(np.asarray(y)[m], axis=1).reshape(-1)
+        return float(np.average(choice[m] == target))
+
+    def predict_paths(self, inputs, hops, nbrhoods=None, E_lookup=None):
+        """The greedy rollout done properly: at every hop the current node AND the readout's last node move to the predicted
+        neighbour, and slots at or past the current node's degree are masked (with -inf: a real neighbour is chosen even where every
+        log-probability lies below the reference's -100 fill).  Returns (N, hops) int64 node ids in the caller's
+        numbering.  nbrhoods / E_lookup default to the complex's own (the Bconds object's; for bunch, the nbrhoods table of
+        inputs[0] and the edges of the B1 pattern, keyed (lower id, higher id) as this project's data sets store them)."""
+        if int(hops) < 1:
+            raise ValueError("hops must be at least 1")
+        plan = self._multihop_plan(inputs)
+        if nbrhoods is None:
+            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
+        if E_lookup is None:
+            E_lookup = self._edge_lookup(inputs)
+        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
+        _, nodes = self._rollout(inputs, None, None, int(hops), tab, advance=True, fill=float("-inf"), trace=getattr(self, "_multi_hop_trace", None))
+        return nodes.T.copy()
+
+    def _edge_lookup(self, inputs):
+        src = inputs[0] if self.model_type != 'bunch' else resolve_operands('bunch', self.shifts, inputs[0])[0][1]
+        hit = getattr(self, "_lookup_cache", None)
+        if hit is not None and hit[0] is src:
+            return hit[1]
+        if self.model_type != 'bunch':
+            edges = np.asarray(src.cx.edges)
+        else:
+            B = abs(src.csr).tocsc()                        # S_10 = B1 scaled (BMM): column e holds the two endpoints of edge e
+            B.sort_indices()
+            edges = B.indices.reshape(-1, 2)
+        lookup = {(int(a), int(b)): k for k, (a, b) in enumerate(edges.tolist())}
+        self._lookup_cache = (src, lookup)
+        return lookup
+
+    def multi_hop_target_probs(self, inputs, target_nodes, nbrhoods, E_lookup, last_nodes, hops):
+        """Per-trajectory probability of reaching target_nodes[i] in `hops` steps (STM:154-204): every path of the probability
+        tree is a leaf of its own; NaN where no leaf ends at the target (0 / 0 in the reference)."""
+        if int(hops) < 1:
+            raise ValueError("hops must be at least 1")
+        plan = self._multihop_plan(inputs)
+        tab = ops.step_tables(plan, nbrhoods, E_lookup, "dist")
+        lib = _lib.load()
+        dev = plan.device
+        N = _n_samples(inputs[-1])
+        if len(np.asarray(last_nodes).reshape(-1)) != N or len(np.asarray(target_nodes).reshape(-1)) != N:
+            raise ValueError("last_nodes and target_nodes need one entry per trajectory of inputs (%d)" % N)
+        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+        root = torch.arange(N, device=dev, dtype=torch.int32)
+        node = i32(np.asarray(last_nodes).reshape(-1))
+        prob = torch.ones((N,), device=dev, dtype=torch.float32)
+        path_row = torch.empty((N, 0), device=dev, dtype=torch.int32)
+        path_sign = torch.empty((N, 0), device=dev, dtype=torch.float32)
+        err = torch.empty((1,), device=dev, dtype=torch.int32)
+        D = plan.max_deg
+        for h in range(int(hops)):
+            L = int(root.shape[0])
+            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node, path_row, path_sign, self._mb(plan, L))
+            if h == int(hops) - 1:
+                break
+            cnt = tab.deg[node.long()]
+            offset = (torch.cumsum(cnt, 0) - cnt).to(torch.int32)
+            C = int(cnt.sum().item())                                     # the one copy back per level: the next level's size
+            if C >= ops.INT32_MAX // max(D, 1):
+                raise ValueError("tree level of %d leaves is too large" % C)
+            c_root = torch.empty((C,), device=dev, dtype=torch.int32)
+            c_node = torch.empty_like(c_root)
+            c_prob = torch.empty((C,), device=dev, dtype=torch.float32)
+            c_row = torch.empty((C, h + 1), device=dev, dtype=torch.int32)
+            c_sign = torch.empty((C, h + 1), device=dev, dtype=torch.float32)
+            err.fill_(ops.INT32_MAX)
+            _lib.check(lib.scn_tree_expand(L, h, D, ops._dev(root, torch.int32), ops._dev(node, torch.int32), ops._dev(prob),
+                                           ops._dev(path_row, torch.int32) if h else None, ops._dev(path_sign) if h else None,
+                                           ops._dev(logp), ops._dev(offset, torch.int32), ops._dev(tab.deg, torch.int32), tab.n_nodes,
+                                           ops._dev(tab.node, torch.int32), ops._dev(tab.edge, torch.int32), ops._dev(tab.sign),
+                                           plan.n_edges, C, ops._dev(c_root, torch.int32), ops._dev(c_node, torch.int32),
+                                           ops._dev(c_prob), ops._dev(c_row, torch.int32), ops._dev(c_sign), ops._dev(err, torch.int32),
+                                           ops._stream()), "scn_tree_expand")
+            t = int(err.item())
+            if t != ops.INT32_MAX:
+                v = int(node[t // D].item())
+                raise KeyError(tuple(sorted((v, int(tab.h_node[v, t % D])))))
+            root, node, prob, path_row, path_sign = c_root, c_node, c_prob, c_row, c_sign
+        leaf_ptr = torch.searchsorted(root, torch.arange(N + 1, device=dev, dtype=torch.int32)).to(torch.int32)
+        out = torch.empty((N,), device=dev, dtype=torch.float32)
+        _lib.check(lib.scn_tree_target(N, ops._dev(leaf_ptr, torch.int32), ops._dev(node, torch.int32), ops._dev(prob), ops._dev(logp), D,
+                                       ops._dev(tab.deg, torch.int32), tab.n_nodes, ops._dev(tab.node, torch.int32),
+                                       ops._dev(i32(np.asarray(target_nodes).reshape(-1)), torch.int32), ops._dev(out), ops._stream()),
+                   "scn_tree_target")
+        return out.cpu().numpy().astype(np.float64)
+
+    def multi_hop_accuracy_dist(self, shifts, inputs, target_nodes, masks, nbrhoods, E_lookup, last_nodes, prefixes, hops):
+        """[average target probability over the trajectories of mask for mask in masks] (STM:154-206; prefixes is unused, as in
+        the reference).  The tree of trajectory i starts at last_nodes[i] with the flow inputs[-1][i]; a child SETS its edge to
+        +1 / -1 (not multiplied by the -flip_edges flips); backtracking paths are kept; every path is its own leaf (the reference's
+        tree identifiers can collide -- not reproduced).  hops < 1 raises ValueError."""
+        tp = self.multi_hop_target_probs(inputs, target_nodes, nbrhoods, E_lookup, last_nodes, hops)
+        return [float(np.average(tp[np.asarray(m) == 1])) for m in masks]
 
     # ------------------------------------------------------------------ gradient step (STM:306-310)
     def stage(self, inputs, y, idx, skip=None):

@@ -30,7 +30,8 @@ def hyperparams(args=None):
           'hidden_layers': [(3, 16), (3, 16), (3, 16)], 'describe': 1, 'reverse': 0, 'load_data': 1,
           'load_model': 0, 'markov': 0, 'model_name': 'model', 'regional': 0, 'flip_edges': 0,
           'data_folder_suffix': 'working', 'multi_graph': '', 'holes': 1,
-          'skip_mode': 'dense'}          # not in the reference: dense | zeros | field (exact zero-skipping, Scone_GCN)
+          'skip_mode': 'dense',          # not in the reference: dense | zeros | field (exact zero-skipping, Scone_GCN)
+          'multi_hop': 0}                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
@@ -271,6 +272,10 @@ def train_model(hp=None):
         rev_inputs = [inputs_1hop[0], rev_last_nodes, rev_flows_in]
         results["reverse"] = scone.test(rev_inputs, rev_targets_1hop, test_mask, rev_n_nbrs)
         results["reverse_log_probs"] = scone._predict(scone.weights, rev_inputs).cpu().numpy()
+    if hp.get('multi_hop', 0):                                             # TE:508-510
+        results["multi_hop"] = scone.multi_hop_accuracy_dist(shifts, inputs_1hop, target_nodes_all[1], [train_mask, test_mask],
+                                                             nbrhoods, E_lookup, inputs_1hop[1], prefixes, 2)
+        print('Multi hop accs:', results["multi_hop"])
     scone.experiment_results = results
     return scone, (train_loss, train_acc, test_loss, test_acc)
 

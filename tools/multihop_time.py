@@ -1,0 +1,176 @@
+"""Timing of the device multi-hop probability tree (Scone_GCN.multi_hop_accuracy_dist, STM:154-206).
+
+  (a) the 400-point generated data set, 1000 paths, dist with hops = 2: the device pipeline against a host loop that calls
+      scone_func once per tree leaf (what the reference does with model_single);
+  (b) |E| ~ 1M, 4096 roots (8-step random walks), hops = 2: leaves per second.
+Device-synchronised wall time (torch.cuda.synchronize around the call), after warm-up calls.  Prints one JSON line per case and
+writes them all to --out.
+
+    python tools/multihop_time.py [--case a|b|ab] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import scone_oracle as so                                     # noqa: E402
+from scone_gcn_amd import dataset_io, synthetic_data_gen as g, trajectory_experiments as te   # noqa: E402
+from scone_gcn_amd.complex import SimplicialComplex                        # noqa: E402
+from scone_gcn_amd.scone_trajectory_model import Scone_GCN                # noqa: E402
+from scone_gcn_amd.synthetic_data_gen import SparseFlows                   # noqa: E402
+
+HIDDEN = [(3, 16)] * 3
+
+
+def _net(shifts, inputs, y, seed=0):
+    net = Scone_GCN(1, 1e-3, 100, 0.0, verbose=False)
+    net.setup(te.scone_func, HIDDEN, shifts, inputs, y, None, np.ones(len(y)))
+    rs = np.random.RandomState(seed)
+    net._install([0.3 * rs.randn(*s) for s in so.weight_shapes(1, HIDDEN, 1)])
+    return net
+
+
+def _timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts))
+
+
+def host_loop_target_probs(net, shifts, readout, flows, targets, nbrhoods, E_lookup, last_nodes, hops):
+    """The reference's loop structure (STM:163-204): one scone_func call per leaf, children built on the host."""
+    nb = [n[n != -1] for n in np.asarray(nbrhoods)]
+    out = np.zeros(len(last_nodes))
+    for i in range(len(last_nodes)):
+        leaves = [(int(last_nodes[i]), flows[i].copy(), 1.0)]
+        for _ in range(hops):
+            new = []
+            for v, f, p in leaves:
+                probs = np.exp(te.scone_func(net.weights, *shifts, readout, v, f).cpu().numpy()[:, 0])
+                for j, u in enumerate(nb[v]):
+                    f2 = f.copy()
+                    f2[E_lookup[tuple(sorted((v, int(u))))]] = 1 if v < u else -1
+                    new.append((int(u), f2, p * probs[j]))
+            leaves = new
+        hit = [p for v, _, p in leaves if v == targets[i]]
+        out[i] = sum(hit) / len(hit) if hit else np.nan
+    return out
+
+
+def case_a(reps, host_roots):
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as d:
+        os.chdir(d)
+        try:
+            dataset_io.generate_dataset(400, 1000, folder="mht", holes=True)
+            hp = te.hyperparams(["prog"])
+            inputs_all, y_all, train_mask, test_mask, shifts, _, E_lookup, nbrhoods, _, targets_all, prefixes = \
+                te.data_setup(hops=(1, 2), folder_suffix="mht", hp=hp)
+        finally:
+            os.chdir(cwd)
+    inputs, y = inputs_all[0], y_all[0]
+    net = _net(shifts, inputs, y)
+    N = len(y)
+    args = (shifts, inputs, targets_all[1], [train_mask, test_mask], nbrhoods, E_lookup, inputs[1], prefixes, 2)
+    t_dev = _timed(lambda: net.multi_hop_accuracy_dist(*args), reps)
+    leaves = int(sum(len(nbrhoods[v][nbrhoods[v] >= 0]) for v in inputs[1]))
+    k = min(host_roots, N)
+    X = inputs[-1]
+    sub = X.select(np.arange(k)) if isinstance(X, SparseFlows) else np.asarray(X)[:k]
+    dense = sub.todense() if isinstance(sub, SparseFlows) else sub
+    dev_tp = net.multi_hop_target_probs([inputs[0], inputs[1][:k], sub], targets_all[1][:k], nbrhoods, E_lookup, inputs[1][:k], 2)
+    host_loop_target_probs(net, shifts, inputs[0], dense[:1], targets_all[1][:1], nbrhoods, E_lookup, inputs[1][:1], 2)   # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host_tp = host_loop_target_probs(net, shifts, inputs[0], dense, targets_all[1][:k], nbrhoods, E_lookup, inputs[1][:k], 2)
+    torch.cuda.synchronize()
+    t_host = (time.perf_counter() - t0) * N / k
+    ok = ~np.isnan(host_tp)
+    return {"case": "a", "n_edges": int(dense.shape[1]), "roots": N, "hops": 2, "level1_leaves": leaves,
+            "device_s": t_dev, "device_traj_per_s": N / t_dev, "host_loop_s_extrapolated": t_host, "host_loop_roots_timed": k,
+            "host_loop_traj_per_s": N / t_host, "speedup": t_host / t_dev,
+            "max_abs_diff_vs_host_loop": float(np.abs(dev_tp[ok] - host_tp[ok]).max()) if ok.any() else None}
+
+
+def _say(*a):
+    print("[multihop_time %.0fs]" % (time.perf_counter() - T0), *a, file=sys.stderr, flush=True)
+
+
+T0 = time.perf_counter()
+
+
+def case_b(reps, roots=4096):
+    _say("building the |E| ~ 1M complex")
+    cx = g.random_SC_graph(g.calibrate_n_points(1_000_000))
+    sc = SimplicialComplex(cx)
+    _say("random walks")
+    # uniform random walks of 8 steps from random nodes (generate_random_walks' waypoint paths take many minutes at this size): the
+    # flow of a walk is +1 / -1 on every edge it crosses (SDG:327-344), the walk's end is the last node
+    rs = np.random.RandomState(1)
+    nb = np.asarray(sc.nbrhoods)
+    deg = (nb >= 0).sum(axis=1)
+    walk = [rs.randint(cx.n_nodes, size=roots)]
+    for _ in range(8):
+        v = walk[-1]
+        walk.append(nb[v, (rs.rand(roots) * deg[v]).astype(np.int64)])
+    a, b = np.stack(walk[:-1], 1).ravel(), np.stack(walk[1:], 1).ravel()
+    M = cx.n_nodes
+    code = cx.edges[:, 0].astype(np.int64) * M + cx.edges[:, 1]
+    order = np.argsort(code)
+    idx = order[np.searchsorted(code[order], np.minimum(a, b) * M + np.maximum(a, b))]
+    flows = SparseFlows(np.arange(0, 8 * roots + 1, 8, dtype=np.int64), idx.astype(np.int64),
+                        np.where(a < b, 1.0, -1.0).astype(np.float32), cx.n_edges)
+    last = walk[-1]
+    shifts, readout, _ = te.setup_from_complex(sc, "scone")
+    E_lookup = {(int(p), int(q)): k for k, (p, q) in enumerate(cx.edges.tolist())}
+    _say("data ready")
+    first = [rs.choice(nb[v][nb[v] >= 0]) for v in last]
+    targets = np.array([rs.choice(nb[b][nb[b] >= 0]) for b in first])
+    y = np.zeros((len(last), sc.max_degree, 1))
+    inputs = [readout, last, flows]
+    net = _net(shifts, inputs, y)
+    t_tab = time.perf_counter()
+    net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 1)        # builds and caches the step tables
+    t_tab = time.perf_counter() - t_tab
+    _say("step tables %.1f s; timing" % t_tab)
+    t = _timed(lambda: net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 2), reps)
+    leaves = len(last) + int((nb[last] >= 0).sum())
+    return {"case": "b", "n_edges": int(cx.n_edges), "roots": len(last), "hops": 2, "leaves_evaluated": leaves, "device_s": t,
+            "leaves_per_s": leaves / t, "first_call_hops1_incl_step_tables_s": t_tab}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default="ab")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--host-roots", type=int, default=40)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    res = []
+    if "a" in a.case:
+        res.append(case_a(a.reps, a.host_roots))
+        print(json.dumps(res[-1]), flush=True)
+    if "b" in a.case:
+        res.append(case_b(a.reps))
+        print(json.dumps(res[-1]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
