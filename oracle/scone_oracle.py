@@ -447,3 +447,139 @@ def onehot_targets(choice, D):
     y = np.zeros((len(choice), D, 1))
     y[np.arange(len(choice)), choice, 0] = 1.0
     return y
+
+
+# ----------------------------------------------------------------------------------------------
+# readout at the C-ABI's own layout (include/scone_hip.h: scn_readout_*, scn_node_readout_*)
+#   H [S][E][ns][C] (trajectory n = s * ns + i), nbr [V][D] padded with -1, node-major CSR of B1
+#   (inc_ptr / inc_edge / inc_sign), edge_nodes [E][2].  Every output comes with the sum of |terms|
+#   that sets its error bar ("*_abs"); dz also with its support, the entries the kernels write.
+# ----------------------------------------------------------------------------------------------
+
+ACT_CODES = {0: "none", 1: "tanh", 2: "relu", 3: "leaky_relu"}      # include/scone_hip.h SCN_ACT_*
+
+
+def incidence_csr(edges, n_nodes, flips=None):
+    """B1 (B1[tail, e] = -1, B1[head, e] = +1, both times flips[e]; TE:288-291) as node-major CSR, edges ascending in a
+    row, and the endpoint table: (inc_ptr [V + 1] int32, inc_edge int32, inc_sign float32, edge_nodes [E][2] int32)."""
+    edges = np.asarray(edges, np.int64)
+    E = len(edges)
+    f = np.ones(E) if flips is None else np.asarray(flips, np.float64)
+    node = np.concatenate([edges[:, 0], edges[:, 1]])
+    edge = np.concatenate([np.arange(E), np.arange(E)])
+    sign = np.concatenate([-f, f])
+    order = np.lexsort((edge, node))
+    ptr = np.zeros(n_nodes + 1, np.int64)
+    np.add.at(ptr, node + 1, 1)
+    return (np.cumsum(ptr).astype(np.int32), edge[order].astype(np.int32), sign[order].astype(np.float32),
+            edges.astype(np.int32).reshape(E, 2))
+
+
+def b1_from_csr(inc_ptr, inc_edge, inc_sign, n_edges):
+    """Dense (V, E) fp64 B1 from the node-major CSR."""
+    V = len(inc_ptr) - 1
+    B = np.zeros((V, n_edges))
+    rows = np.repeat(np.arange(V), np.diff(np.asarray(inc_ptr)))
+    B[rows, np.asarray(inc_edge)] = np.asarray(inc_sign, np.float64)
+    return B
+
+
+def act_grad_from_output(act, y):
+    """d act / d z in terms of the activation's OUTPUT y, as the fused kernels take it (scn_internal.h)."""
+    name = ACT_CODES.get(act, act)
+    if name == "tanh":
+        return 1.0 - y * y
+    if name == "relu":
+        return np.where(y > 0, 1.0, 0.0)
+    if name == "leaky_relu":
+        return np.where(y >= 0, 1.0, 0.01)
+    return np.ones_like(y)
+
+
+def _by_trajectory(T):
+    """[S][R][ns](...) -> [N][R](...) with n = s * ns + i."""
+    T = np.asarray(T, np.float64)
+    return np.swapaxes(T, 1, 2).reshape((T.shape[0] * T.shape[2], T.shape[1]) + T.shape[3:])
+
+
+def _log_softmax_bars(logits, logits_abs):
+    lse = logsumexp(logits, axis=1)
+    logp = logits - lse
+    p = np.exp(logp)
+    # logp moves with its own logit and with the logsumexp (d lse / d logit = softmax); the last term covers rounding at |lse|
+    return logp, logits_abs + np.sum(p * logits_abs, axis=1, keepdims=True) + np.abs(lse)
+
+
+def slab_readout_forward(H, w, nbr, last_nodes, inc_ptr, inc_edge, inc_sign):
+    """scn_readout_forward in fp64: bh [N][D][C], logits / logp [N][D] (padding slots: logit 0, inside the logsumexp, TE:151-152)."""
+    S, E, ns, C = H.shape
+    Hn = _by_trajectory(H)                                                         # (N, E, C)
+    B = b1_from_csr(inc_ptr, inc_edge, inc_sign, E)
+    B = np.concatenate([B, np.zeros((1, E))])                                      # row -1: the appended zero row (TE:288)
+    rows = np.asarray(nbr)[np.asarray(last_nodes)]                                 # (N, D)
+    Bc = B[rows]                                                                   # (N, D, E)
+    bh = Bc @ Hn
+    bh_abs = np.abs(Bc) @ np.abs(Hn)
+    w = np.asarray(w, np.float64).reshape(C)
+    logits, logits_abs = bh @ w, bh_abs @ np.abs(w)
+    logp, logp_abs = _log_softmax_bars(logits, logits_abs)
+    return {"bh": bh, "bh_abs": bh_abs, "logits": logits, "logits_abs": logits_abs, "logp": logp, "logp_abs": logp_abs}
+
+
+def _d_logits(d_logp, logp):
+    g, p = np.asarray(d_logp, np.float64), np.exp(np.asarray(logp, np.float64))
+    dl = g - p * g.sum(axis=1, keepdims=True)
+    return dl, np.abs(g) + p * np.abs(g).sum(axis=1, keepdims=True)
+
+
+def slab_readout_backward(H, w, nbr, last_nodes, inc_ptr, inc_edge, inc_sign, bh, d_logp, logp, act):
+    """scn_readout_backward in fp64 from the same inputs (H, bh, d_logp, logp as handed to the kernel):
+    d_logits [N][D], dz [S][E][ns][C] with support [S][E][ns] (edges incident to a live neighbour of the last node), and the
+    d_w_last increment [C] (sum_{n,d} d_logits * bh)."""
+    S, E, ns, C = H.shape
+    N = S * ns
+    Hn = _by_trajectory(H)
+    B = b1_from_csr(inc_ptr, inc_edge, inc_sign, E)
+    B = np.concatenate([B, np.zeros((1, E))])
+    rows = np.asarray(nbr)[np.asarray(last_nodes)]
+    Bc = B[rows]                                                                   # (N, D, E)
+    dl, dl_abs = _d_logits(d_logp, logp)
+    w = np.asarray(w, np.float64).reshape(C)
+    coef = (dl[:, None, :] @ Bc)[:, 0]
+    coef_abs = (dl_abs[:, None, :] @ np.abs(Bc))[:, 0]
+    fac = act_grad_from_output(act, Hn)
+    dz = coef[:, :, None] * w * fac
+    dz_abs = coef_abs[:, :, None] * np.abs(w) * np.abs(fac)
+    support = np.abs(Bc).sum(axis=1) > 0                                           # (N, E)
+    back = lambda T: np.swapaxes(T.reshape((S, ns) + T.shape[1:]), 1, 2)
+    bh = np.asarray(bh, np.float64)
+    return {"d_logits": dl, "d_logits_abs": dl_abs, "dz": back(dz), "dz_abs": back(dz_abs), "support": back(support),
+            "d_w": np.einsum("nd,ndc->c", dl, bh), "d_w_abs": np.einsum("nd,ndc->c", dl_abs, np.abs(bh)),
+            "n_traj": N}
+
+
+def slab_node_readout_forward(X, nbr, last_nodes):
+    """scn_node_readout_forward in fp64: X [S][V][ns]; logits[n, d] = X at node nbr[last[n]][d], -1 wrapping to V - 1 (TE:201)."""
+    S, V, ns = X.shape
+    Xn = _by_trajectory(X)                                                         # (N, V)
+    idx = np.asarray(nbr)[np.asarray(last_nodes)] % V
+    logits = np.take_along_axis(Xn, idx, axis=1)
+    logp, logp_abs = _log_softmax_bars(logits, np.abs(logits))
+    return {"logits": logits, "logp": logp, "logp_abs": logp_abs}
+
+
+def slab_node_readout_backward(X, nbr, last_nodes, d_logp, logp, act):
+    """scn_node_readout_backward in fp64: dz [S][V][ns], the slots of one node (a real neighbour V - 1 and wrapped -1 slots
+    included) adding up."""
+    S, V, ns = X.shape
+    N = S * ns
+    Xn = _by_trajectory(X)
+    idx = np.asarray(nbr)[np.asarray(last_nodes)] % V
+    dl, dl_abs = _d_logits(d_logp, logp)
+    acc, acc_abs = np.zeros((N, V)), np.zeros((N, V))
+    r = np.repeat(np.arange(N), idx.shape[1])
+    np.add.at(acc, (r, idx.ravel()), dl.ravel())
+    np.add.at(acc_abs, (r, idx.ravel()), dl_abs.ravel())
+    fac = act_grad_from_output(act, Xn)
+    back = lambda T: np.swapaxes(T.reshape(S, ns, V), 1, 2)
+    return {"d_logits": dl, "dz": back(acc * fac), "dz_abs": back(acc_abs * np.abs(fac))}
