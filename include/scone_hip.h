@@ -301,6 +301,20 @@ int scn_conv_dw_first(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float*
                       int32_t c_dz, float* const* dW, void* workspace, size_t workspace_bytes,
                       const scn_work_list* wl /* NULL: dense; a list needs y */, void* stream);
 
+/* The first layer's output H1 need not exist in memory.  With out = NULL scn_conv_forward_first writes only y (dense launches),
+ * and the layer that follows is computed from y and the first layer's weight rows:
+ *   H1[p][c] = act(y[p][0] W_first[0][c] + y[p][1] W_first[1][c] + y[p][2] W_first[2][c])    (16 bytes per point instead of 128)
+ * is rebuilt inside the kernels, bit for bit what scn_conv_forward_first stores.
+ * scn_conv_forward_from_y                = scn_conv_forward on that H1 (channels = 32, dense launches),
+ * scn_conv_backward_fused_first_from_y   = scn_conv_backward_fused_first without `aux` (same workspace, channels = 32).
+ * SCN_ERR_UNSUPPORTED for other shapes: store H1 and use the calls above. */
+int scn_conv_forward_from_y(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                            const float* const* W, int32_t channels, int32_t act, float* out, void* stream);
+int scn_conv_backward_fused_first_from_y(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
+                                         const float* const* W_first, int32_t channels, int32_t act, const float* y,
+                                         float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
+                                         const scn_work_list* wl /* NULL: dense */, void* stream);
+
 /* Backward of the layer that FOLLOWS the first one, fused with the first layer's weight gradient (what jax.grad of TE:144-149
  * yields for weights[0:6], STM:307, in one pass):
  *   this layer :  dW[slot] += aux^T G_slot                       (as scn_conv_backward; aux = the first layer's output)

@@ -102,6 +102,12 @@ SIGNATURES = {
     "scn_conv_backward_fused_first": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_i32,
                                                      c_i32, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p,
                                                      c_size_t, ctypes.POINTER(WorkListDesc), c_void_p]),
+    "scn_conv_forward_from_y": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                               c_i32, c_i32, c_void_p, c_void_p]),
+    "scn_conv_backward_fused_first_from_y": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
+                                                            ctypes.POINTER(c_void_p), c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
+                                                            ctypes.POINTER(c_void_p), c_void_p, c_size_t, ctypes.POINTER(WorkListDesc),
+                                                            c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                         ctypes.POINTER(c_void_p)]),
     "scn_terms_forward": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_i32, c_i32,

@@ -91,12 +91,28 @@ __device__ __forceinline__ void first_dw_tile(std::integer_sequence<int, Rs...>,
     (first_dw_step<Rs>(yv, dx[Rs], dwf), ...);
 }
 
+// the aux-free form's side of the same hand-over: value I of the lane group's 48, and the first layer's output at point pt(R, h) in
+// this lane's channel rebuilt from its three (first_layer_value: what fwd_c1_kernel stores)
+template <int I>
+__device__ __forceinline__ float first_y_at(const float (&yv)[3]) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(yv[I / 16]), 0x150 + (I % 16), 0xf, 0xf, false));
+}
+template <int ACT, int... Rs>
+__device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>, const float (&yv)[3], const float (&fwp)[3],
+                                               float (&a)[16]) {
+    ((a[Rs] = first_layer_value(ACT, first_y_at<3 * Rs>(yv), first_y_at<3 * Rs + 1>(yv), first_y_at<3 * Rs + 2>(yv), fwp[0], fwp[1],
+                                fwp[2])), ...);
+}
+
 // FIRST: this layer's input is the FIRST layer's output (aux = H1 = act(y . W_first), y = the shifted 1-channel input saved by
 // scn_conv_forward_first).  The input gradient dx = dL/d(pre-activation of layer 1) is then needed for one thing only -- the
 // first layer's weight gradient dW_first[g][c] = sum_p y[p][g] dx[p][c] -- so it is contracted with y right here, in registers
 // (y is broadcast across the lanes of a half wave with ds_swizzle: 48 cross-lane reads + 48 FMAs per tile), and never written:
 // no 4*E*C-byte dx tensor, no separate streaming kernel over it.  DZ0 carries y in this variant.
-template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false>
+// FROMY (FIRST, plain C = 32): aux = H1 is not read at all -- `fw` carries the first layer's three weight rows and the tile's sixteen
+// aux values per lane are rebuilt from the y records the lane group already holds for dW_first (the same row_newbcast hand-over,
+// first_layer_value: the bits fwd_c1_kernel would have stored), after the zero-tile early-out.
+template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false>
 __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, const float* __restrict__ DZ,
                                                                      const float* __restrict__ DZ0,
                                                                      const float* __restrict__ W0,
@@ -105,8 +121,10 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                                                                      const float* __restrict__ aux,
                                                                      float* __restrict__ dx, float* __restrict__ partial,
                                                                      int n_rows, int n_cols, int n_slabs, WorkList wl,
-                                                                     float* __restrict__ partial_first = nullptr) {
+                                                                     float* __restrict__ partial_first = nullptr,
+                                                                     FirstW fw = FirstW{{nullptr, nullptr, nullptr}}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!FROMY || (FIRST && !PAIR), "the aux-free form exists for the fused-first C = 32 kernel");
     static_assert(!FIRST || !EXT0, "the fused first-layer gradient exists for the plain forms (C = 32, and C = 16 on slab pairs)");
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / BK_THREADS;
     constexpr int CH = PAIR ? 16 : 32;                       // channels of a stored point
@@ -162,6 +180,11 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) dWacc[g][r] = 0.f;
     float dwf[3] = {0.f, 0.f, 0.f};                           // FIRST: this lane's share of dW_first[g][c = p]
+    float fwp[3] = {0.f, 0.f, 0.f};                           // FROMY: the first layer's weights of this lane's channel p
+    if (FROMY) {
+#pragma unroll
+        for (int g = 0; g < 3; ++g) fwp[g] = fw.w[g][p];
+    }
     int e_run = 1 << 20;                                      // running exponent of the dW accumulators (see the header): none yet
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     SCN_UNIT_RANGE();
@@ -231,11 +254,13 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             // (HBM / LDS) is covered by it; they are issued ahead of the next slab's LDS-DMA, so waiting for them later leaves
             // the DMA in flight
             float a[16];
+            if (!FROMY) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const bool ok = 2 * (r >> 2) + h < rows_left && lane_live;
-                const float v = SCN_LD_STREAM(ap + (ok ? L0 + ((r & 3) + 8 * (r >> 2)) * CH : 0));
-                a[r] = ok ? v : 0.f;
+                for (int r = 0; r < 16; ++r) {
+                    const bool ok = 2 * (r >> 2) + h < rows_left && lane_live;
+                    const float v = SCN_LD_STREAM(ap + (ok ? L0 + ((r & 3) + 8 * (r >> 2)) * CH : 0));
+                    a[r] = ok ? v : 0.f;
+                }
             }
             // ACCUM form (plain kernel): DZ0 is a tensor of dx's shape holding the input gradient's partial sum
             // over the output blocks before this one (hidden widths above 32, see fwd_c32_w16_kernel); it may be dx itself
@@ -315,6 +340,12 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                     }
                     STAMP_ADD(4);
                     continue;
+                }
+                if (FROMY) {                                        // aux[pt(r, h)][p] from the tile's y records (value 3 r + g of the lane group's 48)
+                    first_aux_tile<ACT>(std::make_integer_sequence<int, 16>{}, yv, fwp, a);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (!(2 * (r >> 2) + h < rows_left && lane_live)) a[r] = 0.f;
                 }
                 if (umax32(mgb_a, mgb_b) > 0x7f800000u) {           // a NaN in the tile (rare): the scales from the NaN-ignoring maximum
                     asm volatile("; NaN tile: scales without it");

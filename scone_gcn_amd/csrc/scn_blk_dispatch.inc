@@ -101,7 +101,16 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
     dim3 grid;
     const int ci = c_in[0];
     const int nr = c->n_rows, nc = c->g[0].n_cols;
+    const FirstW no_fw{{nullptr, nullptr, nullptr}};
     if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
+    if (!out) {                                                           // first layer, shifted input only (scn_conv_forward_first with out = NULL)
+        if (ci != 1 || !y_out || wl.block) return SCN_ERR_UNSUPPORTED;
+        const size_t lds = smem_bytes(16);
+        launch_grid(c, n_slabs, lds, grid);
+        hipLaunchKernelGGL(gather3_c1_kernel, grid, dim3(BK_THREADS), lds, st, P, src[0], y_out, nr, nc, n_slabs);
+        SCN_LAUNCH_CHECK();
+        return SCN_OK;
+    }
     if (ci == 32) {                                                       // 16 waves, f16 hi + lo split
         const size_t lds16 = smem_bytes_c32(W16_EXTRA_BYTES);
         launch_grid(c, n_slabs, lds16, grid);
@@ -112,11 +121,11 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
         if (partial) {                                                                                            \
             SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, false, true>), lds16);                                          \
             hipLaunchKernelGGL((fwd_c32_w16_kernel<A, false, true>), grid, dim3(W16_THREADS), lds16, st, P, src[0], partial, \
-                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl);                                       \
+                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl, no_fw);                                \
         } else {                                                                                                  \
             SCN_ENSURE_LDS(fwd_c32_w16_kernel<A>, lds16);                                                         \
             hipLaunchKernelGGL(fwd_c32_w16_kernel<A>, grid, dim3(W16_THREADS), lds16, st, P, src[0], (const float*)nullptr, \
-                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl);                                       \
+                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl, no_fw);                                \
         }                                                                                                         \
     } while (0)
         switch (act) {
@@ -153,6 +162,38 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
         else
             hipLaunchKernelGGL(fwd_c1_kernel<16>, grid, dim3(BK_THREADS), lds, st, P, src[0], W[0], W[1], W[2], out, y_out, nr,
                                nc, n_slabs, act, wl);
+    }
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+// Layer 2 of a stack whose first layer has one input channel, straight from the first layer's shifted-input records
+// (fwd_c32_w16_kernel<.., FROMY>): H1 is rebuilt in LDS, never stored.  Dense launches, 32 channels.
+bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
+    return scone_shape(c) && ns == BK_NS && ch == 32 && c->n_rows == c->g[0].n_cols;
+}
+
+int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
+                           float* out, hipStream_t st) {
+    PlanDev P = c->plan.dev;
+    const WorkList wl{0, nullptr, nullptr, nullptr};
+    const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
+    dim3 grid;
+    const size_t lds16 = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
+    launch_grid(c, n_slabs, lds16, grid);
+    P.assign = balanced_assignment(c, grid.x);
+    const int nr = c->n_rows, nc = c->g[0].n_cols;
+#define SCN_LAUNCH_FWDY(A)                                                                                        \
+    do {                                                                                                          \
+        SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, false, false, true>), lds16);                                       \
+        hipLaunchKernelGGL((fwd_c32_w16_kernel<A, false, false, true>), grid, dim3(W16_THREADS), lds16, st, P, y, \
+                           (const float*)nullptr, W[0], W[1], W[2], out, nr, nc, n_slabs, wl, fw);                \
+    } while (0)
+    switch (act) {
+        case SCN_ACT_TANH: SCN_LAUNCH_FWDY(SCN_ACT_TANH); break;
+        case SCN_ACT_RELU: SCN_LAUNCH_FWDY(SCN_ACT_RELU); break;
+        case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWDY(SCN_ACT_LEAKY_RELU); break;
+        default: SCN_LAUNCH_FWDY(SCN_ACT_NONE); break;
     }
     SCN_LAUNCH_CHECK();
     return SCN_OK;
@@ -266,7 +307,7 @@ __global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* _
 
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st) {
+                           hipStream_t st, const float* const* W_first) {   // W_first (32 channels): aux is rebuilt from y, not read
     PlanDev P = c->plan.dev;
     const WorkList wl = wlp ? *wlp : WorkList{0, nullptr, nullptr, nullptr};
     dim3 grid;
@@ -282,9 +323,25 @@ int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const fl
     do {                                                                                                          \
         SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, PAIRV, true>), lds);                                        \
         hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, PAIRV, true>), grid, dim3(BK_THREADS), lds, st, P, dz, y, W[0], \
-                           W[1], W[2], aux, (float*)nullptr, partial, nr, nc, n_slabs, wl, partial_first);        \
+                           W[1], W[2], aux, (float*)nullptr, partial, nr, nc, n_slabs, wl, partial_first,         \
+                           FirstW{{nullptr, nullptr, nullptr}});                                                  \
     } while (0)
-    if (ch == 32) {
+#define SCN_LAUNCH_BWDFY(A)                                                                                       \
+    do {                                                                                                          \
+        SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, false, true, false, true>), lds);                           \
+        hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, false, true, false, true>), grid, dim3(BK_THREADS), lds, st, P, dz, y, \
+                           W[0], W[1], W[2], (const float*)nullptr, (float*)nullptr, partial, nr, nc, n_slabs, wl, partial_first, \
+                           FirstW{{W_first[0], W_first[1], W_first[2]}});                                          \
+    } while (0)
+    if (W_first) {
+        if (ch != 32) return SCN_ERR_UNSUPPORTED;
+        switch (act) {
+            case SCN_ACT_TANH: SCN_LAUNCH_BWDFY(SCN_ACT_TANH); break;
+            case SCN_ACT_RELU: SCN_LAUNCH_BWDFY(SCN_ACT_RELU); break;
+            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDFY(SCN_ACT_LEAKY_RELU); break;
+            default: SCN_LAUNCH_BWDFY(SCN_ACT_NONE); break;
+        }
+    } else if (ch == 32) {
         switch (act) {
             case SCN_ACT_TANH: SCN_LAUNCH_BWDF(SCN_ACT_TANH, false); break;
             case SCN_ACT_RELU: SCN_LAUNCH_BWDF(SCN_ACT_RELU, false); break;
@@ -421,7 +478,7 @@ int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const flo
     do {                                                                                                          \
         SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, true>), lds16);                                                     \
         hipLaunchKernelGGL((fwd_c32_w16_kernel<A, true>), grid, dim3(W16_THREADS), lds16, st, P, x, x0, W[0], W[1], W[2], \
-                           out, nr, nc, n_slabs, wl);                                                             \
+                           out, nr, nc, n_slabs, wl, FirstW{{nullptr, nullptr, nullptr}});                        \
     } while (0)
     switch (act) {
         case SCN_ACT_TANH: SCN_LAUNCH_FWDP(SCN_ACT_TANH); break;

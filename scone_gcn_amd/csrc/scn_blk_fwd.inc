@@ -210,21 +210,32 @@ template <int I> __device__ __forceinline__ void fwd_prio() { __builtin_amdgcn_s
 // ACCUM (plain form only): X0 is a tensor of the output's shape holding partial pre-activations and the
 // result is act(X0 + the three terms) (X0 may be `out` itself: a lane reads exactly the 32 bytes it writes).  Hidden widths above 32
 // run a layer as (input block, output block) pairs of 32 channels; this adds the pairs up without a pass of their own.
-template <int ACT, bool EXT0 = false, bool ACCUM = false>
+// FROMY (plain form only): the layer's input is the FIRST layer's output H1, which is never stored -- X carries the first layer's
+// shifted-input records y[slab][row][trajectory] = (x, S_lo x, S_up x, 0) (16 bytes per point instead of 128) and `fw` the first
+// layer's three weight rows.  Per slab the block's source rows' records are fetched with ordinary 16-byte loads and EXPANDED
+// into the same swizzled LDS image the LDS-DMA builds from a stored H1 (first_layer_value: the bits fwd_c1_kernel would have
+// written), so the gather, the split, the MFMA chain, the early-out and the stores are the plain form's.  Thread = (channel quad
+// tid & 7, trajectory (tid >> 3) & 3, slots (tid >> 5) + 32 i, i = 0..3): four records and four ds_write_b128 per slab, 32
+// consecutive lanes write one whole 512-byte piece.  The records of slab v + 1 are requested at the start of interval v and
+// expanded between the wave's two phases; the slab barrier waits for the LDS writes (lgkmcnt) instead of the LDS-DMA (vmcnt).
+constexpr int W16_FIRSTW_BYTES = 3 * 32 * 4;              // FROMY: the first layer's weights [g][32], behind the plain form's extra bytes
+template <int ACT, bool EXT0 = false, bool ACCUM = false, bool FROMY = false>
 __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, const float* __restrict__ X,
                                                                      const float* __restrict__ X0,
                                                                      const float* __restrict__ W0,
                                                                      const float* __restrict__ W1,
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
-                                                                     int n_slabs, WorkList wl) {
+                                                                     int n_slabs, WorkList wl, FirstW fw) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave
+    static_assert(!FROMY || (!EXT0 && !ACCUM), "the from-y form exists for the plain kernel");
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     char* wfrag = smem + smem_bytes_c32();
     uint8_t* tws = (uint8_t*)(wfrag + W16_WFRAG_BYTES);
     uint32_t* wred = (uint32_t*)(tws + 16);
+    float* fwl = (float*)(smem + smem_bytes_c32(W16_EXTRA_BYTES));   // FROMY only (the launch adds W16_FIRSTW_BYTES)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the wave's four rows are a QUAD of its 8-row group (rows {0,3,5,6} / {1,2,4,7}: the row sets the backward's lane groups
@@ -244,8 +255,14 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         for (int j = 0; j < 8; ++j) w[j] = Wg[(8 * (l >> 4) + j) * 32 + 16 * ct + (l & 15)];
     }
     bool w_bad;                                               // a weight is NaN / Inf: no zero-tile early-out (above block_abs_max)
+    bool fw_bad = false;                                      // FROMY: the first layer's weights count too (0 * Inf: no zero-record short cut)
+    if (FROMY && tid < 96) {
+        const float v = fw.w[tid >> 5][tid & 31];
+        fwl[tid] = v;                                         // (visible after block_abs_max's barrier)
+        fw_bad = not_finite(v);
+    }
     const float sW = pow2_scale(block_abs_max<W16_THREADS>(amax3(amax3(amax3(amax3(0.f, w[0], w[1]), w[2], w[3]), w[4], w[5]), w[6], w[7]),
-                                                           any_not_finite(w), wred, w_bad), invW);
+                                                           any_not_finite(w) || fw_bad, wred, w_bad), invW);
     if (tid < 3 * 2 * 64) {
         const int f = tid;
         const int g = f / 128, ct = (f >> 6) & 1, l = f & 63;
@@ -304,6 +321,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         const uint32_t dchunk = (uint32_t)swz32(((wave & 1) << 1) | (lane >> 5), lane & 31) * 16;
         const int32_t* my_src = sm.srcrows + 2 * wave + (lane >> 5);          // + 32 * k
         auto dma = [&](int k, const char* Xs, int bufi) {
+            if (FROMY) return;                                     // staged by y_load / y_expand below
 #if defined(SCN_FWD_FLOOR) && SCN_FWD_FLOOR == 2                 // diagnostic build (results wrong by design): no staging, gather + contraction + stores only
             return;
 #endif
@@ -314,7 +332,41 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         // listed form loads them with a vector load: left to itself the compiler does slab * slab_bytes in quarter-rate v_mul_*_u32)
         auto slab_at = [&](int it) { return SLAB_AT_U(it); };
         auto slab_base = [&](int slab) { return (const char*)X + (size_t)slab * slab_bytes; };   // SGPR base + 32-bit lane offset in the LDS-DMA
-        {
+        // FROMY staging: this thread's four records of a slab (slots ys_slot + 32 i, trajectory ys_n), then their channel quad ys_cq
+        // of H1 into the image: piece chunk ys_n * 8 + ys_cq of slot s lives at s * 512 + swz32(s, chunk) * 16 (what the LDS-DMA builds)
+        const int ys_cq = tid & 7, ys_n = (tid >> 3) & 3, ys_slot = tid >> 5;
+        typedef float f32x3 __attribute__((ext_vector_type(3)));   // (the record's fourth float is padding: 12 registers, not 16)
+        f32x3 yr[NDMA];
+        auto y_load = [&](int slab) {
+            const char* Ys = (const char*)X + (size_t)slab * n_cols * (BK_NS * Y_STRIDE * 4);
+#pragma unroll
+            for (int i = 0; i < NDMA; ++i) {
+                const int s = ys_slot + 32 * i;
+                if (s < m.nsrc) yr[i] = *(const f32x3*)(Ys + ((size_t)(uint32_t)sm.srcrows[s] * BK_NS + ys_n) * (Y_STRIDE * 4));
+            }
+        };
+        auto y_expand = [&](int bufi) {
+            const f32x4 f0 = *(const f32x4*)(fwl + 4 * ys_cq), f1 = *(const f32x4*)(fwl + 32 + 4 * ys_cq),
+                        f2 = *(const f32x4*)(fwl + 64 + 4 * ys_cq);
+#pragma unroll
+            for (int i = 0; i < NDMA; ++i) {
+                const int s = ys_slot + 32 * i;
+                const bool live = s < m.nsrc;                       // (s is uniform over 32 lanes: half-wave granular)
+                const uint32_t bits = live ? (__float_as_uint(yr[i][0]) | __float_as_uint(yr[i][1]) | __float_as_uint(yr[i][2])) : 0u;
+                // records that are all zero BITS expand to zeros without the FMAs and the activation (decided per wave; -0, NaN and Inf
+                // are not zero bits, and a non-finite first-layer weight turns the short cut off: 0 * Inf is NaN)
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (w_bad || __builtin_amdgcn_ballot_w64(bits != 0u) != 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = first_layer_value(ACT, yr[i][0], yr[i][1], yr[i][2], f0[j], f1[j], f2[j]);
+                }
+                if (live) *(f32x4*)(sm.buf(bufi) + s * PIECE + swz32(s, ys_n * 8 + ys_cq) * 16) = v;
+            }
+        };
+        if (FROMY) {
+            y_load(slab_at(0));
+            y_expand(0);
+        } else {
             const char* Xs = slab_base(slab_at(0));
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma(i, Xs, 0);
@@ -324,7 +376,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         // behind waves 0-7 (every SIMD hosts two of each): while one half gathers slab v the other contracts slab v - 1, between
         // the same two slab barriers.  A late wave carries its gathered z across the barrier; its share of the next LDS-DMA is one
         // visit further ahead (slab v + 2), the early waves' as before (slab v + 1).
-        if (late && n_it > 1) {                        // the late waves' share of slab 1 has no contraction to ride in
+        if (!FROMY && late && n_it > 1) {              // the late waves' share of slab 1 has no contraction to ride in
             const char* Xs = slab_base(slab_at(1));
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma(i, Xs, 1);
@@ -454,20 +506,27 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         for (int v = 0; v <= n_it; ++v) {
             STAMP_START();
 #ifndef SCN_FWD_FREERUN               // (diagnostic build, results WRONG by design: no slab barrier at all -- the no-synchronisation floor)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // FROMY: the image of slab v was WRITTEN by this workgroup's waves (and every LDS read of the buffer it replaces has
+            // returned): wait for the LDS queue; stores and record loads stay in flight across the barrier
+            if (FROMY) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             STAMP_ADD(0);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
 #endif
             STAMP_ADD(1);
+            const bool stage = FROMY && v + 1 < n_it;          // both halves stage slab v + 1 during interval v
+            if (stage) y_load(slab_at(v + 1));
             if (!late) {
                 if (v < n_it) {
                     SCN_FWD_PRIO_GATHER();
                     gather_phase(v);
+                    if (stage) y_expand((v + 1) & 1);
                     contract_phase(v);
                 }
             } else {
                 if (v > 0) contract_phase(v - 1);
+                if (stage) y_expand((v + 1) & 1);
                 SCN_FWD_PRIO_GATHER();
                 if (v < n_it) gather_phase(v);
             }
@@ -759,9 +818,9 @@ __global__ __launch_bounds__(BK_THREADS, 6) void fwd_c1_kernel(PlanDev P, const 
             for (int idx = tid; idx < total; idx += BK_THREADS) {
                 const int pt = idx / CQ;
                 const float zs = Zs[pt * 3], zl = Zs[pt * 3 + 1], zu = Zs[pt * 3 + 2];
-                f32x4 v = zs * w0 + zl * w1 + zu * w2;
-                v[0] = act_apply_fast(act, v[0]); v[1] = act_apply_fast(act, v[1]);
-                v[2] = act_apply_fast(act, v[2]); v[3] = act_apply_fast(act, v[3]);
+                f32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = first_layer_value(act, zs, zl, zu, w0[j], w1[j], w2[j]);
                 __builtin_nontemporal_store(v, (f32x4*)(o + (size_t)idx * 4));   // streamed out: keep the L2 for the gathered input
             }
         }

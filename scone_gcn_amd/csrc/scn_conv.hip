@@ -38,7 +38,10 @@ bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch);
 size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st);
+                           hipStream_t st, const float* const* W_first = nullptr);
+bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
+int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
+                           float* out, hipStream_t st);
 int build_terms_plan(scn_conv_s* c, const uint8_t* term, const int32_t* lvl_row0, const uint8_t* merged, const int32_t* bins,
                      int group_rows);
 int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
@@ -593,13 +596,39 @@ int scn_conv_backward_fused_first(scn_conv_t c, int32_t n_slabs, int32_t ns, con
 
 int scn_conv_forward_first(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, const float* const* W, int32_t c_out,
                            int32_t act, float* out, float* y_out, const scn_work_list* wl, void* stream) {
-    if (!c || !x || !W || !W[0] || !W[1] || !W[2] || !out || !y_out || !valid_list(wl)) return SCN_ERR_BAD_ARG;
+    if (!c || !x || !W || !W[0] || !W[1] || !W[2] || !y_out || !valid_list(wl)) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (!out && wl) return SCN_ERR_UNSUPPORTED;        // y only: dense launches
     const int32_t c_in = 1;
     if (c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, c_out)) return SCN_ERR_UNSUPPORTED;
     WorkList wlist{0, nullptr, nullptr, nullptr};
     if (wl) wlist = to_list(wl);
     return blocked_forward(c, n_slabs, ns, &x, &c_in, W, c_out, act, out, y_out, wl ? &wlist : nullptr, (hipStream_t)stream);
+}
+
+int scn_conv_forward_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                            const float* const* W, int32_t channels, int32_t act, float* out, void* stream) {
+    if (!c || !y || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !W || !W[0] || !W[1] || !W[2] || !out)
+        return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream);
+}
+
+int scn_conv_backward_fused_first_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
+                                         const float* const* W_first, int32_t channels, int32_t act, const float* y,
+                                         float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
+                                         const scn_work_list* wl, void* stream) {
+    if (!c || !dz || !W || !W[0] || !W[1] || !W[2] || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !y || !dW ||
+        !dW[0] || !dW[1] || !dW[2] || !dW_first || !dW_first[0] || !dW_first[1] || !dW_first[2] || !workspace || !valid_list(wl))
+        return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535 || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (workspace_bytes < blocked_backward_first_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
+    WorkList wlist{0, nullptr, nullptr, nullptr};
+    if (wl) wlist = to_list(wl);
+    return blocked_backward_first(c, n_slabs, dz, W, nullptr, channels, act, y, dW, dW_first, workspace, wl ? &wlist : nullptr,
+                                  (hipStream_t)stream, W_first);
 }
 
 int scn_clear_list(scn_conv_t c, int32_t ns, int32_t channels, float* tensor, const scn_work_list* wl, void* stream) {

@@ -51,6 +51,15 @@ __device__ __forceinline__ float act_apply_fast(int act, float z) {
         default: return z;
     }
 }
+// One value of the first layer's output (1 -> C channels): H1[p][c] = act(x w0[c] + (S_lo x) w1[c] + (S_up x) w2[c]) from the point's
+// shifted-input record y[p] = (ys, yl, yu, 0).  The ONE definition: fwd_c1_kernel writes it, the from-y forward and the aux-free
+// fused-first backward rebuild it instead of reading it back, and all three must round alike -- every multiply-add spelled out
+// (see adam_update for what contraction does otherwise).
+__device__ __forceinline__ float first_layer_value(int act, float ys, float yl, float yu, float w0, float w1, float w2) {
+    return act_apply_fast(act, __builtin_fmaf(yu, w2, __builtin_fmaf(yl, w1, ys * w0)));
+}
+// first-layer weight rows handed to the kernels that rebuild H1 (by value; all null elsewhere)
+struct FirstW { const float* w[3]; };
 __device__ __forceinline__ float act_apply(int act, float z) {
     switch (act) {
         case SCN_ACT_TANH: return tanhf(z);

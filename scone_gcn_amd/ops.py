@@ -77,6 +77,10 @@ def _nbytes(*tensors):
 # Module switches for tests and same-box A/B runs (set them from Python; the one environment variable read here is SCN_SMALL_STEP, once,
 # at import):
 FUSE_FIRST = True      # False: separate scn_conv_backward + scn_conv_dw_first instead of the fused-first backward
+# The first layer's output H1 is 128 bytes per point that follow from the 16-byte shifted-input record y and 96 weights: the plain scone
+# stack at hidden 32 never stores it -- layer 1 writes y only, layer 2's forward expands y into its LDS image and the fused-first backward
+# rebuilds its aux values in registers (SconePlan.conv_stack / _backward).  False: H1 is materialised (the path every other shape takes).
+RECOMPUTE_FIRST = True
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
 # step, one launch against the layer-by-layer kernels, ms (tools/small_step.py, profiles/r04_small_step_ab.txt):
@@ -305,6 +309,42 @@ class ConvOp:
         check(st, "scn_conv_forward_first")
         return out, y
 
+    def shifted_input(self, x):
+        """y = (x, S_lo x, S_up x, 0) per point of a 1-channel input WITHOUT the first layer's output (scn_conv_forward_first with
+        out = NULL); None when the shape is not served."""
+        lib = _lib.load()
+        S, rows, ns, c_in = x.shape
+        if c_in != 1 or self.n_groups != 1 or self.n_slots != 3:
+            return None
+        y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
+        dummy = ptr_array([_dev(x).value] * 3)        # (the weights are not read without an output; the call checks them for NULL)
+        with _timed("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes):
+            st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
+        if st == _lib.SCN_ERR_UNSUPPORTED:
+            return None
+        check(st, "scn_conv_forward_first")
+        return y
+
+    def forward_from_y(self, y, Ws_first, Ws, act):
+        """The layer AFTER a 1-channel first layer from that layer's shifted input y and weights Ws_first: act(sum_s (S_s H1) Ws[s]) with
+        H1 rebuilt inside the kernel (scn_conv_forward_from_y); None when the shape is not served."""
+        lib = _lib.load()
+        S, rows, ns, _ = y.shape
+        c = Ws[0].shape[1]
+        if self.n_groups != 1 or self.n_slots != 3 or rows != self.n_rows or any(tuple(w.shape) != (c, c) for w in Ws) or \
+                any(tuple(w.shape) != (1, c) for w in Ws_first):
+            return None
+        out = torch.empty((S, self.n_rows, ns, c), device=y.device, dtype=torch.float32)
+        # (the key of the plain C -> C forward: the same kernel family, and what callers that look for the fused layer kernels expect;
+        # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
+        with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y, out) + self.csr_bytes):
+            st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), ptr_array([_dev(w).value for w in Ws_first]),
+                                             ptr_array([_dev(w).value for w in Ws]), c, ACT[act], _dev(out), _stream())
+        if st == _lib.SCN_ERR_UNSUPPORTED:
+            return None
+        check(st, "scn_conv_forward_from_y")
+        return out
+
     def forward_power(self, x0, x, Ws, act):
         """out = act(x0 W0 + x W1 + (S x) W2) for an operator with identity + one value array (scn_conv_forward_power);
         None when the shape is not served."""
@@ -335,18 +375,31 @@ class ConvOp:
                                               ws.numel(), _stream()), "scn_conv_backward_power")
         return True, dx
 
-    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None):
+    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None):
         """Backward of the layer after the first one, fused with the first layer's weight gradient: dWs (this layer) and
         dWs_first are accumulated, the input gradient is never written (scn_conv_backward_fused_first).  False when the shape
-        is not served."""
+        is not served.  aux = None with Ws_first (the first layer's weights): the first layer's output is rebuilt from y
+        inside the kernel instead of being read (scn_conv_backward_fused_first_from_y, 32 channels)."""
         lib = _lib.load()
         S, rows, ns, c = dz.shape
-        if tuple(aux.shape) != (S, rows, ns, c) or tuple(y.shape) != (S, rows, ns, Y_STRIDE) or self.n_groups != 1:
+        if (aux is not None and tuple(aux.shape) != (S, rows, ns, c)) or tuple(y.shape) != (S, rows, ns, Y_STRIDE) or self.n_groups != 1:
+            return False
+        if aux is None and (Ws_first is None or c != 32):
             return False
         nbytes = int(lib.scn_conv_backward_fused_first_workspace(self.handle, S, ns, c))
         if nbytes == 0:
             return False
         ws = torch.empty(nbytes, device=dz.device, dtype=torch.uint8)
+        if aux is None:
+            with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, y) + self.csr_bytes):
+                check(lib.scn_conv_backward_fused_first_from_y(self.handle, S, ns, _dev(dz), ptr_array([_dev(w).value for w in Ws]),
+                                                               ptr_array([_dev(w).value for w in Ws_first]), c, ACT[act], _dev(y),
+                                                               ptr_array([_dev(d).value for d in dWs]),
+                                                               ptr_array([_dev(d).value for d in dWs_first]),
+                                                               ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                                               wl.ref() if wl is not None else None, _stream()),
+                      "scn_conv_backward_fused_first_from_y")
+            return True
         with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, aux, y) + self.csr_bytes):
             check(lib.scn_conv_backward_fused_first(self.handle, S, ns, _dev(dz), ptr_array([_dev(w).value for w in Ws]), _dev(aux),
                                                     c, ACT[act], _dev(y), ptr_array([_dev(d).value for d in dWs]),
@@ -801,6 +854,17 @@ class SconePlan:
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:141-142
         hs, y0 = [x], None
         S, E, ns, _ = x.shape
+        if self._recompute_first(x, weights, activity):
+            # hidden 32 throughout, 1-channel input, dense: H1 is never stored (hs[1] is None).  Layer 1 writes the shifted input y
+            # only, layer 2 expands it in LDS; the backward sees hs[1] is None and rebuilds its aux values from y (see _backward)
+            y0 = self.conv.shifted_input(x)
+            h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act) if y0 is not None else None
+            if h2 is not None:
+                hs += [None, h2]
+                for i in range(2, int(n_layers)):
+                    hs.append(self.conv.forward([hs[-1]], weights[3 * i:3 * i + 3], 32, self.act))
+                return hs, y0
+            y0 = None
         for i in range(int(n_layers)):
             w = weights[3 * i:3 * i + 3]
             c_out = w[0].shape[1]
@@ -817,6 +881,14 @@ class SconePlan:
             else:
                 hs.append(self.conv.forward([hs[-1]], w, c_out, self.act, out=out, wl=wl))
         return hs, y0
+
+    def _recompute_first(self, x, weights, activity):
+        """Whether this stack runs without a stored H1: plain scone plan, 1-channel input, every hidden width 32 (no promotion), at
+        least two layers, dense launches, symmetric or not.  All observed, not chosen; RECOMPUTE_FIRST is the tests' and A/B's switch."""
+        L = (len(weights) - 1) // 3
+        return (RECOMPUTE_FIRST and FUSE_FIRST and type(self) is SconePlan and activity is None and x.shape[3] == 1 and L >= 2
+                and x.shape[2] == NS and self._blocked()
+                and [tuple(w.shape) for w in weights[:-1]] == [(1, 32)] * 3 + [(32, 32)] * (3 * (L - 1)))
 
     # -- zero-skipping mode ---------------------------------------------------------------------------------
     def _block_graph(self):
@@ -1154,7 +1226,12 @@ class SconePlan:
             wl_out = activity["bwd"][i] if (activity and i > 0) else None      # items of this layer's input gradient
             wl_in = activity["bwd"][i + 1] if activity else None                # support of dz
             dz_in = dz
-            if i == 1 and hs[0].shape[3] == 1 and y0 is not None and FUSE_FIRST and \
+            if i == 1 and hs[1] is None:                # the forward ran without a stored H1 (conv_stack): aux is rebuilt from y0
+                assert self.conv_T.backward_fused_first(dz, weights[3:6], None, self.act, y0, grads[3:6], grads[0:3],
+                                                        Ws_first=weights[0:3]), "aux-free fused-first backward not served"
+                fused_first = True
+                dz = None
+            elif i == 1 and hs[0].shape[3] == 1 and y0 is not None and FUSE_FIRST and \
                     self.conv_T.backward_fused_first(dz, weights[3:6], hs[1], self.act, y0, grads[3:6], grads[0:3], wl=wl_out):
                 fused_first = True                      # dx of this layer only feeds dW_first: contracted in registers, never written
                 dz = None
