@@ -503,6 +503,30 @@ int scn_tree_slabs(int32_t n_leaves, int32_t n_slabs, int32_t h, const int32_t* 
  *   STM:199-204).  One wave per root, fixed summation order, no atomics: bitwise repeatable. */
 int scn_tree_target(int32_t n_roots, const int32_t* leaf_ptr, const int32_t* node, const float* prob, const float* logp, int32_t d,
                     const int32_t* deg, int32_t n_nodes, const int32_t* step_node, const int32_t* target, float* out, void* stream);
+/* scn_beam_step: level h -> h + 1 of a beam search.  Entries are root-major with a fixed stride: entry (r, k), k < w_in, of the input
+ *   level sits at r * w_in + k and carries node, score (the fp32 sum of the log-probabilities along its path) and, for h > 0, its
+ *   path as h (device row, value) pairs (the path_row / path_sign layout of scn_tree_expand); node = -1 marks a dead entry (fewer
+ *   than w_in paths exist), and logp[(r * w_in + k)][0..d) is the forward's output for it.  The candidates of root r are every (k, j)
+ *   with k live and j < deg[node]; each scores score[k] + logp[k][j] (one fp32 add).  The best w_out of them go to r * w_out + 0 ..
+ *   w_out - 1 in this total order: a NaN score before every number (the np.argmax rule of scn_hop_select), then the higher score,
+ *   and among equal scores the lower k, then the lower j.  Child o gets c_root = r, c_node = step_node[v][j], c_score, c_parent = k,
+ *   c_slot = j and -- unless c_path_row is NULL (final level) -- the parent's path plus (step_edge[v][j], step_sign[v][j])
+ *   ([r * w_out + o][h + 1]).  Where fewer than w_out candidates exist the rest are written dead: c_root = c_node = c_parent =
+ *   c_slot = -1, c_score = -inf, path rows -1 (scn_tree_slabs writes a zero column for root -1 and skips a row of -1).  Every
+ *   candidate of a live entry whose pair has no edge (step_edge < 0 or >= n_rows, or step_node < 0) lowers err[0] to
+ *   (r * w_in + k) * d + j (atomicMin; the caller initialises it to INT32_MAX), selected or not.  Such a candidate still takes
+ *   its place in the order and, if selected, is written as the tables give it: c_root = r with c_node possibly -1 and a path row
+ *   that is -1 or >= n_rows (scn_tree_slabs skips such a row; an entry with node -1 is dead at the next level) -- the caller
+ *   reads err and discards the level.  A node id outside [0, n_nodes) other than the -1 of a dead entry is a caller's error the
+ *   library only guards against: the entry is treated as dead, nothing is read through it and err is not lowered.  One wave per root, no float
+ *   atomics: bitwise repeatable.  The outputs must not overlap the inputs.  w_in, w_out <= SCN_BEAM_MAX (SCN_ERR_UNSUPPORTED
+ *   beyond), any d. */
+#define SCN_BEAM_MAX 256
+int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32_t d, const int32_t* node, const float* score,
+                  const int32_t* path_row, const float* path_sign, const float* logp, const int32_t* deg, int32_t n_nodes,
+                  const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows, int32_t* c_root,
+                  int32_t* c_node, float* c_score, int32_t* c_parent, int32_t* c_slot, int32_t* c_path_row, float* c_path_sign,
+                  int32_t* err, void* stream);
 
 #ifdef __cplusplus
 }

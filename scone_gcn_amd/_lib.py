@@ -19,6 +19,7 @@ SCN_MAX_SLOTS = 4
 ACT = {"none": 0, "tanh": 1, "relu": 2, "leaky_relu": 3}
 SCN_ERR_BAD_ARG = -1              # include/scone_hip.h
 SCN_ERR_UNSUPPORTED = -4
+SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
 
 
 class WorkListDesc(ctypes.Structure):          # scn_work_list (device pointers)
@@ -142,6 +143,9 @@ SIGNATURES = {
                                       c_void_p]),
     "scn_tree_target": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "scn_beam_step": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

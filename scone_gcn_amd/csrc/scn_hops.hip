@@ -1,6 +1,6 @@
-// Multi-hop prediction (STM:110-206): the device steps between the forwards of a greedy rollout or of a probability tree.
-// The forwards themselves are the fused layer kernels; these kernels choose the next node, look up the edge it crosses, build the
-// child flow slabs and reduce the leaf probabilities per trajectory, so that no level of a rollout or of a tree goes through the host.
+// Multi-hop prediction (STM:110-206): the device steps between the forwards of a greedy rollout, of a probability tree or of a beam
+// search.  The forwards themselves are the fused layer kernels; these kernels choose the next node, look up the edge it crosses, build
+// the child flow slabs, prune a beam and reduce the leaf probabilities per trajectory, so that no level goes through the host.
 #include "scn_internal.h"
 
 #include <climits>
@@ -144,6 +144,120 @@ __global__ __launch_bounds__(64) void tree_target_kernel(int n_roots, const int3
     if (lane == 0) out[r] = cnt ? s / (float)cnt : __builtin_nanf("");     // 0 / 0 in the reference (STM:203)
 }
 
+// The beam's total order as one 64-bit key, higher = earlier: the score mapped to an unsigned that orders like the float (a NaN
+// above +inf, -0 with +0), then the candidate's index c = k * d + j counted down, so equal scores fall to the lower k, then the lower
+// j.  Keys of distinct candidates differ, none is 0 (the score half of -inf is 0x007fffff) and none is ~0.
+__device__ __forceinline__ unsigned long long beam_key(float s, int c) {
+    unsigned u;
+    if (isnan(s)) {
+        u = 0xffffffffu;
+    } else {
+        const unsigned b = __float_as_uint(s == 0.f ? 0.f : s);
+        u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - c);
+}
+
+// one wave per root.  Round o finds, lane-strided over the root's w_in * d candidates and then by a shuffle butterfly, the highest key
+// strictly below round o - 1's winner: no bookkeeping, any d, and nothing depends on the order lanes or blocks run in.
+__global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int h, int d, const int32_t* __restrict__ node,
+                                                       const float* __restrict__ score, const int32_t* __restrict__ path_row,
+                                                       const float* __restrict__ path_sign, const float* __restrict__ logp,
+                                                       const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
+                                                       const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
+                                                       int n_rows, int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
+                                                       float* __restrict__ c_score, int32_t* __restrict__ c_parent,
+                                                       int32_t* __restrict__ c_slot, int32_t* __restrict__ c_path_row,
+                                                       float* __restrict__ c_path_sign, int32_t* err) {
+    __shared__ int s_node[SCN_BEAM_MAX];
+    __shared__ int s_lim[SCN_BEAM_MAX];              // slots of entry k that are candidates: deg[node], 0 for a dead entry
+    __shared__ float s_score[SCN_BEAM_MAX];
+    const int r = blockIdx.x;
+    const int lane = threadIdx.x;
+    const size_t in0 = (size_t)r * w_in;
+    for (int k = lane; k < w_in; k += 64) {
+        const int v = node[in0 + k];
+        const bool live = v >= 0 && v < n_nodes;
+        const int dv = live ? deg[v] : 0;
+        s_node[k] = live ? v : -1;
+        s_lim[k] = dv < 0 ? 0 : (dv > d ? d : dv);
+        s_score[k] = score[in0 + k];
+    }
+    __syncthreads();
+    const float* __restrict__ lp = logp + in0 * d;
+    const int n_cand = w_in * d;
+    // candidate c = k * d + j of lane `lane` advances by 64: (k, j) += (64 / d, 64 % d) with one carry
+    const int k0 = lane / d, j0 = lane % d, dk = 64 / d, dj = 64 % d;
+    for (int c = lane, k = k0, j = j0; c < n_cand; c += 64) {
+        if (j < s_lim[k]) {
+            const size_t t = (size_t)s_node[k] * d + j;
+            const int e = step_edge[t];
+            if (e < 0 || e >= n_rows || step_node[t] < 0) atomicMin(err, (int)(in0 * d) + c);
+        }
+        k += dk;
+        j += dj;
+        if (j >= d) {
+            j -= d;
+            ++k;
+        }
+    }
+    const size_t out0 = (size_t)r * w_out;
+    unsigned long long prev = ~0ull;
+    int o = 0;
+    for (; o < w_out; ++o) {
+        unsigned long long best = 0;
+        for (int c = lane, k = k0, j = j0; c < n_cand; c += 64) {
+            if (j < s_lim[k]) {
+                const unsigned long long key = beam_key(s_score[k] + lp[c], c);
+                if (key < prev && key > best) best = key;
+            }
+            k += dk;
+            j += dj;
+            if (j >= d) {
+                j -= d;
+                ++k;
+            }
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const unsigned long long other = __shfl_xor(best, m, 64);
+            best = other > best ? other : best;
+        }
+        if (best == 0) break;                                             // (wave-uniform) every candidate is placed
+        prev = best;
+        const int c = 0x7fffffff - (int)(unsigned)(best & 0xffffffffu);
+        const int k = c / d, j = c - k * d;
+        const size_t t = (size_t)s_node[k] * d + j;
+        if (lane == 0) {
+            c_root[out0 + o] = r;
+            c_node[out0 + o] = step_node[t];
+            c_score[out0 + o] = s_score[k] + lp[c];
+            c_parent[out0 + o] = k;
+            c_slot[out0 + o] = j;
+        }
+        if (c_path_row) {
+            const size_t dst = (out0 + o) * (size_t)(h + 1), src = (in0 + k) * (size_t)h;
+            for (int q = lane; q <= h; q += 64) {
+                c_path_row[dst + q] = q < h ? path_row[src + q] : step_edge[t];
+                c_path_sign[dst + q] = q < h ? path_sign[src + q] : step_sign[t];
+            }
+        }
+    }
+    for (int p = o + lane; p < w_out; p += 64) {                          // fewer than w_out candidates: the rest are dead
+        c_root[out0 + p] = -1;
+        c_node[out0 + p] = -1;
+        c_score[out0 + p] = -__builtin_inff();
+        c_parent[out0 + p] = -1;
+        c_slot[out0 + p] = -1;
+        if (c_path_row) {
+            for (int q = 0; q <= h; ++q) {
+                c_path_row[(out0 + p) * (size_t)(h + 1) + q] = -1;
+                c_path_sign[(out0 + p) * (size_t)(h + 1) + q] = 0.f;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -211,6 +325,25 @@ int scn_tree_target(int32_t n_roots, const int32_t* leaf_ptr, const int32_t* nod
     if (!leaf_ptr || !node || !prob || !logp || !deg || !step_node || !target || !out) return SCN_ERR_BAD_ARG;
     hipLaunchKernelGGL(tree_target_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, n_roots, leaf_ptr, node, prob, logp,
                        d, deg, n_nodes, step_node, target, out);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32_t d, const int32_t* node, const float* score,
+                  const int32_t* path_row, const float* path_sign, const float* logp, const int32_t* deg, int32_t n_nodes,
+                  const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows, int32_t* c_root,
+                  int32_t* c_node, float* c_score, int32_t* c_parent, int32_t* c_slot, int32_t* c_path_row, float* c_path_sign,
+                  int32_t* err, void* stream) {
+    if (n_roots < 0 || w_in <= 0 || w_out <= 0 || h < 0 || d <= 0 || n_nodes <= 0 || n_rows <= 0) return SCN_ERR_BAD_SHAPE;
+    if (w_in > SCN_BEAM_MAX || w_out > SCN_BEAM_MAX) return SCN_ERR_UNSUPPORTED;
+    if ((int64_t)n_roots * w_in * d >= INT_MAX || (int64_t)n_roots * w_out >= INT_MAX) return SCN_ERR_UNSUPPORTED;
+    if (n_roots == 0) return SCN_OK;
+    if (!node || !score || !logp || !deg || !step_node || !step_edge || !step_sign || !err) return SCN_ERR_BAD_ARG;
+    if (!c_root || !c_node || !c_score || !c_parent || !c_slot) return SCN_ERR_BAD_ARG;
+    if (c_path_row && (!c_path_sign || (h > 0 && (!path_row || !path_sign)))) return SCN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, w_in, w_out, h, d, node, score,
+                       path_row, path_sign, logp, deg, n_nodes, step_node, step_edge, step_sign, n_rows, c_root, c_node, c_score,
+                       c_parent, c_slot, c_path_row, c_path_sign, err);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

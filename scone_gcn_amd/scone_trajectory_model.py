@@ -450,6 +450,88 @@ class Scone_GCN():
         _, nodes = self._rollout(inputs, None, None, int(hops), tab, advance=True, fill=float("-inf"), trace=getattr(self, "_multi_hop_trace", None))
         return nodes.T.copy()
 
+    def predict_paths_beam(self, inputs, hops, beam, nbrhoods=None, E_lookup=None):
+        """Beam search with the semantics of predict_paths (current and readout node advance, a step SETS its edge, backtracking
+        allowed, "binary" step tables, same defaults): the `beam` most likely continuations of every trajectory.  Returns
+        (paths (N, beam, hops) int64 node ids, logp (N, beam) float64 = the summed log-probabilities), best first per trajectory;
+        where fewer than `beam` paths of that length exist the tail is -1 / -inf.  Level h holds W_h = min(beam, W_{h-1} * max_deg)
+        entries per trajectory (W_0 = 1), a size the host knows without a copy back: one batched forward over N * W_h entries, then
+        scn_beam_step keeps the best W_{h+1} children per trajectory (order: include/scone_hip.h).  beam = 1 is predict_paths, a
+        beam as wide as the tree is the probability tree.  The error words of all levels are read once, at the end."""
+        hops, beam = int(hops), int(beam)
+        if hops < 1:
+            raise ValueError("hops must be at least 1")
+        if beam < 1 or beam > _lib.SCN_BEAM_MAX:
+            raise ValueError("beam must be between 1 and %d (SCN_BEAM_MAX)" % _lib.SCN_BEAM_MAX)
+        plan = self._multihop_plan(inputs)
+        if nbrhoods is None:
+            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
+        if E_lookup is None:
+            E_lookup = self._edge_lookup(inputs)
+        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
+        lib = _lib.load()
+        dev = plan.device
+        N, D = _n_samples(inputs[-1]), plan.max_deg
+        if len(np.asarray(inputs[1]).reshape(-1)) != N:
+            raise ValueError("last nodes need one entry per trajectory of inputs (%d)" % N)
+        if N * beam * D >= ops.INT32_MAX:
+            raise ValueError("beam level of %d x %d entries is too large" % (N, beam))
+        trace = getattr(self, "_multi_hop_trace", None)
+        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)          # a copy: the caller's flows stay as they are
+        i32, f32 = (lambda *s: torch.empty(s, device=dev, dtype=torch.int32)), (lambda *s: torch.empty(s, device=dev, dtype=torch.float32))
+        p = lambda t: None if t is None else ops._dev(t, t.dtype)
+        W = 1
+        root = torch.arange(N, device=dev, dtype=torch.int32)
+        node = torch.from_numpy(np.ascontiguousarray(np.asarray(inputs[1]).reshape(-1), np.int32)).to(dev)
+        score = torch.zeros((N,), device=dev, dtype=torch.float32)
+        path_row, path_sign = i32(N, 0), f32(N, 0)
+        err = torch.full((hops,), ops.INT32_MAX, device=dev, dtype=torch.int32)
+        levels = []                                                          # per level: (entry nodes, children's parents, nodes)
+        for h in range(hops):
+            # dead entries (node -1: zero flow column) ride along with last node 0; their output is never read
+            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node.clamp(min=0), path_row, path_sign,
+                                       self._mb(plan, N * W))
+            W2 = min(beam, W * D)
+            final = h == hops - 1
+            c_root, c_node, c_score, c_parent, c_slot = i32(N * W2), i32(N * W2), f32(N * W2), i32(N * W2), i32(N * W2)
+            c_row, c_sign = (None, None) if final else (i32(N * W2, h + 1), f32(N * W2, h + 1))
+            _lib.check(lib.scn_beam_step(N, W, W2, h, D, p(node), p(score), p(path_row) if h else None, p(path_sign) if h else None,
+                                         p(logp), p(tab.deg), tab.n_nodes, p(tab.node), p(tab.edge), p(tab.sign), plan.n_edges,
+                                         p(c_root), p(c_node), p(c_score), p(c_parent), p(c_slot), p(c_row), p(c_sign), p(err[h:]),
+                                         ops._stream()), "scn_beam_step")
+            if trace is not None:
+                trace.append({"node": node.view(N, W).cpu().numpy(), "score": score.view(N, W).cpu().numpy(),
+                              "logp": logp.view(N, W, D).cpu().numpy(), "parent": c_parent.view(N, W2).cpu().numpy(),
+                              "slot": c_slot.view(N, W2).cpu().numpy()})
+            levels.append((node, c_parent.view(N, W2), c_node.view(N, W2)))
+            root, node, score, path_row, path_sign, W = c_root, c_node, c_score, c_row, c_sign, W2
+        errs = err.cpu().numpy()
+        for h in np.flatnonzero(errs != ops.INT32_MAX)[:1]:
+            t = int(errs[h])
+            v = int(levels[h][0][t // D].item())
+            raise KeyError((v, int(tab.h_node[v, t % D])))
+        # node paths from the per-level parents, on the device: walk every final entry back to its root
+        dead = (levels[-1][2] < 0)
+        k = torch.arange(W, device=dev).expand(N, W)
+        steps = []
+        for _, parent, nodes in reversed(levels):
+            steps.append(torch.gather(nodes, 1, k))
+            k = torch.gather(parent, 1, k).clamp(min=0).long()
+        paths = torch.stack(steps[::-1], dim=2).long().masked_fill(dead[:, :, None], -1)
+        out_paths = np.full((N, beam, hops), -1, np.int64)
+        out_logp = np.full((N, beam), -np.inf, np.float64)
+        out_paths[:, :W] = paths.cpu().numpy()
+        out_logp[:, :W] = score.view(N, W).cpu().numpy()
+        return out_paths, out_logp
+
+    def multi_hop_accuracy_topk(self, inputs, target_nodes, mask, hops, beam):
+        """Fraction of the trajectories of mask whose target_nodes[i] is the end node of one of their `beam` best paths of `hops`
+        steps (predict_paths_beam)."""
+        paths, _ = self.predict_paths_beam(inputs, hops, beam)
+        end = paths[:, :, -1]
+        hit = np.any((end >= 0) & (end == np.asarray(target_nodes).reshape(-1, 1)), axis=1)
+        return float(np.average(hit[np.asarray(mask) == 1]))
+
     def _edge_lookup(self, inputs):
         src = inputs[0] if self.model_type != 'bunch' else resolve_operands('bunch', self.shifts, inputs[0])[0][1]
         hit = getattr(self, "_lookup_cache", None)

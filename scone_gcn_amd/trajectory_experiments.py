@@ -31,7 +31,8 @@ def hyperparams(args=None):
           'load_model': 0, 'markov': 0, 'model_name': 'model', 'regional': 0, 'flip_edges': 0,
           'data_folder_suffix': 'working', 'multi_graph': '', 'holes': 1,
           'skip_mode': 'dense',          # not in the reference: dense | zeros | field (exact zero-skipping, Scone_GCN)
-          'multi_hop': 0}                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
+          'multi_hop': 0,                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
+          'beam': 0}                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
@@ -276,6 +277,10 @@ def train_model(hp=None):
         results["multi_hop"] = scone.multi_hop_accuracy_dist(shifts, inputs_1hop, target_nodes_all[1], [train_mask, test_mask],
                                                              nbrhoods, E_lookup, inputs_1hop[1], prefixes, 2)
         print('Multi hop accs:', results["multi_hop"])
+        if int(hp.get('beam', 0)) > 0:                                     # not in the reference: is the target among the beam's end nodes
+            results["multi_hop_topk"] = [scone.multi_hop_accuracy_topk(inputs_1hop, target_nodes_all[1], m, 2, int(hp['beam']))
+                                         for m in (train_mask, test_mask)]
+            print('Multi hop top-%d accs:' % int(hp['beam']), results["multi_hop_topk"])
     scone.experiment_results = results
     return scone, (train_loss, train_acc, test_loss, test_acc)
 

@@ -1,12 +1,17 @@
-"""Timing of the device multi-hop probability tree (Scone_GCN.multi_hop_accuracy_dist, STM:154-206).
+"""Timing of the device multi-hop probability tree (Scone_GCN.multi_hop_accuracy_dist, STM:154-206) and of the beam search
+(Scone_GCN.predict_paths_beam).
 
   (a) the 400-point generated data set, 1000 paths, dist with hops = 2: the device pipeline against a host loop that calls
       scone_func once per tree leaf (what the reference does with model_single);
-  (b) |E| ~ 1M, 4096 roots (8-step random walks), hops = 2: leaves per second.
+  (b) |E| ~ 1M, 4096 roots (8-step random walks), hops = 2: leaves per second;
+  (c) the complex and roots of (b), beam search with hops = 4 and beam = 8: leaves per second (every entry a level pushes through
+      the forward is a leaf), to be read against (b) of the same run.  The share of kernel time the forward kernels take comes from
+      a run of `--case c` alone under `rocprofv3 --kernel-trace --stats`, whose kernel table `--kernel-stats FILE` sums up.
 Device-synchronised wall time (torch.cuda.synchronize around the call), after warm-up calls.  Prints one JSON line per case and
 writes them all to --out.
 
-    python tools/multihop_time.py [--case a|b|ab] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
+    python tools/multihop_time.py [--case a|b|c|abc] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
+    python tools/multihop_time.py --kernel-stats profiles/multihop_c_kernel_stats.csv
 """
 import argparse
 import json
@@ -111,7 +116,17 @@ def _say(*a):
 T0 = time.perf_counter()
 
 
-def case_b(reps, roots=4096):
+_BIG = {}
+
+
+def _big(roots=4096):
+    """The |E| ~ 1M complex, its roots and the model of cases (b) and (c), built once per run."""
+    if roots not in _BIG:
+        _BIG[roots] = _build_big(roots)
+    return _BIG[roots]
+
+
+def _build_big(roots):
     _say("building the |E| ~ 1M complex")
     cx = g.random_SC_graph(g.calibrate_n_points(1_000_000))
     sc = SimplicialComplex(cx)
@@ -140,7 +155,11 @@ def case_b(reps, roots=4096):
     targets = np.array([rs.choice(nb[b][nb[b] >= 0]) for b in first])
     y = np.zeros((len(last), sc.max_degree, 1))
     inputs = [readout, last, flows]
-    net = _net(shifts, inputs, y)
+    return _net(shifts, inputs, y), inputs, targets, sc, E_lookup, last, nb, cx
+
+
+def case_b(reps, roots=4096):
+    net, inputs, targets, sc, E_lookup, last, nb, cx = _big(roots)
     t_tab = time.perf_counter()
     net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 1)        # builds and caches the step tables
     t_tab = time.perf_counter() - t_tab
@@ -151,13 +170,52 @@ def case_b(reps, roots=4096):
             "leaves_per_s": leaves / t, "first_call_hops1_incl_step_tables_s": t_tab}
 
 
+def case_c(reps, roots=4096, hops=4, beam=8):
+    net, inputs, targets, sc, E_lookup, last, nb, cx = _big(roots)
+    t_tab = time.perf_counter()
+    net.predict_paths_beam(inputs, 1, 1, sc.nbrhoods, E_lookup)                        # builds and caches the step tables
+    t_tab = time.perf_counter() - t_tab
+    _say("step tables %.1f s; timing the beam" % t_tab)
+    out = []
+    t = _timed(lambda: out.append(net.predict_paths_beam(inputs, hops, beam, sc.nbrhoods, E_lookup)), reps)
+    paths, logp = out[-1]
+    widths = [1]
+    for _ in range(hops - 1):
+        widths.append(min(beam, widths[-1] * sc.max_degree))
+    leaves = len(last) * int(sum(widths))
+    return {"case": "c", "n_edges": int(cx.n_edges), "roots": len(last), "hops": hops, "beam": beam, "level_widths": widths,
+            "leaves_evaluated": leaves, "device_s": t, "leaves_per_s": leaves / t, "live_paths": int((paths[:, :, -1] >= 0).sum()),
+            "mean_best_logp": float(logp[:, 0].mean()), "first_call_hops1_incl_step_tables_s": t_tab}
+
+
+def kernel_shares(path):
+    """Shares of kernel time from a `rocprofv3 --kernel-trace --stats` kernel table (Name, Calls, TotalDurationNs, ...): the forward
+    kernels (the fused layer kernels `scn::fwd_*` and the readout) and every multi-hop kernel of csrc/scn_hops.hip by name."""
+    import csv
+    with open(path, newline="") as f:
+        rows = [(r["Name"], int(r["Calls"]), int(r["TotalDurationNs"])) for r in csv.DictReader(f)]
+    total = sum(t for _, _, t in rows)
+    fwd = sum(t for n, _, t in rows if "scn::fwd_" in n or "scn::readout_fwd" in n)
+    hops = {}
+    for n, c, t in rows:
+        for k in ("beam_step", "hop_select", "tree_expand", "tree_copy", "tree_patch", "tree_target"):
+            if k + "_kernel" in n:
+                hops[k] = {"calls": c, "total_ns": t, "share": t / total}
+    return {"kernel_time_s": total / 1e9, "forward_share": fwd / total, "multihop_kernels": hops,
+            "other_share": 1.0 - (fwd + sum(v["total_ns"] for v in hops.values())) / total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="ab")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-roots", type=int, default=40)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-stats", default=None, help="a rocprofv3 kernel_stats.csv: print the shares of kernel time and exit")
     a = ap.parse_args()
+    if a.kernel_stats:
+        print(json.dumps(kernel_shares(a.kernel_stats)))
+        return
     torch.cuda.set_device(0)
     res = []
     if "a" in a.case:
@@ -165,6 +223,9 @@ def main():
         print(json.dumps(res[-1]), flush=True)
     if "b" in a.case:
         res.append(case_b(a.reps))
+        print(json.dumps(res[-1]), flush=True)
+    if "c" in a.case:
+        res.append(case_c(a.reps))
         print(json.dumps(res[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
