@@ -541,3 +541,15 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         }
     }
 }
+
+// The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so the trailing partial_first and fw are always passed; the
+// dispatch never spells the boolean pack).  The static_asserts inside the kernel say which combinations exist; what DZ, DZ0, aux and
+// fw carry in each:
+template <int ACT> constexpr auto bwd_c32_plain = bwd_c32_bf16_kernel<ACT>;                                  // DZ = dz, DZ0 null
+template <int ACT> constexpr auto bwd_c32_pair = bwd_c32_bf16_kernel<ACT, false, true>;                      // the same at C = 16, on slab pairs
+template <int ACT> constexpr auto bwd_c32_power = bwd_c32_bf16_kernel<ACT, true>;                            // DZ = g1 = S^T dz, DZ0 = dz
+template <int ACT> constexpr auto bwd_c32_power_pair = bwd_c32_bf16_kernel<ACT, true, true>;                 // the same at C = 16
+template <int ACT> constexpr auto bwd_c32_accum = bwd_c32_bf16_kernel<ACT, false, false, false, true>;       // DZ0 = dx_partial, added to dx
+template <int ACT> constexpr auto bwd_c32_first = bwd_c32_bf16_kernel<ACT, false, false, true>;              // DZ0 = y, dx null: -> partial_first
+template <int ACT> constexpr auto bwd_c32_first_pair = bwd_c32_bf16_kernel<ACT, false, true, true>;          // the same at C = 16
+template <int ACT> constexpr auto bwd_c32_first_from_y = bwd_c32_bf16_kernel<ACT, false, false, true, false, true>;   // and aux null: rebuilt from y and fw

@@ -2,15 +2,6 @@
 // ------------------------------------------------------------------------------------------------
 // host dispatch
 // ------------------------------------------------------------------------------------------------
-// dynamic LDS above 64 KB has to be opted into per kernel
-#define SCN_ENSURE_LDS(kernel, bytes)                                                                          \
-    do {                                                                                                       \
-        if ((bytes) > 160 * 1024) return SCN_ERR_UNSUPPORTED;                                                  \
-        if ((bytes) > 64 * 1024)                                                                               \
-            SCN_HIP_TRY(hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                            (int)(bytes)));                                                    \
-    } while (0)
-
 static bool scone_shape(const scn_conv_s* c) {
     return c->plan.built && c->n_groups == 1 && c->g[0].identity == 1 && c->g[0].n_vals == 2;
 }
@@ -67,7 +58,7 @@ int build_assignments(scn_conv_s* c) {                      // every grid.x laun
     return SCN_OK;
 }
 
-static void launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, dim3& grid, int max_per_cu = 2) {
+static dim3 launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, int max_per_cu = 2) {
     const int nb = c->plan.dev.n_blocks;
     const int per_cu = (max_per_cu >= 3 && lds <= 160 * 1024 / max_per_cu) ? max_per_cu : (lds <= 80 * 1024 ? 2 : 1);
     const int cap = 256 * per_cu;
@@ -84,7 +75,31 @@ static void launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, dim3& grid
         const long cost = work * 64 + gy;                                                    // ties: fewer slab splits
         if (best < 0 || cost < best) { best = cost; bx = gx; by = gy; }
     }
-    grid = dim3(bx, by);
+    return dim3(bx, by);
+}
+
+constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
+constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
+
+// What a launch of a blocked kernel starts from: the plan's device view with the block assignment of the chosen grid, the grid
+// (a work list carries its own slab lists: no slab split then), the operator's shape.
+struct BlockedLaunch {
+    PlanDev P;
+    dim3 grid;
+    int nr, nc;
+    int n_wg() const { return (int)(grid.x * grid.y); }
+};
+static BlockedLaunch blocked_launch(const scn_conv_s* c, int n_slabs, size_t lds, const WorkList& wl = NO_LIST, int max_per_cu = 2) {
+    BlockedLaunch L{c->plan.dev, launch_grid(c, n_slabs, lds, max_per_cu), c->n_rows, c->g[0].n_cols};
+    L.P.assign = balanced_assignment(c, L.grid.x);
+    if (wl.block) L.grid.y = 1;
+    return L;
+}
+
+// dW[k][ca][c] += the workgroups' partial sums [n_wg][c_aux][3 * cd] of a backward launch (fixed order)
+static int reduce_dw(const float* partial, int n_wg, int c_aux, int cd, float* const* dW, hipStream_t st) {
+    return launch_checked(blocked_dw_reduce, dim3((c_aux * 3 * cd + 63) / 64), dim3(1024), 0, st, partial, n_wg, c_aux, cd, dW[0], dW[1],
+                          dW[2]);
 }
 
 bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in, int c_out) {
@@ -96,187 +111,99 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wlp,
                     hipStream_t st, const float* partial) {            // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
-    PlanDev P = c->plan.dev;
-    const WorkList wl = wlp ? *wlp : WorkList{0, nullptr, nullptr, nullptr};
-    dim3 grid;
+    const WorkList wl = wlp ? *wlp : NO_LIST;
     const int ci = c_in[0];
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
-    const FirstW no_fw{{nullptr, nullptr, nullptr}};
     if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
     if (!out) {                                                           // first layer, shifted input only (scn_conv_forward_first with out = NULL)
         if (ci != 1 || !y_out || wl.block) return SCN_ERR_UNSUPPORTED;
         const size_t lds = smem_bytes(16);
-        launch_grid(c, n_slabs, lds, grid);
-        hipLaunchKernelGGL(gather3_c1_kernel, grid, dim3(BK_THREADS), lds, st, P, src[0], y_out, nr, nc, n_slabs);
-        SCN_LAUNCH_CHECK();
-        return SCN_OK;
+        return launch_checked(gather3_c1_kernel, launch_grid(c, n_slabs, lds), dim3(BK_THREADS), lds, st, c->plan.dev, src[0], y_out,
+                              c->n_rows, c->g[0].n_cols, n_slabs);
     }
     if (ci == 32) {                                                       // 16 waves, f16 hi + lo split
-        const size_t lds16 = smem_bytes_c32(W16_EXTRA_BYTES);
-        launch_grid(c, n_slabs, lds16, grid);
-        P.assign = balanced_assignment(c, grid.x);
-        if (wl.block) grid.y = 1;                                          // a work list carries its own slab lists
-#define SCN_LAUNCH_FWD32W(A)                                                                                      \
-    do {                                                                                                          \
-        if (partial) {                                                                                            \
-            SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, false, true>), lds16);                                          \
-            hipLaunchKernelGGL((fwd_c32_w16_kernel<A, false, true>), grid, dim3(W16_THREADS), lds16, st, P, src[0], partial, \
-                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl, no_fw);                                \
-        } else {                                                                                                  \
-            SCN_ENSURE_LDS(fwd_c32_w16_kernel<A>, lds16);                                                         \
-            hipLaunchKernelGGL(fwd_c32_w16_kernel<A>, grid, dim3(W16_THREADS), lds16, st, P, src[0], (const float*)nullptr, \
-                               W[0], W[1], W[2], out, nr, nc, n_slabs, wl, no_fw);                                \
-        }                                                                                                         \
-    } while (0)
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_FWD32W(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_FWD32W(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWD32W(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_FWD32W(SCN_ACT_NONE); break;
-        }
-    } else if (ci == 16) {                                                // 16 waves, f16 hi + lo split, two slabs per visit
-        const size_t lds16 = smem_bytes_c32(16 + 64);
-        launch_grid(c, n_slabs, lds16, grid);
-        P.assign = balanced_assignment(c, grid.x);
-        if (wl.block) grid.y = 1;
-#define SCN_LAUNCH_FWD16W(A)                                                                                      \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS(fwd_c16_w16_kernel<A>, lds16);                                                             \
-        hipLaunchKernelGGL(fwd_c16_w16_kernel<A>, grid, dim3(W16_THREADS), lds16, st, P, src[0], (const float*)nullptr,      \
-                           W[0], W[1], W[2], out, nr, nc, n_slabs, wl);                                           \
-    } while (0)
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_FWD16W(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_FWD16W(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWD16W(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_FWD16W(SCN_ACT_NONE); break;
-        }
-    } else {
-        const size_t lds = smem_bytes(16, 2 * BK_R * BK_NS * 12);
-        launch_grid(c, n_slabs, lds, grid, 3);      // 8-wave workgroups at 64 VGPRs and 23 KB of LDS: three per CU (4.45 -> 3.9 ms; four: 4.8)
-        P.assign = balanced_assignment(c, grid.x);
-        if (wl.block) grid.y = 1;
-        if (c_out == 32)
-            hipLaunchKernelGGL(fwd_c1_kernel<32>, grid, dim3(BK_THREADS), lds, st, P, src[0], W[0], W[1], W[2], out, y_out, nr,
-                               nc, n_slabs, act, wl);
-        else
-            hipLaunchKernelGGL(fwd_c1_kernel<16>, grid, dim3(BK_THREADS), lds, st, P, src[0], W[0], W[1], W[2], out, y_out, nr,
-                               nc, n_slabs, act, wl);
+        const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES);
+        const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
+        return with_act(act, [&](auto A) -> int {
+            constexpr int ACT = decltype(A)::value;
+            return launch_checked(partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0],
+                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW);
+        });
     }
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    if (ci == 16) {                                                       // 16 waves, f16 hi + lo split, two slabs per visit
+        const size_t lds = smem_bytes_c32(16 + 64);
+        const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
+        return with_act(act, [&](auto A) -> int {
+            return launch_checked(fwd_c16_plain<decltype(A)::value>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1],
+                                  W[2], out, L.nr, L.nc, n_slabs, wl);
+        });
+    }
+    const size_t lds = smem_bytes(16, 2 * BK_R * BK_NS * 12);
+    // 8-wave workgroups at 64 VGPRs and 23 KB of LDS: three per CU (4.45 -> 3.9 ms; four: 4.8)
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl, 3);
+    return launch_checked(c_out == 32 ? fwd_c1_kernel<32> : fwd_c1_kernel<16>, L.grid, dim3(BK_THREADS), lds, st, L.P, src[0], W[0], W[1],
+                          W[2], out, y_out, L.nr, L.nc, n_slabs, act, wl);
 }
 
 // Layer 2 of a stack whose first layer has one input channel, straight from the first layer's shifted-input records
-// (fwd_c32_w16_kernel<.., FROMY>): H1 is rebuilt in LDS, never stored.  Dense launches, 32 channels.
+// (fwd_c32_from_y): H1 is rebuilt in LDS, never stored.  Dense launches, 32 channels.
 bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
     return scone_shape(c) && ns == BK_NS && ch == 32 && c->n_rows == c->g[0].n_cols;
 }
 
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
                            float* out, hipStream_t st) {
-    PlanDev P = c->plan.dev;
-    const WorkList wl{0, nullptr, nullptr, nullptr};
     const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
-    dim3 grid;
-    const size_t lds16 = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
-    launch_grid(c, n_slabs, lds16, grid);
-    P.assign = balanced_assignment(c, grid.x);
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
-#define SCN_LAUNCH_FWDY(A)                                                                                        \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, false, false, true>), lds16);                                       \
-        hipLaunchKernelGGL((fwd_c32_w16_kernel<A, false, false, true>), grid, dim3(W16_THREADS), lds16, st, P, y, \
-                           (const float*)nullptr, W[0], W[1], W[2], out, nr, nc, n_slabs, wl, fw);                \
-    } while (0)
-    switch (act) {
-        case SCN_ACT_TANH: SCN_LAUNCH_FWDY(SCN_ACT_TANH); break;
-        case SCN_ACT_RELU: SCN_LAUNCH_FWDY(SCN_ACT_RELU); break;
-        case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWDY(SCN_ACT_LEAKY_RELU); break;
-        default: SCN_LAUNCH_FWDY(SCN_ACT_NONE); break;
-    }
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
+    return with_act(act, [&](auto A) -> int {
+        return launch_checked(fwd_c32_from_y<decltype(A)::value>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
+                              out, L.nr, L.nc, n_slabs, NO_LIST, fw);
+    });
 }
 
-bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux, bool has_dx) {
+bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux) {
     if (!scone_shape(c) || ns != BK_NS) return false;
     const int cd = c_dz[0];
-    (void)has_dx;
     return (cd == 32 && c_aux == 32) || (cd == 16 && c_aux == 16);      // (one input channel: scn_conv_dw_first)
 }
 
 // C = 16 runs the C = 32 kernel on slab pairs (a dedicated 16 x 16-tile kernel was built in round 4 and lost: profiles/r04_bwd16_ab.txt,
-// profiles/r04_bwd16_and_elastic_experiments.patch).
-static size_t bwd_lds(int cd, int) {
+// profiles/r04_bwd16_and_elastic_experiments.patch), so every form of the backward has one LDS footprint.
+static size_t bwd_lds() {
     return smem_bytes_c32(B32_EXTRA_BYTES);                      // staging buffers + ELL + weight and selection fragments
 }
 
+// workgroups of a backward launch without a work list: each owns one set of weight-gradient partials in the workspace
+static size_t bwd_workgroups(const scn_conv_s* c, int n_slabs) {
+    const dim3 grid = launch_grid(c, n_slabs, bwd_lds());
+    return (size_t)grid.x * grid.y;
+}
+
 size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux) {
-    if (!blocked_backward_supported(c, ns, c_dz, c_aux, false) && !blocked_backward_supported(c, ns, c_dz, c_aux, true))
-        return 0;
-    dim3 grid;
-    launch_grid(c, n_slabs, bwd_lds(c_dz[0], c_aux), grid);
-    return (size_t)grid.x * grid.y * c_aux * 3 * c_dz[0] * sizeof(float);
+    if (!blocked_backward_supported(c, ns, c_dz, c_aux)) return 0;
+    return bwd_workgroups(c, n_slabs) * c_aux * 3 * c_dz[0] * sizeof(float);
 }
 
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
                      float* const* dW, void* ws, size_t ws_bytes, const WorkList* wlp, hipStream_t st,
                      const float* dx_partial) {           // dx_partial (32 -> 32 only): dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
-    PlanDev P = c->plan.dev;
-    const WorkList wl = wlp ? *wlp : WorkList{0, nullptr, nullptr, nullptr};
-    dim3 grid;
+    const WorkList wl = wlp ? *wlp : NO_LIST;
     const int cd = c_dz[0];
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
     float* partial = (float*)ws;
-    const size_t lds = bwd_lds(cd, c_aux);
-    launch_grid(c, n_slabs, lds, grid);
-    P.assign = balanced_assignment(c, grid.x);
-    if (wl.block) grid.y = 1;
+    const size_t lds = bwd_lds();
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
     if (dx_partial && (c_aux != 32 || !dx)) return SCN_ERR_UNSUPPORTED;
-    if (c_aux == 32) {
-#define SCN_LAUNCH_BWD32(A)                                                                                       \
-    do {                                                                                                          \
-        if (dx_partial) {                                                                                         \
-            SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, false, false, true>), lds);                             \
-            hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, false, false, true>), grid, dim3(BK_THREADS), lds, st, P, dz[0], \
-                               dx_partial, W[0], W[1], W[2], aux, dx, partial, nr, nc, n_slabs, wl);              \
-        } else {                                                                                                  \
-            SCN_ENSURE_LDS(bwd_c32_bf16_kernel<A>, lds);                                                          \
-            hipLaunchKernelGGL(bwd_c32_bf16_kernel<A>, grid, dim3(BK_THREADS), lds, st, P, dz[0], (const float*)nullptr,     \
-                               W[0], W[1], W[2], aux, dx, partial, nr, nc, n_slabs, wl);                          \
-        }                                                                                                         \
-    } while (0)
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWD32(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWD32(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWD32(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_BWD32(SCN_ACT_NONE); break;
-        }
-    } else {                                                              // C = 16: the C = 32 kernel on slab pairs
-#define SCN_LAUNCH_BWD16P(A)                                                                                      \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, true>), lds);                                               \
-        hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, true>), grid, dim3(BK_THREADS), lds, st, P, dz[0],      \
-                           (const float*)nullptr, W[0], W[1], W[2], aux, dx, partial, nr, nc, n_slabs, wl);       \
-    } while (0)
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWD16P(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWD16P(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWD16P(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_BWD16P(SCN_ACT_NONE); break;
-        }
-    }
-    SCN_LAUNCH_CHECK();
-    const int per = c_aux * 3 * cd;
-    hipLaunchKernelGGL(blocked_dw_reduce, dim3((per + 63) / 64), dim3(1024), 0, st, partial, (int)(grid.x * grid.y), c_aux,
-                       cd, dW[0], dW[1], dW[2]);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    const int st_k = with_act(act, [&](auto A) -> int {
+        constexpr int ACT = decltype(A)::value;
+        const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
+        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
+                              n_slabs, wl, nullptr, NO_FIRSTW);
+    });
+    return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), c_aux, cd, dW, st);
 }
 
-// Backward of the layer that follows the first one, fused with the first layer's weight gradient (bwd_c32_bf16_kernel<.., FIRST>).
+// Backward of the layer that follows the first one, fused with the first layer's weight gradient (bwd_c32_first and its kin).
 // Workspace: [this layer's dW partials][dW_first partials: 96 floats per workgroup].
 bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch) {
     return scone_shape(c) && ns == BK_NS && (ch == 32 || ch == 16);          // 16: the slab-pair form
@@ -284,9 +211,7 @@ bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch) {
 
 size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch) {
     if (!blocked_backward_first_supported(c, ns, ch)) return 0;
-    dim3 grid;
-    launch_grid(c, n_slabs, bwd_lds(ch, ch), grid);
-    return (size_t)grid.x * grid.y * (3 * ch * ch + 96) * sizeof(float);
+    return bwd_workgroups(c, n_slabs) * (3 * ch * ch + 96) * sizeof(float);
 }
 
 // dW_first[slot][cc] of the slab-pair form: partial [b][slot * 32 + 16 s + cc], the two slabs s folded here (fixed order)
@@ -308,66 +233,27 @@ __global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* _
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
                            hipStream_t st, const float* const* W_first) {   // W_first (32 channels): aux is rebuilt from y, not read
-    PlanDev P = c->plan.dev;
-    const WorkList wl = wlp ? *wlp : WorkList{0, nullptr, nullptr, nullptr};
-    dim3 grid;
-    const size_t lds = bwd_lds(ch, ch);
-    launch_grid(c, n_slabs, lds, grid);
-    P.assign = balanced_assignment(c, grid.x);
-    if (wl.block) grid.y = 1;
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
-    const int n_wg = (int)(grid.x * grid.y);
+    const WorkList wl = wlp ? *wlp : NO_LIST;
+    const size_t lds = bwd_lds();
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
+    const int n_wg = L.n_wg();
     float* partial = (float*)ws;
     float* partial_first = partial + (size_t)n_wg * 3 * ch * ch;
-#define SCN_LAUNCH_BWDF(A, PAIRV)                                                                                 \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, PAIRV, true>), lds);                                        \
-        hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, PAIRV, true>), grid, dim3(BK_THREADS), lds, st, P, dz, y, W[0], \
-                           W[1], W[2], aux, (float*)nullptr, partial, nr, nc, n_slabs, wl, partial_first,         \
-                           FirstW{{nullptr, nullptr, nullptr}});                                                  \
-    } while (0)
-#define SCN_LAUNCH_BWDFY(A)                                                                                       \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, false, false, true, false, true>), lds);                           \
-        hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, false, false, true, false, true>), grid, dim3(BK_THREADS), lds, st, P, dz, y, \
-                           W[0], W[1], W[2], (const float*)nullptr, (float*)nullptr, partial, nr, nc, n_slabs, wl, partial_first, \
-                           FirstW{{W_first[0], W_first[1], W_first[2]}});                                          \
-    } while (0)
-    if (W_first) {
-        if (ch != 32) return SCN_ERR_UNSUPPORTED;
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWDFY(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWDFY(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDFY(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_BWDFY(SCN_ACT_NONE); break;
-        }
-    } else if (ch == 32) {
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWDF(SCN_ACT_TANH, false); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWDF(SCN_ACT_RELU, false); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDF(SCN_ACT_LEAKY_RELU, false); break;
-            default: SCN_LAUNCH_BWDF(SCN_ACT_NONE, false); break;
-        }
-    } else {
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWDF(SCN_ACT_TANH, true); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWDF(SCN_ACT_RELU, true); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDF(SCN_ACT_LEAKY_RELU, true); break;
-            default: SCN_LAUNCH_BWDF(SCN_ACT_NONE, true); break;
-        }
-    }
-    SCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(blocked_dw_reduce, dim3((ch * 3 * ch + 63) / 64), dim3(1024), 0, st, partial, n_wg, ch, ch, dW[0], dW[1],
-                       dW[2]);
-    SCN_LAUNCH_CHECK();
+    if (W_first && ch != 32) return SCN_ERR_UNSUPPORTED;
+    const FirstW fw = W_first ? FirstW{{W_first[0], W_first[1], W_first[2]}} : NO_FIRSTW;
+    int st_k = with_act(act, [&](auto A) -> int {
+        constexpr int ACT = decltype(A)::value;
+        const auto k = W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
+        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2], W_first ? nullptr : aux, nullptr, partial,
+                              L.nr, L.nc, n_slabs, wl, partial_first, fw);
+    });
+    if (st_k == SCN_OK) st_k = reduce_dw(partial, n_wg, ch, ch, dW, st);
+    if (st_k != SCN_OK) return st_k;
     if (ch == 32)
-        hipLaunchKernelGGL(dw_first_reduce_kernel, dim3(96), dim3(64), 0, st, partial_first, n_wg, 32, dW_first[0], dW_first[1],
-                           dW_first[2]);
-    else
-        hipLaunchKernelGGL(dw_first_reduce_pair_kernel, dim3(48), dim3(64), 0, st, partial_first, n_wg, dW_first[0], dW_first[1],
-                           dW_first[2]);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+        return launch_checked(dw_first_reduce_kernel, dim3(96), dim3(64), 0, st, partial_first, n_wg, 32, dW_first[0], dW_first[1],
+                              dW_first[2]);
+    return launch_checked(dw_first_reduce_pair_kernel, dim3(48), dim3(64), 0, st, partial_first, n_wg, dW_first[0], dW_first[1],
+                          dW_first[2]);
 }
 
 // (with a y handed in the operator only supplies the row count and, for work lists, the block table)
@@ -407,10 +293,9 @@ int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y,
     if (!y) {
         if (!scone_shape(c)) return SCN_ERR_UNSUPPORTED;          // recomputing y needs identity + two value arrays
         float* Y = (float*)ws;
-        dim3 grid;
         const size_t lds = smem_bytes(16);
-        launch_grid(c, n_slabs, lds, grid);
-        hipLaunchKernelGGL(gather3_c1_kernel, grid, dim3(BK_THREADS), lds, st, P, x, Y, c->n_rows, c->g[0].n_cols, n_slabs);
+        hipLaunchKernelGGL(gather3_c1_kernel, launch_grid(c, n_slabs, lds), dim3(BK_THREADS), lds, st, P, x, Y, c->n_rows, c->g[0].n_cols,
+                           n_slabs);
         SCN_LAUNCH_CHECK();
         y = Y;
     }
@@ -444,88 +329,34 @@ bool blocked_power_supported(const scn_conv_s* c, int ns, int ch) {
 
 size_t blocked_power_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch) {
     if (!blocked_power_supported(c, ns, ch)) return 0;
-    dim3 grid;
-    launch_grid(c, n_slabs, smem_bytes_c32(B32_EXTRA_BYTES), grid);
-    return (size_t)grid.x * grid.y * ch * 3 * ch * sizeof(float);
+    return bwd_workgroups(c, n_slabs) * ch * 3 * ch * sizeof(float);
 }
 
 int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const float* x, const float* const* W, int ch, int act,
                           float* out, hipStream_t st) {
-    PlanDev P = c->plan.dev;
-    const WorkList wl{0, nullptr, nullptr, nullptr};
-    dim3 grid;
-    const size_t lds16 = ch == 32 ? smem_bytes_c32(W16_EXTRA_BYTES) : smem_bytes_c32(16 + 64);
-    launch_grid(c, n_slabs, lds16, grid);
-    P.assign = balanced_assignment(c, grid.x);
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
-    if (ch == 16) {
-#define SCN_LAUNCH_FWDP16(A)                                                                                      \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((fwd_c16_w16_kernel<A, true>), lds16);                                                     \
-        hipLaunchKernelGGL((fwd_c16_w16_kernel<A, true>), grid, dim3(W16_THREADS), lds16, st, P, x, x0, W[0], W[1], W[2], \
-                           out, nr, nc, n_slabs, wl);                                                             \
-    } while (0)
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_FWDP16(SCN_ACT_TANH); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_FWDP16(SCN_ACT_RELU); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWDP16(SCN_ACT_LEAKY_RELU); break;
-            default: SCN_LAUNCH_FWDP16(SCN_ACT_NONE); break;
-        }
-        SCN_LAUNCH_CHECK();
-        return SCN_OK;
-    }
-#define SCN_LAUNCH_FWDP(A)                                                                                        \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((fwd_c32_w16_kernel<A, true>), lds16);                                                     \
-        hipLaunchKernelGGL((fwd_c32_w16_kernel<A, true>), grid, dim3(W16_THREADS), lds16, st, P, x, x0, W[0], W[1], W[2], \
-                           out, nr, nc, n_slabs, wl, FirstW{{nullptr, nullptr, nullptr}});                        \
-    } while (0)
-    switch (act) {
-        case SCN_ACT_TANH: SCN_LAUNCH_FWDP(SCN_ACT_TANH); break;
-        case SCN_ACT_RELU: SCN_LAUNCH_FWDP(SCN_ACT_RELU); break;
-        case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_FWDP(SCN_ACT_LEAKY_RELU); break;
-        default: SCN_LAUNCH_FWDP(SCN_ACT_NONE); break;
-    }
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    const size_t lds = ch == 32 ? smem_bytes_c32(W16_EXTRA_BYTES) : smem_bytes_c32(16 + 64);
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
+    return with_act(act, [&](auto A) -> int {
+        constexpr int ACT = decltype(A)::value;
+        if (ch == 16)
+            return launch_checked(fwd_c16_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc,
+                                  n_slabs, NO_LIST);
+        return launch_checked(fwd_c32_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs,
+                              NO_LIST, NO_FIRSTW);
+    });
 }
 
 int blocked_power_backward(scn_conv_s* c, int n_slabs, const float* dz, const float* g1, const float* const* W,
                            const float* aux, int ch, int act, float* dx, float* const* dW, void* ws, hipStream_t st) {
-    PlanDev P = c->plan.dev;
-    const WorkList wl{0, nullptr, nullptr, nullptr};
-    dim3 grid;
-    const size_t lds = smem_bytes_c32(B32_EXTRA_BYTES);
-    launch_grid(c, n_slabs, lds, grid);
-    P.assign = balanced_assignment(c, grid.x);
-    const int nr = c->n_rows, nc = c->g[0].n_cols;
+    const size_t lds = bwd_lds();
+    const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
     float* partial = (float*)ws;
-#define SCN_LAUNCH_BWDP(A, PAIRV)                                                                                 \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((bwd_c32_bf16_kernel<A, true, PAIRV>), lds);                                               \
-        hipLaunchKernelGGL((bwd_c32_bf16_kernel<A, true, PAIRV>), grid, dim3(BK_THREADS), lds, st, P, g1, dz, W[0], W[1], \
-                           W[2], aux, dx, partial, nr, nc, n_slabs, wl);                                          \
-    } while (0)
-    if (ch == 32) {
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWDP(SCN_ACT_TANH, false); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWDP(SCN_ACT_RELU, false); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDP(SCN_ACT_LEAKY_RELU, false); break;
-            default: SCN_LAUNCH_BWDP(SCN_ACT_NONE, false); break;
-        }
-    } else {                                                              // C = 16: the same kernel on slab pairs
-        switch (act) {
-            case SCN_ACT_TANH: SCN_LAUNCH_BWDP(SCN_ACT_TANH, true); break;
-            case SCN_ACT_RELU: SCN_LAUNCH_BWDP(SCN_ACT_RELU, true); break;
-            case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_BWDP(SCN_ACT_LEAKY_RELU, true); break;
-            default: SCN_LAUNCH_BWDP(SCN_ACT_NONE, true); break;
-        }
-    }
-    SCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(blocked_dw_reduce, dim3((ch * 3 * ch + 63) / 64), dim3(1024), 0, st, partial, (int)(grid.x * grid.y), ch, ch,
-                       dW[0], dW[1], dW[2]);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    const int st_k = with_act(act, [&](auto A) -> int {
+        constexpr int ACT = decltype(A)::value;
+        return launch_checked(ch == 32 ? bwd_c32_power<ACT> : bwd_c32_power_pair<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, g1, dz, W[0],
+                              W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, NO_LIST, nullptr, NO_FIRSTW);
+    });
+    return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), ch, ch, dW, st);
 }
 
 bool blocked_spmm_supported(const scn_conv_s* c, int k) {
@@ -533,27 +364,16 @@ bool blocked_spmm_supported(const scn_conv_s* c, int k) {
 }
 
 int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st) {
-    PlanDev P = c->plan.dev;
-    dim3 grid;
-    const size_t lds = smem_bytes(k * 4, 16);
-    launch_grid(c, n_slabs, lds, grid);
-    P.assign = balanced_assignment(c, grid.x);
 #ifdef SCN_AB_SPMM_TWO_BUFFERS                                                  // diagnostic builds: the two-buffer kernel for every K
     const bool ring = false;
 #else
     const bool ring = k == 128 || k == 64;
 #endif
     if (ring) {
-#define SCN_LAUNCH_RING(D, NI)                                                                                    \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS((spmm_ring_kernel<D, NI>), lds);                                                           \
-        hipLaunchKernelGGL((spmm_ring_kernel<D, NI>), grid, dim3(SP_THREADS), lds, st, P, x, ya, yb, c->n_rows,   \
-                           c->g[0].n_cols, n_slabs);                                                              \
-    } while (0)
-        if (yb) { if (k == 128) SCN_LAUNCH_RING(true, 2); else SCN_LAUNCH_RING(true, 1); }
-        else    { if (k == 128) SCN_LAUNCH_RING(false, 2); else SCN_LAUNCH_RING(false, 1); }
-        SCN_LAUNCH_CHECK();
-        return SCN_OK;
+        const size_t lds = smem_bytes(k * 4, 16);
+        const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
+        const auto kern = k == 128 ? (yb ? spmm_ring_dual<2> : spmm_ring_single<2>) : (yb ? spmm_ring_dual<1> : spmm_ring_single<1>);
+        return launch_checked(kern, L.grid, dim3(SP_THREADS), lds, st, L.P, x, ya, yb, L.nr, L.nc, n_slabs);
     }
     // narrow operands: fold consecutive slabs into one staged piece (see dma_stage_sp) until it is 128 floats wide
 #ifdef SCN_AB_SPMM_NO_BATCH                                                     // diagnostic builds: one slab per staged piece
@@ -561,19 +381,8 @@ int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, f
 #else
     const int batch = k > 32 ? 1 : std::max(1, std::min(n_slabs, 128 / k));
 #endif
-    const size_t ldsb = smem_bytes(k * 4 * batch, 16);
-    if (batch > 1) {
-        launch_grid(c, (n_slabs + batch - 1) / batch, ldsb, grid);
-        P.assign = balanced_assignment(c, grid.x);
-    }
-    SCN_ENSURE_LDS(spmm_blocked_kernel<true>, ldsb);
-    SCN_ENSURE_LDS(spmm_blocked_kernel<false>, ldsb);
-    if (yb)
-        hipLaunchKernelGGL(spmm_blocked_kernel<true>, grid, dim3(SP_THREADS), ldsb, st, P, x, ya, yb, c->n_rows, c->g[0].n_cols,
-                           n_slabs, k, batch);
-    else
-        hipLaunchKernelGGL(spmm_blocked_kernel<false>, grid, dim3(SP_THREADS), ldsb, st, P, x, ya, yb, c->n_rows,
-                           c->g[0].n_cols, n_slabs, k, batch);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    const size_t lds = smem_bytes(k * 4 * batch, 16);
+    const BlockedLaunch L = blocked_launch(c, (n_slabs + batch - 1) / batch, lds);      // the grid splits staged pieces, not slabs
+    return launch_checked(yb ? spmm_blocked_dual : spmm_blocked_single, L.grid, dim3(SP_THREADS), lds, st, L.P, x, ya, yb, L.nr, L.nc,
+                          n_slabs, k, batch);
 }

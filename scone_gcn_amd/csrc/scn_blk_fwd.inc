@@ -546,6 +546,13 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     }
 }
 
+// The forms of fwd_c32_w16_kernel by name (one function-pointer type; the dispatch never spells the boolean pack).  The
+// static_asserts inside the kernel say which combinations exist; here is what X, X0 and fw carry in each:
+template <int ACT> constexpr auto fwd_c32_plain = fwd_c32_w16_kernel<ACT>;                        // X = the layer's input; X0 null, fw null
+template <int ACT> constexpr auto fwd_c32_power = fwd_c32_w16_kernel<ACT, true>;                  // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
+template <int ACT> constexpr auto fwd_c32_accum = fwd_c32_w16_kernel<ACT, false, true>;           // X0 = partial pre-activation, added before act
+template <int ACT> constexpr auto fwd_c32_from_y = fwd_c32_w16_kernel<ACT, false, false, true>;   // X = the first layer's records y, fw = its weight rows
+
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = C_out = 16, sixteen waves, f16 hi + lo split -- the C=32 machinery on TWO slabs at a time:
 // a staged 512-byte piece is [slab A: 4 trajectories x 16 channels | slab B: the same], so the plan, the LDS image, the
@@ -754,6 +761,10 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
     for (int q = 0; q < 2; ++q)
         if (pend_ptr[q]) *(f32x4*)(pend_ptr[q]) = pend[q];
 }
+
+// The forms of fwd_c16_w16_kernel by name (one function-pointer type; the dispatch never spells the boolean pack):
+template <int ACT> constexpr auto fwd_c16_plain = fwd_c16_w16_kernel<ACT>;            // X = the layer's input, X0 unused (null)
+template <int ACT> constexpr auto fwd_c16_power = fwd_c16_w16_kernel<ACT, true>;      // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = 1 -> C_out = C (first layer, TE:143-147 with flow (E,1)): three gathered scalars per point,

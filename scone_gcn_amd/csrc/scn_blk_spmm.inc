@@ -137,6 +137,9 @@ __global__ __launch_bounds__(SP_THREADS, 4) void spmm_blocked_kernel(PlanDev P, 
     if (pend_total >= 0) store_pending();
 }
 
+constexpr auto spmm_blocked_single = spmm_blocked_kernel<false>;      // ya = S_a X (yb null)
+constexpr auto spmm_blocked_dual = spmm_blocked_kernel<true>;         // and yb = S_b X
+
 // ------------------------------------------------------------------------------------------------
 // dual SpMM, K = 128 or 64, as a RING of four half-piece stages: the staged unit is half a row piece (K/2 floats of every
 // source row), so the same 128 KB of LDS holds four stages instead of two buffers and three stages' LDS-DMAs are in flight
@@ -263,3 +266,6 @@ __global__ __launch_bounds__(SP_THREADS, 4) void spmm_ring_kernel(PlanDev P, con
         if (DUAL) __builtin_nontemporal_store(pb, (f32x4*)pend_b);
     }
 }
+
+template <int NI> constexpr auto spmm_ring_single = spmm_ring_kernel<false, NI>;      // ya = S_a X (yb null); NI = K / 64
+template <int NI> constexpr auto spmm_ring_dual = spmm_ring_kernel<true, NI>;         // and yb = S_b X

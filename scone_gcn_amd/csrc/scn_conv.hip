@@ -21,7 +21,7 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wl,
                     hipStream_t st, const float* partial = nullptr);
-bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux, bool has_dx);
+bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux);
 size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux);
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
@@ -675,7 +675,7 @@ int scn_conv_backward_accumulate(scn_conv_t c, int32_t n_slabs, int32_t ns, cons
     if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace || !dx || !dx_partial) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
     if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
-    if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux, true)) return SCN_ERR_UNSUPPORTED;
+    if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
     if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
     return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
                             (hipStream_t)stream, dx_partial);
@@ -693,7 +693,7 @@ int scn_conv_backward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const floa
     if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
     WorkList wlist{0, nullptr, nullptr, nullptr};
     if (wl) wlist = to_list(wl);
-    if (blocked_backward_supported(c, ns, c_dz, c_aux, dx != nullptr))
+    if (blocked_backward_supported(c, ns, c_dz, c_aux))
         return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes,
                                 wl ? &wlist : nullptr, st);
     if (wl) return SCN_ERR_UNSUPPORTED;

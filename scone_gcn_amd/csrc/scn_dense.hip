@@ -518,16 +518,11 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
                 a1.G[k] = G[k]; a1.W[k] = W[k];
             }
             const int blocks = (int)std::min<int64_t>(8192, (n_points * (c_out / 4) + 255) / 256);
-#define SCN_LAUNCH_IN1(CG)                                                                                                   \
-    switch (act) {                                                                                                           \
-        case SCN_ACT_TANH: hipLaunchKernelGGL((dense_fwd_in1_kernel<CG, SCN_ACT_TANH>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a1); break; \
-        case SCN_ACT_RELU: hipLaunchKernelGGL((dense_fwd_in1_kernel<CG, SCN_ACT_RELU>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a1); break; \
-        case SCN_ACT_LEAKY_RELU: hipLaunchKernelGGL((dense_fwd_in1_kernel<CG, SCN_ACT_LEAKY_RELU>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a1); break; \
-        default: hipLaunchKernelGGL((dense_fwd_in1_kernel<CG, SCN_ACT_NONE>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a1); break; \
-    }
-            if (c_out == 16) { SCN_LAUNCH_IN1(4) } else if (c_out == 32) { SCN_LAUNCH_IN1(8) } else { SCN_LAUNCH_IN1(16) }
-            SCN_LAUNCH_CHECK();
-            return SCN_OK;
+            return with_act(act, [&](auto A) -> int {
+                constexpr int ACT = decltype(A)::value;
+                const auto k = c_out == 16 ? dense_fwd_in1_kernel<4, ACT> : (c_out == 32 ? dense_fwd_in1_kernel<8, ACT> : dense_fwd_in1_kernel<16, ACT>);
+                return launch_checked(k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a1);
+            });
         }
     }
     if (n_terms > DN_MAX_TERMS) return SCN_ERR_BAD_SHAPE;
@@ -544,15 +539,9 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
     for (int k = 0; k < n_terms; ++k) all32 = all32 && c_in[k] == 32;
     if (all32) {
         const int blocks = (int)std::min<int64_t>(2048, ((n_points + 31) / 32 + DM_WAVES - 1) / DM_WAVES);
-        hipStream_t st = (hipStream_t)stream;
-        switch (act) {
-            case SCN_ACT_TANH: hipLaunchKernelGGL(dense_fwd_mfma_kernel<SCN_ACT_TANH>, dim3(blocks), dim3(DM_THREADS), 0, st, a); break;
-            case SCN_ACT_RELU: hipLaunchKernelGGL(dense_fwd_mfma_kernel<SCN_ACT_RELU>, dim3(blocks), dim3(DM_THREADS), 0, st, a); break;
-            case SCN_ACT_LEAKY_RELU: hipLaunchKernelGGL(dense_fwd_mfma_kernel<SCN_ACT_LEAKY_RELU>, dim3(blocks), dim3(DM_THREADS), 0, st, a); break;
-            default: hipLaunchKernelGGL(dense_fwd_mfma_kernel<SCN_ACT_NONE>, dim3(blocks), dim3(DM_THREADS), 0, st, a); break;
-        }
-        SCN_LAUNCH_CHECK();
-        return SCN_OK;
+        return with_act(act, [&](auto A) -> int {
+            return launch_checked(dense_fwd_mfma_kernel<decltype(A)::value>, dim3(blocks), dim3(DM_THREADS), 0, (hipStream_t)stream, a);
+        });
     }
     bool same = c_out == 1 && (c_in[0] == 16 || c_in[0] == 32);
     for (int k = 1; k < n_terms; ++k) same = same && c_in[k] == c_in[0];
@@ -612,15 +601,12 @@ int scn_dense_terms_backward(int64_t n_points, int32_t n_terms, const float* con
         g.partial = (float*)workspace;
         for (int k = 0; k < n_terms; ++k) { g.G[k] = G[k]; g.W[k] = W[k]; }
         const int nbs = (int)std::min<int64_t>(1024, (n_points * (c_aux / 4) + 255) / 256);
-#define SCN_LAUNCH_G1(CG)                                                                                         \
-    switch (act) {                                                                                                \
-        case SCN_ACT_TANH: hipLaunchKernelGGL((dense_bwd_g1_kernel<CG, SCN_ACT_TANH>), dim3(nbs), dim3(256), 0, st, g); break; \
-        case SCN_ACT_RELU: hipLaunchKernelGGL((dense_bwd_g1_kernel<CG, SCN_ACT_RELU>), dim3(nbs), dim3(256), 0, st, g); break; \
-        case SCN_ACT_LEAKY_RELU: hipLaunchKernelGGL((dense_bwd_g1_kernel<CG, SCN_ACT_LEAKY_RELU>), dim3(nbs), dim3(256), 0, st, g); break; \
-        default: hipLaunchKernelGGL((dense_bwd_g1_kernel<CG, SCN_ACT_NONE>), dim3(nbs), dim3(256), 0, st, g); break; \
-    }
-        if (c_aux == 16) { SCN_LAUNCH_G1(4) } else if (c_aux == 32) { SCN_LAUNCH_G1(8) } else { SCN_LAUNCH_G1(16) }
-        SCN_LAUNCH_CHECK();
+        const int st_k = with_act(act, [&](auto A) -> int {
+            constexpr int ACT = decltype(A)::value;
+            const auto k = c_aux == 16 ? dense_bwd_g1_kernel<4, ACT> : (c_aux == 32 ? dense_bwd_g1_kernel<8, ACT> : dense_bwd_g1_kernel<16, ACT>);
+            return launch_checked(k, dim3(nbs), dim3(256), 0, st, g);
+        });
+        if (st_k != SCN_OK) return st_k;
         r.partial = g.partial; r.n_partials = nbs; r.total = r.off[n_terms]; r.n_terms = n_terms;
         hipLaunchKernelGGL(dense_dw_reduce, dim3((r.total + 255) / 256), dim3(256), 0, st, r);
         SCN_LAUNCH_CHECK();
@@ -629,18 +615,16 @@ int scn_dense_terms_backward(int64_t n_points, int32_t n_terms, const float* con
     const int nb = dense_blocks(n_points);
     bool all32 = c_aux == 32;
     for (int k = 0; k < n_terms; ++k) all32 = all32 && c[k] == 32;
+    int st_k;
     if (all32) {
-        switch (act) {
-            case SCN_ACT_TANH: hipLaunchKernelGGL(dense_bwd_mfma_kernel<SCN_ACT_TANH>, dim3(nb), dim3(DM_THREADS), 0, st, a); break;
-            case SCN_ACT_RELU: hipLaunchKernelGGL(dense_bwd_mfma_kernel<SCN_ACT_RELU>, dim3(nb), dim3(DM_THREADS), 0, st, a); break;
-            case SCN_ACT_LEAKY_RELU: hipLaunchKernelGGL(dense_bwd_mfma_kernel<SCN_ACT_LEAKY_RELU>, dim3(nb), dim3(DM_THREADS), 0, st, a); break;
-            default: hipLaunchKernelGGL(dense_bwd_mfma_kernel<SCN_ACT_NONE>, dim3(nb), dim3(DM_THREADS), 0, st, a); break;
-        }
+        st_k = with_act(act, [&](auto A) -> int {
+            return launch_checked(dense_bwd_mfma_kernel<decltype(A)::value>, dim3(nb), dim3(DM_THREADS), 0, st, a);
+        });
     } else {
         if (lds > 64 * 1024) return SCN_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(dense_bwd_kernel, dim3(nb), dim3(DN_THREADS), lds, st, a);
+        st_k = launch_checked(dense_bwd_kernel, dim3(nb), dim3(DN_THREADS), lds, st, a);
     }
-    SCN_LAUNCH_CHECK();
+    if (st_k != SCN_OK) return st_k;
     r.partial = a.partial; r.n_partials = nb; r.total = r.off[n_terms]; r.n_terms = n_terms;
     hipLaunchKernelGGL(dense_dw_reduce, dim3((r.total + 255) / 256), dim3(256), 0, st, r);
     SCN_LAUNCH_CHECK();
@@ -659,16 +643,10 @@ int scn_sum_act(int64_t n, int32_t n_terms, const float* const* terms, int32_t a
     if ((uintptr_t)out & 15) return SCN_ERR_BAD_ARG;
     const int64_t n4 = n / 4;
     const dim3 grid((int)std::min<int64_t>(8192, (n4 + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    switch (act) {
-        case SCN_ACT_TANH: hipLaunchKernelGGL(sum_act_kernel<SCN_ACT_TANH>, grid, dim3(256), 0, st, n4, T, out); break;
-        case SCN_ACT_RELU: hipLaunchKernelGGL(sum_act_kernel<SCN_ACT_RELU>, grid, dim3(256), 0, st, n4, T, out); break;
-        case SCN_ACT_LEAKY_RELU: hipLaunchKernelGGL(sum_act_kernel<SCN_ACT_LEAKY_RELU>, grid, dim3(256), 0, st, n4, T, out); break;
-        case SCN_ACT_NONE: hipLaunchKernelGGL(sum_act_kernel<SCN_ACT_NONE>, grid, dim3(256), 0, st, n4, T, out); break;
-        default: return SCN_ERR_BAD_ARG;
-    }
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    if (act != SCN_ACT_NONE && act != SCN_ACT_TANH && act != SCN_ACT_RELU && act != SCN_ACT_LEAKY_RELU) return SCN_ERR_BAD_ARG;
+    return with_act(act, [&](auto A) -> int {
+        return launch_checked(sum_act_kernel<decltype(A)::value>, grid, dim3(256), 0, (hipStream_t)stream, n4, T, out);
+    });
 }
 
 int scn_split_sign(int64_t n, const float* g, float* g_pos, float* g_neg, void* stream) {

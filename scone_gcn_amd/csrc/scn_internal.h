@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <map>
+#include <type_traits>
 #include <vector>
 
 #include "scone_hip.h"
@@ -29,6 +30,33 @@ void set_hip_error(hipError_t e, const char* where);
             return SCN_ERR_HIP;                             \
         }                                                   \
     } while (0)
+
+// The runtime activation code as a compile-time constant: calls f(std::integral_constant<int, SCN_ACT_x>{}) and returns its status.
+// Kernels take the activation as a template parameter; this is the one switch that picks the instantiation.  A code outside the
+// four runs as SCN_ACT_NONE (an entry point that refuses such a code checks it before the call).  SCN_HIP_TRY / SCN_LAUNCH_CHECK
+// inside f return out of f: it returns int, and the caller hands that on.
+template <class F>
+static inline int with_act(int act, F&& f) {
+    switch (act) {
+        case SCN_ACT_TANH: return f(std::integral_constant<int, SCN_ACT_TANH>{});
+        case SCN_ACT_RELU: return f(std::integral_constant<int, SCN_ACT_RELU>{});
+        case SCN_ACT_LEAKY_RELU: return f(std::integral_constant<int, SCN_ACT_LEAKY_RELU>{});
+        default: return f(std::integral_constant<int, SCN_ACT_NONE>{});
+    }
+}
+
+// One checked launch of the kernel (form) k: dynamic LDS above 64 KB is opted into per kernel (160 KB is what a CU has:
+// SCN_ERR_UNSUPPORTED beyond), a launch error becomes SCN_ERR_HIP.  The arguments convert to k's parameter types (nullptr included).
+template <class... KA, class... A>
+static inline int launch_checked(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... a) {
+    static_assert(sizeof...(KA) == sizeof...(A), "one argument per kernel parameter");
+    if (lds > 160 * 1024) return SCN_ERR_UNSUPPORTED;
+    if (lds > 64 * 1024)
+        SCN_HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, grid, block, lds, st, static_cast<KA>(a)...);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
 
 // relu and its negative-part twin that keep a NaN a NaN, like the reference's np.maximum (fmaxf(z, 0.f) returns 0 for a NaN z)
 __device__ __forceinline__ float relu_nan(float z) { return z <= 0.f ? 0.f : z; }

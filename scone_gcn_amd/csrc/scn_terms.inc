@@ -688,11 +688,9 @@ __global__ __launch_bounds__(W16_THREADS, 4) void terms_fwd_c32_kernel(TermsDev 
 
 static size_t terms_fwd_lds() { return (size_t)TK_LDS_BYTES; }
 
-static void terms_grid(const scn_conv_s* c, int n_slabs, dim3& grid) {
+static dim3 terms_grid(const scn_conv_s* c) {
     const int nb = c->plan.dev.n_blocks;
-    const int gx = std::max(8, std::min(256, ((nb + 7) / 8) * 8) / 8 * 8);
-    grid = dim3(gx, 1);
-    (void)n_slabs;
+    return dim3(std::max(8, std::min(256, ((nb + 7) / 8) * 8) / 8 * 8), 1);
 }
 
 int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
@@ -702,22 +700,10 @@ int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float
     TermsPtrs A;
     for (int i = 0; i < 3; ++i) { A.x[i] = x[i]; A.aux[i] = nullptr; A.out[i] = out[i]; }
     for (int i = 0; i < 9; ++i) A.W[i] = W[i];
-    dim3 grid;
-    terms_grid(c, n_slabs, grid);
-    const size_t lds = terms_fwd_lds();
-#define SCN_LAUNCH_TFWD(ACTV)                                                                                     \
-    do {                                                                                                          \
-        SCN_ENSURE_LDS(terms_fwd_c32_kernel<ACTV>, lds);                                                          \
-        hipLaunchKernelGGL(terms_fwd_c32_kernel<ACTV>, grid, dim3(W16_THREADS), lds, st, T, A, n_slabs);          \
-    } while (0)
-    switch (act) {
-        case SCN_ACT_TANH: SCN_LAUNCH_TFWD(SCN_ACT_TANH); break;
-        case SCN_ACT_RELU: SCN_LAUNCH_TFWD(SCN_ACT_RELU); break;
-        case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_TFWD(SCN_ACT_LEAKY_RELU); break;
-        default: SCN_LAUNCH_TFWD(SCN_ACT_NONE); break;
-    }
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    return with_act(act, [&](auto ACT) -> int {
+        return launch_checked(terms_fwd_c32_kernel<decltype(ACT)::value>, terms_grid(c), dim3(W16_THREADS), terms_fwd_lds(), st, T, A,
+                              n_slabs);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1088,9 +1074,12 @@ __global__ void terms_dw_reduce_kernel(const float* __restrict__ partial, int n_
 
 static size_t terms_bwd_lds() { return (size_t)TK_LDS_BYTES; }
 
-size_t terms_backward_workspace(const scn_conv_s* c, int n_slabs) {
-    dim3 grid;
-    terms_grid(c, n_slabs, grid);
+// The forms of terms_bwd_c32_kernel by name:
+template <int ACT> constexpr auto terms_bwd_c32_plain = terms_bwd_c32_kernel<ACT, false>;      // A.out = the input gradients, A.y null
+template <int ACT> constexpr auto terms_bwd_c32_first = terms_bwd_c32_kernel<ACT, true>;       // A.out null: contracted with A.y into A.partial_first
+
+size_t terms_backward_workspace(const scn_conv_s* c, int) {         // (any slab count: the grid covers the blocks)
+    const dim3 grid = terms_grid(c);
     return (size_t)grid.x * grid.y * BK_WAVES * (3072 + 64) * sizeof(float);
 }
 
@@ -1103,31 +1092,18 @@ int terms_backward(scn_conv_s* c, int n_slabs, const float* const* dz, const flo
     TermsPtrs A;
     for (int i = 0; i < 3; ++i) { A.x[i] = dz[i]; A.aux[i] = aux[i]; A.out[i] = first ? nullptr : dx[i]; A.y[i] = first ? y[i] : nullptr; }
     for (int i = 0; i < 9; ++i) A.W[i] = W[i];
-    dim3 grid;
-    terms_grid(c, n_slabs, grid);
+    const dim3 grid = terms_grid(c);
     const int n_wg = (int)(grid.x * grid.y);
     float* partial = (float*)ws;
     A.partial_first = partial + (size_t)n_wg * BK_WAVES * 3072;
     TermsDW D;
     for (int i = 0; i < 9; ++i) D.p[i] = dW[i];
-    const size_t lds = terms_bwd_lds();
-#define SCN_LAUNCH_TBWD(ACTV)                                                                                     \
-    do {                                                                                                          \
-        if (first) {                                                                                              \
-            SCN_ENSURE_LDS((terms_bwd_c32_kernel<ACTV, true>), lds);                                              \
-            hipLaunchKernelGGL((terms_bwd_c32_kernel<ACTV, true>), grid, dim3(BK_THREADS), lds, st, T, A, partial, n_slabs);  \
-        } else {                                                                                                  \
-            SCN_ENSURE_LDS((terms_bwd_c32_kernel<ACTV, false>), lds);                                             \
-            hipLaunchKernelGGL((terms_bwd_c32_kernel<ACTV, false>), grid, dim3(BK_THREADS), lds, st, T, A, partial, n_slabs); \
-        }                                                                                                         \
-    } while (0)
-    switch (act) {
-        case SCN_ACT_TANH: SCN_LAUNCH_TBWD(SCN_ACT_TANH); break;
-        case SCN_ACT_RELU: SCN_LAUNCH_TBWD(SCN_ACT_RELU); break;
-        case SCN_ACT_LEAKY_RELU: SCN_LAUNCH_TBWD(SCN_ACT_LEAKY_RELU); break;
-        default: SCN_LAUNCH_TBWD(SCN_ACT_NONE); break;
-    }
-    SCN_LAUNCH_CHECK();
+    const int st_k = with_act(act, [&](auto ACT) -> int {
+        constexpr int AV = decltype(ACT)::value;
+        return launch_checked(first ? terms_bwd_c32_first<AV> : terms_bwd_c32_plain<AV>, grid, dim3(BK_THREADS), terms_bwd_lds(), st, T, A,
+                              partial, n_slabs);
+    });
+    if (st_k != SCN_OK) return st_k;
     hipLaunchKernelGGL(terms_dw_reduce_kernel, dim3(12, 3), dim3(256), 0, st, partial, n_wg, T.bins[0] >> 3, T.bins[1] >> 3, D);
     SCN_LAUNCH_CHECK();
     if (first) {

@@ -140,6 +140,30 @@ def _dev(t, dtype=torch.float32):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _ptrs(tensors, dtype=torch.float32):
+    """The array-of-device-pointers argument of a call: None entries stay NULL (an absent level or term), a 3 x 3 list of lists goes
+    in row by row."""
+    if tensors and isinstance(tensors[0], (list, tuple)):
+        tensors = [t for row in tensors for t in row]
+    return ptr_array([_dev(t, dtype).value if t is not None else None for t in tensors])
+
+
+def _workspace(nbytes, device, floor=0):
+    """The (pointer, size) argument pair of a call's scratch buffer of max(nbytes, floor) bytes; the pointer object keeps the buffer."""
+    ws = torch.empty(max(int(nbytes), floor), device=device, dtype=torch.uint8)
+    p = ctypes.c_void_p(ws.data_ptr())
+    p.buffer = ws
+    return p, ws.numel()
+
+
+def _served(status, name):
+    """False when the library does not take the shape (SCN_ERR_UNSUPPORTED: the caller falls back), any other error raises."""
+    if status == _lib.SCN_ERR_UNSUPPORTED:
+        return False
+    check(status, name)
+    return True
+
+
 class WorkList:
     """Device copy of a (block, slab) work list of the zero-skipping mode (scn_work_list).  Built from a boolean
     scipy matrix A[slab, block]; `items` counts the (block, slab) pairs."""
@@ -240,13 +264,11 @@ class ConvOp:
             out = torch.empty((S, self.n_rows, ns, c_out), device=srcs[0].device, dtype=torch.float32)
         if partial is not None:
             with _timed("conv_fwd c%s->%d + partial" % ("+".join(map(str, c_in)), c_out), _nbytes(out, partial, *srcs) + self.csr_bytes):
-                check(lib.scn_conv_forward_accumulate(self.handle, S, ns, ptr_array([_dev(x).value for x in srcs]), i32_array(c_in),
-                                                      ptr_array([_dev(w).value for w in Ws]), c_out, ACT[act], _dev(partial), _dev(out),
-                                                      _stream()), "scn_conv_forward_accumulate")
+                check(lib.scn_conv_forward_accumulate(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act],
+                                                      _dev(partial), _dev(out), _stream()), "scn_conv_forward_accumulate")
             return out
         with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if wl is not None else _nbytes(out, *srcs) + self.csr_bytes):
-            check(lib.scn_conv_forward_list(self.handle, S, ns, ptr_array([_dev(x).value for x in srcs]), i32_array(c_in),
-                                            ptr_array([_dev(w).value for w in Ws]), c_out, ACT[act], _dev(out),
+            check(lib.scn_conv_forward_list(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
                                             wl.ref() if wl is not None else None, _stream()), "scn_conv_forward")
         return out
 
@@ -268,25 +290,20 @@ class ConvOp:
         for s, (w, dw) in enumerate(zip(Ws, dWs)):
             assert tuple(w.shape) == (c_aux, c_dz[self.slot_group[s]]) and tuple(dw.shape) == tuple(w.shape)
         cdz = i32_array(c_dz)
-        nbytes = lib.scn_conv_backward_workspace(self.handle, S, ns, cdz, c_aux)
-        ws = torch.empty(max(int(nbytes), 256), device=aux.device, dtype=torch.uint8)
+        ws = _workspace(lib.scn_conv_backward_workspace(self.handle, S, ns, cdz, c_aux), aux.device, 256)
         if need_dx and dx is None:
             dx = torch.empty_like(aux)
         if dx_partial is not None:
             with _timed("conv_bwd c%s->%d + partial" % ("+".join(map(str, c_dz)), c_aux), _nbytes(aux, dx, dx_partial, *dzs) + self.csr_bytes):
-                check(lib.scn_conv_backward_accumulate(self.handle, S, ns, ptr_array([_dev(x).value for x in dzs]), cdz,
-                                                       ptr_array([_dev(w).value for w in Ws]), _dev(aux), c_aux, ACT[act],
-                                                       _dev(dx_partial), _dev(dx), ptr_array([_dev(d).value for d in dWs]),
-                                                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+                check(lib.scn_conv_backward_accumulate(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
+                                                       _dev(dx_partial), _dev(dx), _ptrs(dWs), *ws, _stream()),
                       "scn_conv_backward_accumulate")
             return dx
         with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
                     None if wl is not None else _nbytes(aux, dx if need_dx else None, *dzs) + self.csr_bytes):
-            check(lib.scn_conv_backward_list(self.handle, S, ns, ptr_array([_dev(x).value for x in dzs]), cdz,
-                                             ptr_array([_dev(w).value for w in Ws]), _dev(aux), c_aux, ACT[act],
-                                             _dev(dx) if need_dx else None, ptr_array([_dev(d).value for d in dWs]),
-                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                             wl.ref() if wl is not None else None, _stream()), "scn_conv_backward")
+            check(lib.scn_conv_backward_list(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
+                                             _dev(dx) if need_dx else None, _ptrs(dWs), *ws, wl.ref() if wl is not None else None,
+                                             _stream()), "scn_conv_backward")
         return dx if need_dx else None
 
     def forward_first(self, x, Ws, c_out, act, out=None, y=None, wl=None):
@@ -302,12 +319,9 @@ class ConvOp:
         if y is None:
             y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
         with _timed("conv_fwd c1->%d" % c_out, None if wl is not None else _nbytes(x, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), ptr_array([_dev(w).value for w in Ws]), c_out,
-                                            ACT[act], _dev(out), _dev(y), wl.ref() if wl is not None else None, _stream())
-        if st == _lib.SCN_ERR_UNSUPPORTED:
-            return None
-        check(st, "scn_conv_forward_first")
-        return out, y
+            st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), _ptrs(Ws), c_out, ACT[act], _dev(out), _dev(y),
+                                            wl.ref() if wl is not None else None, _stream())
+        return (out, y) if _served(st, "scn_conv_forward_first") else None
 
     def shifted_input(self, x):
         """y = (x, S_lo x, S_up x, 0) per point of a 1-channel input WITHOUT the first layer's output (scn_conv_forward_first with
@@ -317,13 +331,10 @@ class ConvOp:
         if c_in != 1 or self.n_groups != 1 or self.n_slots != 3:
             return None
         y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
-        dummy = ptr_array([_dev(x).value] * 3)        # (the weights are not read without an output; the call checks them for NULL)
+        dummy = _ptrs([x] * 3)                        # (the weights are not read without an output; the call checks them for NULL)
         with _timed("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes):
             st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
-        if st == _lib.SCN_ERR_UNSUPPORTED:
-            return None
-        check(st, "scn_conv_forward_first")
-        return y
+        return y if _served(st, "scn_conv_forward_first") else None
 
     def forward_from_y(self, y, Ws_first, Ws, act):
         """The layer AFTER a 1-channel first layer from that layer's shifted input y and weights Ws_first: act(sum_s (S_s H1) Ws[s]) with
@@ -338,12 +349,8 @@ class ConvOp:
         # (the key of the plain C -> C forward: the same kernel family, and what callers that look for the fused layer kernels expect;
         # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
         with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), ptr_array([_dev(w).value for w in Ws_first]),
-                                             ptr_array([_dev(w).value for w in Ws]), c, ACT[act], _dev(out), _stream())
-        if st == _lib.SCN_ERR_UNSUPPORTED:
-            return None
-        check(st, "scn_conv_forward_from_y")
-        return out
+            st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
+        return out if _served(st, "scn_conv_forward_from_y") else None
 
     def forward_power(self, x0, x, Ws, act):
         """out = act(x0 W0 + x W1 + (S x) W2) for an operator with identity + one value array (scn_conv_forward_power);
@@ -352,12 +359,8 @@ class ConvOp:
         S, rows, ns, c = x.shape
         out = torch.empty_like(x)
         with _timed("conv_fwd_power c%d" % c, _nbytes(x0, x, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_power(self.handle, S, ns, _dev(x0), _dev(x), ptr_array([_dev(w).value for w in Ws]), c,
-                                            ACT[act], _dev(out), _stream())
-        if st == _lib.SCN_ERR_UNSUPPORTED:
-            return None
-        check(st, "scn_conv_forward_power")
-        return out
+            st = lib.scn_conv_forward_power(self.handle, S, ns, _dev(x0), _dev(x), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
+        return out if _served(st, "scn_conv_forward_power") else None
 
     def backward_power(self, dz, g1, Ws, aux, act, need_dx, dWs):
         """Backward of forward_power given g1 = S^T dz (scn_conv_backward_power); returns (served, dx)."""
@@ -366,13 +369,11 @@ class ConvOp:
         nbytes = int(lib.scn_conv_backward_power_workspace(self.handle, S, ns, c))
         if nbytes == 0:
             return False, None
-        ws = torch.empty(nbytes, device=dz.device, dtype=torch.uint8)
+        ws = _workspace(nbytes, dz.device)
         dx = torch.empty_like(aux) if need_dx else None
         with _timed("conv_bwd_power c%d" % c, _nbytes(dz, g1, aux, dx) + self.csr_bytes):
-            check(lib.scn_conv_backward_power(self.handle, S, ns, _dev(dz), _dev(g1), ptr_array([_dev(w).value for w in Ws]),
-                                              _dev(aux), c, ACT[act], _dev(dx) if need_dx else None,
-                                              ptr_array([_dev(d).value for d in dWs]), ctypes.c_void_p(ws.data_ptr()),
-                                              ws.numel(), _stream()), "scn_conv_backward_power")
+            check(lib.scn_conv_backward_power(self.handle, S, ns, _dev(dz), _dev(g1), _ptrs(Ws), _dev(aux), c, ACT[act],
+                                              _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _stream()), "scn_conv_backward_power")
         return True, dx
 
     def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None):
@@ -389,23 +390,16 @@ class ConvOp:
         nbytes = int(lib.scn_conv_backward_fused_first_workspace(self.handle, S, ns, c))
         if nbytes == 0:
             return False
-        ws = torch.empty(nbytes, device=dz.device, dtype=torch.uint8)
+        ws = _workspace(nbytes, dz.device)
+        tail = (_dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws, wl.ref() if wl is not None else None, _stream())
         if aux is None:
             with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, y) + self.csr_bytes):
-                check(lib.scn_conv_backward_fused_first_from_y(self.handle, S, ns, _dev(dz), ptr_array([_dev(w).value for w in Ws]),
-                                                               ptr_array([_dev(w).value for w in Ws_first]), c, ACT[act], _dev(y),
-                                                               ptr_array([_dev(d).value for d in dWs]),
-                                                               ptr_array([_dev(d).value for d in dWs_first]),
-                                                               ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                                               wl.ref() if wl is not None else None, _stream()),
+                check(lib.scn_conv_backward_fused_first_from_y(self.handle, S, ns, _dev(dz), _ptrs(Ws), _ptrs(Ws_first), c, ACT[act], *tail),
                       "scn_conv_backward_fused_first_from_y")
             return True
         with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, aux, y) + self.csr_bytes):
-            check(lib.scn_conv_backward_fused_first(self.handle, S, ns, _dev(dz), ptr_array([_dev(w).value for w in Ws]), _dev(aux),
-                                                    c, ACT[act], _dev(y), ptr_array([_dev(d).value for d in dWs]),
-                                                    ptr_array([_dev(d).value for d in dWs_first]),
-                                                    ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                                    wl.ref() if wl is not None else None, _stream()), "scn_conv_backward_fused_first")
+            check(lib.scn_conv_backward_fused_first(self.handle, S, ns, _dev(dz), _ptrs(Ws), _dev(aux), c, ACT[act], *tail),
+                  "scn_conv_backward_fused_first")
         return True
 
     def clear(self, t, wl):
@@ -433,12 +427,11 @@ class ConvOp:
         nbytes = int(lib.scn_conv_dw_first_workspace(self.handle, S, ns, c))
         if nbytes == 0:
             return False
-        ws = torch.empty(nbytes, device=dz.device, dtype=torch.uint8)
+        ws = _workspace(nbytes, dz.device)
         with _timed("conv_dw_first c%d" % c, None if wl is not None else _nbytes(dz) + 4.0 * S * rows * ns + self.csr_bytes):
-            check(lib.scn_conv_dw_first(self.handle, S, ns, _dev(x) if x is not None else None,
-                                        _dev(y) if y is not None else None, _dev(dz), c,
-                                        ptr_array([_dev(d).value for d in dWs]), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                        wl.ref() if wl is not None else None, _stream()), "scn_conv_dw_first")
+            check(lib.scn_conv_dw_first(self.handle, S, ns, _dev(x) if x is not None else None, _dev(y) if y is not None else None,
+                                        _dev(dz), c, _ptrs(dWs), *ws, wl.ref() if wl is not None else None, _stream()),
+                  "scn_conv_dw_first")
         return True
 
     def spmm_dual(self, x, dual=True):
@@ -509,13 +502,9 @@ class TermsOp:
         S, ns = ref.shape[0], ref.shape[2]
         outs = [torch.empty((S, self.sizes[l], ns, 32), device=ref.device, dtype=torch.float32) if want[l] else None
                 for l in range(3)]
-        flatW = [Ws[l][j] for l in range(3) for j in range(3)]
         nb = _nbytes(*[x for x in xs if x is not None], *[o for o in outs if o is not None]) + self.csr_bytes
         with _timed("terms_fwd c32", nb):
-            check(lib.scn_terms_forward(self.handle, S, ns, ptr_array([_dev(x).value if x is not None else None for x in xs]),
-                                        ptr_array([_dev(w).value if w is not None else None for w in flatW]), 32, ACT[act],
-                                        ptr_array([_dev(o).value if o is not None else None for o in outs]), _stream()),
-                  "scn_terms_forward")
+            check(lib.scn_terms_forward(self.handle, S, ns, _ptrs(xs), _ptrs(Ws), 32, ACT[act], _ptrs(outs), _stream()), "scn_terms_forward")
         return outs
 
 
@@ -528,13 +517,11 @@ def _terms_backward(op, dzs, Ws, auxs, act, want_dx, dWs):
     dxs = [torch.empty((S, op.sizes[l], ns, 32), device=ref.device, dtype=torch.float32) if want_dx[l] else None for l in range(3)]
     nbytes = int(lib.scn_terms_backward_workspace(op.handle, S, ns, 32))
     assert nbytes > 0, "terms backward not served"
-    ws = torch.empty(nbytes, device=ref.device, dtype=torch.uint8)
-    flat = lambda M: ptr_array([_dev(M[l][j]).value if M[l][j] is not None else None for l in range(3) for j in range(3)])
-    p3 = lambda L: ptr_array([_dev(t).value if t is not None else None for t in L])
+    ws = _workspace(nbytes, ref.device)
     nb = _nbytes(*[x for x in dzs if x is not None], *[x for x in auxs if x is not None], *[x for x in dxs if x is not None]) + op.csr_bytes
     with _timed("terms_bwd c32", nb):
-        check(lib.scn_terms_backward(op.handle, S, ns, p3(dzs), flat(Ws), p3(auxs), 32, ACT[act], p3(dxs), flat(dWs),
-                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "scn_terms_backward")
+        check(lib.scn_terms_backward(op.handle, S, ns, _ptrs(dzs), _ptrs(Ws), _ptrs(auxs), 32, ACT[act], _ptrs(dxs), _ptrs(dWs), *ws,
+                                     _stream()), "scn_terms_backward")
     return dxs
 
 
@@ -547,14 +534,11 @@ def _terms_backward_first(op, dzs, Ws, auxs, act, ys, dWs, dWs_first):
     S, ns = ref.shape[0], ref.shape[2]
     nbytes = int(lib.scn_terms_backward_workspace(op.handle, S, ns, 32))
     assert nbytes > 0, "terms backward not served"
-    ws = torch.empty(nbytes, device=ref.device, dtype=torch.uint8)
-    flat = lambda M: ptr_array([_dev(M[l][j]).value if M[l][j] is not None else None for l in range(3) for j in range(3)])
-    p3 = lambda L: ptr_array([_dev(t).value if t is not None else None for t in L])
+    ws = _workspace(nbytes, ref.device)
     nb = _nbytes(*[x for x in dzs if x is not None], *[x for x in auxs if x is not None], *[x for x in ys if x is not None]) + op.csr_bytes
     with _timed("terms_bwd c32 + dW_first", nb):
-        check(lib.scn_terms_backward_fused_first(op.handle, S, ns, p3(dzs), flat(Ws), p3(auxs), 32, ACT[act], p3(ys), flat(dWs),
-                                                 p3(dWs_first), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
-              "scn_terms_backward_fused_first")
+        check(lib.scn_terms_backward_fused_first(op.handle, S, ns, _ptrs(dzs), _ptrs(Ws), _ptrs(auxs), 32, ACT[act], _ptrs(ys), _ptrs(dWs),
+                                                 _ptrs(dWs_first), *ws, _stream()), "scn_terms_backward_fused_first")
 
 
 def _pairable(widths, ns):
@@ -596,9 +580,8 @@ def dense_terms_forward(Gs, Ws, c_out, act):
                           for c0 in range(0, c_out, 32)], dim=3)
     out = torch.empty((S, R, ns, c_out), device=Gs[0].device, dtype=torch.float32)
     with _timed("dense_fwd x%d ->%d" % (len(Gs), c_out), _nbytes(out, *Gs)):
-        check(lib.scn_dense_terms_forward(S * R * ns, len(Gs), ptr_array([_dev(g).value for g in Gs]),
-                                          i32_array([g.shape[3] for g in Gs]), ptr_array([_dev(w).value for w in Ws]),
-                                          c_out, ACT[act], _dev(out), _stream()), "scn_dense_terms_forward")
+        check(lib.scn_dense_terms_forward(S * R * ns, len(Gs), _ptrs(Gs), i32_array(cins), _ptrs(Ws), c_out, ACT[act], _dev(out), _stream()),
+              "scn_dense_terms_forward")
     return out
 
 
@@ -616,15 +599,11 @@ def dense_terms_backward(Gs, Ws, aux, act, need_dx, dWs):
         return _dense_terms_backward_blocks(Gs, Ws, aux, act, need_dx, dWs)
     cs = i32_array([g.shape[3] for g in Gs])
     n_points = S * R * ns
-    nbytes = lib.scn_dense_terms_backward_workspace(n_points, len(Gs), cs, c_aux)
-    ws = torch.empty(max(int(nbytes), 256), device=aux.device, dtype=torch.uint8)
+    ws = _workspace(lib.scn_dense_terms_backward_workspace(n_points, len(Gs), cs, c_aux), aux.device, 256)
     dx = torch.empty_like(aux) if need_dx else None
     with _timed("dense_bwd x%d" % len(Gs), _nbytes(aux, dx, *Gs)):
-        check(lib.scn_dense_terms_backward(n_points, len(Gs), ptr_array([_dev(g).value for g in Gs]), cs,
-                                           ptr_array([_dev(w).value for w in Ws]), _dev(aux), c_aux, ACT[act],
-                                           _dev(dx) if need_dx else None, ptr_array([_dev(d).value for d in dWs]),
-                                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
-              "scn_dense_terms_backward")
+        check(lib.scn_dense_terms_backward(n_points, len(Gs), _ptrs(Gs), cs, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
+                                           _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _stream()), "scn_dense_terms_backward")
     return dx
 
 
@@ -769,7 +748,7 @@ def promoted_width(widths, wide=False):
 def sum_act(terms, act, out=None):
     """out = act(terms[0] + terms[1] + ...) elementwise (scn_sum_act; out defaults to terms[0], in place)."""
     out = terms[0] if out is None else out
-    check(_lib.load().scn_sum_act(out.numel(), len(terms), ptr_array([_dev(t).value for t in terms]), ACT[act], _dev(out), _stream()),
+    check(_lib.load().scn_sum_act(out.numel(), len(terms), _ptrs(terms), ACT[act], _dev(out), _stream()),
           "scn_sum_act")
     return out
 
@@ -1045,7 +1024,7 @@ class SconePlan:
         lib = _lib.load()
         if not lib.scn_small_step_supported(self.conv.handle, L, hidden, self.max_deg, self.max_items):
             return False
-        ws = torch.empty(int(lib.scn_small_step_workspace(E, S * ns, L)), device=x.device, dtype=torch.uint8)
+        ws = _workspace(lib.scn_small_step_workspace(E, S * ns, L), x.device)
         # bytes the launch has to move at least: the input flows, the saved activations written and read back, the operator
         nb = x.numel() * 4 + 2 * (L - 1) * S * ns * E * hidden * 4 + self.conv.csr_bytes
         if adam is not None:
@@ -1055,9 +1034,9 @@ class SconePlan:
                 check(lib.scn_small_step_adam(self.conv.handle, self.conv_T.handle, S, ns, L, hidden, _dev(x), _dev(last_dev, torch.int32),
                                               _dev(yt), float(scale), _dev(self.nbr, torch.int32), self.n_nodes, self.max_deg,
                                               self.max_items, _dev(self.inc_ptr, torch.int32), _dev(self.inc_edge, torch.int32),
-                                              _dev(self.inc_sign), ptr_array([_dev(w).value for w in weights]), ACT[self.act],
-                                              ptr_array([_dev(g).value for g in grads]), ctypes.c_void_p(loss.data_ptr()),
-                                              ctypes.c_void_p(ws.data_ptr()), ws.numel(), _dev(flat_w), _dev(m), _dev(v), float(lr),
+                                              _dev(self.inc_sign), _ptrs(weights), ACT[self.act],
+                                              _ptrs(grads), ctypes.c_void_p(loss.data_ptr()),
+                                              *ws, _dev(flat_w), _dev(m), _dev(v), float(lr),
                                               0.9, 0.999, 1e-8, ctypes.c_void_p(step_dev.data_ptr()), float(wd), _stream()),
                       "scn_small_step_adam")
             return True
@@ -1065,9 +1044,9 @@ class SconePlan:
             check(lib.scn_small_step(self.conv.handle, self.conv_T.handle, S, ns, L, hidden, _dev(x), _dev(last_dev, torch.int32),
                                      _dev(yt), float(scale), _dev(self.nbr, torch.int32), self.n_nodes, self.max_deg,
                                      self.max_items, _dev(self.inc_ptr, torch.int32), _dev(self.inc_edge, torch.int32),
-                                     _dev(self.inc_sign), ptr_array([_dev(w).value for w in weights]), ACT[self.act],
-                                     ptr_array([_dev(g).value for g in grads]), ctypes.c_void_p(loss.data_ptr()),
-                                     1 if overwrite else 0, ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+                                     _dev(self.inc_sign), _ptrs(weights), ACT[self.act],
+                                     _ptrs(grads), ctypes.c_void_p(loss.data_ptr()),
+                                     1 if overwrite else 0, *ws, _stream()),
                   "scn_small_step")
         return True
 
@@ -1092,7 +1071,7 @@ class SconePlan:
                 bhs.append(bh)
                 parts.append(lg)
             logp = torch.empty_like(parts[0])
-            check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), ptr_array([_dev(t).value for t in parts]),
+            check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), _ptrs(parts),
                                                          _dev(parts[0]), _dev(logp), _stream()), "scn_logits_sum_log_softmax")
             return logp, (hs, bhs, y0, None, wp, "wide")
         hs, y0 = self.conv_stack(x, w, activity)
