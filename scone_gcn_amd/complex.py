@@ -367,6 +367,7 @@ class SimplicialComplex:
 
     def __init__(self, cx, reorder=True):
         self.cx = cx
+        self._bunch_layout = None                             # bunch_layout(), built on first use
         self.B1, self.B2 = incidence_matrices(cx)
         self.nbrhoods, self.degrees = neighborhood_table(cx)
         self.max_degree = int(self.nbrhoods.shape[1])
@@ -430,7 +431,7 @@ class SimplicialComplex:
         common frame, no per-block re-sorting), plus the merged order of the three levels along that curve -- the fused Bunch
         layer cuts its blocks as patches across the levels (scn_terms_create).  Without coordinates: the default orders, merged
         level by level (correct, but the patches then have no cross-level locality)."""
-        if getattr(self, "_bunch_layout", None) is None:
+        if self._bunch_layout is None:
             cx = self.cx
             sizes = (cx.n_nodes, cx.n_edges, cx.n_faces)
             if cx.coords is not None and cx.n_edges > 1 and cx.n_faces > 0:

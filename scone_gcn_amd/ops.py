@@ -5,6 +5,7 @@ expose forward / backward over "flow slabs" ([n_slabs, rows, ns, C] fp32, see in
 """
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -770,12 +771,66 @@ def demote_grads(grads, padded):
 
 
 # ----------------------------------------------------------------------------------------------
+# what the callers ask of either plan family; what a forward hands its backward
+# ----------------------------------------------------------------------------------------------
+
+class Plan:
+    """Common to SconePlan / PowerPlan / BunchPlan.  Each has forward(x, last_dev, weights) -> (logp, saved record), _backward of that
+    record, promotion(weights) and n_rows = the rows of one trajectory's activation (all levels), which the micro-batch rule prices."""
+    weights_per_layer = None      # 3 (scone / ebli: identity, lower, upper) or 7 (the Bunch shifts)
+
+    def backward(self, saved, logp, d_logp, last_dev, weights, grads):
+        """grads: list of tensors (same shapes as weights) accumulated into."""
+        wp = saved.promoted
+        if wp is None:
+            return self._backward(saved, logp, d_logp, last_dev, weights, grads)
+        gp = [torch.zeros_like(w) if w is not w0 else g for w, w0, g in zip(wp, weights, grads)]
+        self._backward(saved, logp, d_logp, last_dev, wp, gp)      # gradients of the padded matrices, cut back afterwards
+        demote_grads(grads, gp)
+        return grads
+
+    def layer_widths(self, weights):
+        """[1, width of layer 1, ...] of a weight list (or the list of its shapes) as this plan runs it: with the promoted width in
+        place of every hidden width where the stack is promoted."""
+        shapes = _shapes(weights)
+        k = self.weights_per_layer
+        widths = [1] + [int(shapes[k * i][1]) for i in range(len(shapes) // k)]
+        P = self.promotion(shapes)
+        return [w if w == 1 else P for w in widths] if P else widths
+
+
+def _shapes(weights):
+    return [tuple(getattr(w, "shape", w)) for w in weights]
+
+
+class SconeState(NamedTuple):
+    """SconePlan / PowerPlan.forward -> backward / release."""
+    hs: list            # [x, H_1 .. H_L]; H_1 is None where it is rebuilt from y0; wide: every entry the list of its 32-channel blocks
+    bh: object          # the readout's gathered rows (wide: one per block of H_L)
+    y0: object          # the first layer's shifted input, or None
+    activity: object    # work lists of the zero-skipping mode, or None
+    promoted: object    # the zero-padded weights the stack ran on, or None
+    wide: bool          # hidden widths above 32 ran in 32-channel blocks (_wide_stack / _wide_backward)
+
+
+class BunchState(NamedTuple):
+    """BunchPlan.forward -> backward."""
+    states: list        # per layer boundary the three level tensors (None: not computed)
+    zeros: list         # ... and which of them are identically zero
+    first_g: dict       # slot k -> S_k x of the 1-channel input, where the first layer ran per shift
+    fold: object        # slot k2 -> (S_k2 g^+, S_k2 g^-, k1) of the rank-one fold of the first two layers, or None
+    promoted: object    # the zero-padded weights the stack ran on, or None
+
+
+# ----------------------------------------------------------------------------------------------
 # scone / ebli
 # ----------------------------------------------------------------------------------------------
 
-class SconePlan:
+class SconePlan(Plan):
     """Device state of a scone/ebli model: the fused conv operator (identity + S_lower + S_upper on their shared
     pattern), its transpose when the shifts are not symmetric, and the readout tables."""
+    weights_per_layer = 3
+    fused_conv = True             # identity + both shifts as ONE operator (self.conv): what the recompute-first and wide stacks run on
 
     def __init__(self, S_lower, S_upper, bconds, act, device):
         assert isinstance(S_lower, Shift) and isinstance(S_upper, Shift), "shifts must come from SimplicialComplex"
@@ -783,12 +838,13 @@ class SconePlan:
         self.act = act
         self.device = device
         E = S_lower.shape[0]
-        self.n_edges = E
+        self.n_edges = self.n_rows = E
         self._init_operators(S_lower, S_upper)
         self.bconds = bconds
         self._dz_zero = {}                              # all-zero readout-gradient buffers, by shape (see backward)
         self._zero_pool = {}                            # zero-skipping mode: all-zero activation / gradient buffers
         self._blocks = None                             # (block of row, block adjacency), built on first use
+        self._act_cache = None                          # _trajectory_supports of the last data set
         self._upload_readout()
 
     def _upload_readout(self):
@@ -865,7 +921,7 @@ class SconePlan:
         """Whether this stack runs without a stored H1: plain scone plan, 1-channel input, every hidden width 32 (no promotion), at
         least two layers, dense launches, symmetric or not.  All observed, not chosen; RECOMPUTE_FIRST is the tests' and A/B's switch."""
         L = (len(weights) - 1) // 3
-        return (RECOMPUTE_FIRST and FUSE_FIRST and type(self) is SconePlan and activity is None and x.shape[3] == 1 and L >= 2
+        return (RECOMPUTE_FIRST and FUSE_FIRST and self.fused_conv and activity is None and x.shape[3] == 1 and L >= 2
                 and x.shape[2] == NS and self._blocked()
                 and [tuple(w.shape) for w in weights[:-1]] == [(1, 32)] * 3 + [(32, 32)] * (3 * (L - 1)))
 
@@ -886,7 +942,7 @@ class SconePlan:
 
     def _readout_rows(self):
         """(n_nodes x n_edges) 0/1: device rows of the edges incident to a neighbour of the node (what Bcond(node) reads)."""
-        if getattr(self, "_ro_rows", None) is None:
+        if self._ro_rows is None:
             import scipy.sparse as sp
             V, D = self._h_nbr.shape
             r, c = np.nonzero(self._h_nbr >= 0)
@@ -915,7 +971,7 @@ class SconePlan:
             h.update(np.ascontiguousarray(fa).view(np.uint8))
         h.update(np.ascontiguousarray(ln, np.int64).view(np.uint8))
         key = (n_layers, h.hexdigest())
-        c = getattr(self, "_act_cache", None)
+        c = self._act_cache
         if c is not None and c["key"] == key:
             return c
         blk_of, radj, to_blk, nb = self._block_graph()
@@ -975,15 +1031,24 @@ class SconePlan:
 
     def release(self, saved):
         """Forward-only use of the zero-skipping mode (prediction): hand the forward's pooled buffers back, all-zero again."""
-        hs, bh, y0, activity = saved[:4]
-        if activity:
-            for l in range(1, len(hs)):
-                self._give_back(hs[l], activity["fwd"][l - 1])
-            self._give_back(y0, activity["fwd"][0])
+        if saved.activity:
+            self._give_back_forward(saved)
 
     def _give_back(self, t, wl):
         self.conv.clear(t, wl)                              # all-zero again
         self._zero_pool.setdefault(tuple(t.shape), []).append(t)
+
+    def _give_back_forward(self, saved):
+        for l in range(1, len(saved.hs)):
+            self._give_back(saved.hs[l], saved.activity["fwd"][l - 1])
+        self._give_back(saved.y0, saved.activity["fwd"][0])
+
+    def _readout_args(self, last_dev, sign=True, edge_nodes=False):
+        """The readout tables as every launch that reads them takes them: nbr, n_nodes, max_deg, last nodes, inc_ptr, inc_edge
+        [, inc_sign][, edge_nodes].  last_dev = None: the one-launch step's form -- it takes the last nodes earlier and max_items here."""
+        i32 = lambda t: _dev(t, torch.int32)
+        return (i32(self.nbr), self.n_nodes, self.max_deg, self.max_items if last_dev is None else i32(last_dev), i32(self.inc_ptr),
+                i32(self.inc_edge)) + ((_dev(self.inc_sign),) if sign else ()) + ((i32(self.edge_nodes),) if edge_nodes else ())
 
     def readout(self, H, w_last, last_dev):
         lib = _lib.load()
@@ -993,9 +1058,7 @@ class SconePlan:
         bh = torch.empty((N, self.max_deg, C), device=H.device, dtype=torch.float32)
         logits = torch.empty((N, self.max_deg), device=H.device, dtype=torch.float32)
         logp = torch.empty_like(logits)
-        check(lib.scn_readout_forward(S, ns, E, C, _dev(H), _dev(w_last), _dev(self.nbr, torch.int32), self.n_nodes,
-                                      self.max_deg, _dev(last_dev, torch.int32), _dev(self.inc_ptr, torch.int32),
-                                      _dev(self.inc_edge, torch.int32), _dev(self.inc_sign), _dev(bh), _dev(logits),
+        check(lib.scn_readout_forward(S, ns, E, C, _dev(H), _dev(w_last), *self._readout_args(last_dev), _dev(bh), _dev(logits),
                                       _dev(logp), _stream()), "scn_readout_forward")
         return logp, bh, logits
 
@@ -1027,42 +1090,32 @@ class SconePlan:
         ws = _workspace(lib.scn_small_step_workspace(E, S * ns, L), x.device)
         # bytes the launch has to move at least: the input flows, the saved activations written and read back, the operator
         nb = x.numel() * 4 + 2 * (L - 1) * S * ns * E * hidden * 4 + self.conv.csr_bytes
-        if adam is not None:
-            assert overwrite, "the fused optimiser step takes the whole gradient of the batch"
-            flat_w, m, v, lr, wd, step_dev = adam
-            with _timed("small_step L%d c%d" % (L, hidden), nb):
-                check(lib.scn_small_step_adam(self.conv.handle, self.conv_T.handle, S, ns, L, hidden, _dev(x), _dev(last_dev, torch.int32),
-                                              _dev(yt), float(scale), _dev(self.nbr, torch.int32), self.n_nodes, self.max_deg,
-                                              self.max_items, _dev(self.inc_ptr, torch.int32), _dev(self.inc_edge, torch.int32),
-                                              _dev(self.inc_sign), _ptrs(weights), ACT[self.act],
-                                              _ptrs(grads), ctypes.c_void_p(loss.data_ptr()),
-                                              *ws, _dev(flat_w), _dev(m), _dev(v), float(lr),
-                                              0.9, 0.999, 1e-8, ctypes.c_void_p(step_dev.data_ptr()), float(wd), _stream()),
-                      "scn_small_step_adam")
-            return True
+        assert adam is None or overwrite, "the fused optimiser step takes the whole gradient of the batch"
+        args = (self.conv.handle, self.conv_T.handle, S, ns, L, hidden, _dev(x), _dev(last_dev, torch.int32), _dev(yt), float(scale),
+                *self._readout_args(None), _ptrs(weights), ACT[self.act], _ptrs(grads), ctypes.c_void_p(loss.data_ptr()))
         with _timed("small_step L%d c%d" % (L, hidden), nb):
-            check(lib.scn_small_step(self.conv.handle, self.conv_T.handle, S, ns, L, hidden, _dev(x), _dev(last_dev, torch.int32),
-                                     _dev(yt), float(scale), _dev(self.nbr, torch.int32), self.n_nodes, self.max_deg,
-                                     self.max_items, _dev(self.inc_ptr, torch.int32), _dev(self.inc_edge, torch.int32),
-                                     _dev(self.inc_sign), _ptrs(weights), ACT[self.act],
-                                     _ptrs(grads), ctypes.c_void_p(loss.data_ptr()),
-                                     1 if overwrite else 0, *ws, _stream()),
-                  "scn_small_step")
+            if adam is None:
+                check(lib.scn_small_step(*args, 1 if overwrite else 0, *ws, _stream()), "scn_small_step")
+            else:
+                flat_w, m, v, lr, wd, step_dev = adam
+                check(lib.scn_small_step_adam(*args, *ws, _dev(flat_w), _dev(m), _dev(v), float(lr), 0.9, 0.999, 1e-8,
+                                              ctypes.c_void_p(step_dev.data_ptr()), float(wd), _stream()), "scn_small_step_adam")
         return True
 
     def promotion(self, weights):
         """Promoted hidden width of this weight list on this plan (None: runs as it is)."""
-        if len(weights) < 4 or (len(weights) - 1) % 3 or not self._blocked():
+        shapes = _shapes(weights)
+        if len(shapes) < 4 or (len(shapes) - 1) % 3 or not self._blocked():
             return None
         # widths above 32 are padded to a multiple of 32 on both plans: the fused plan runs them in 32-channel blocks (_wide_stack), the
         # composed Ebli plan (PowerPlan) keeps its per-shift structure and runs its dense-term kernels as 32 x 32 MFMA blocks
-        return promoted_width([w.shape[1] for w in weights[:-1]], wide=weights[0].shape[0] == 1)
+        return promoted_width([sh[1] for sh in shapes[:-1]], wide=shapes[0][0] == 1)
 
     def forward(self, x, last_dev, weights, activity=None):
         P = self.promotion(weights)
         wp = promote_weights(weights, 3, 1, P) if P else None
         w = wp if P else weights
-        if P and P > 32 and type(self) is SconePlan:
+        if P and P > 32 and self.fused_conv:
             hs, y0 = self._wide_stack(x, w, P)
             # the readout is linear in H: block by block with the block's rows of W_last, the logits added and normalised in one launch
             bhs, parts = [], []
@@ -1073,10 +1126,10 @@ class SconePlan:
             logp = torch.empty_like(parts[0])
             check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), _ptrs(parts),
                                                          _dev(parts[0]), _dev(logp), _stream()), "scn_logits_sum_log_softmax")
-            return logp, (hs, bhs, y0, None, wp, "wide")
+            return logp, SconeState(hs, bhs, y0, None, wp, wide=True)
         hs, y0 = self.conv_stack(x, w, activity)
         logp, bh, _ = self.readout(hs[-1], w[-1], last_dev)
-        return logp, (hs, bh, y0, activity, wp)
+        return logp, SconeState(hs, bh, y0, activity, wp, wide=False)
 
     # -- hidden widths above 32 (TE:103-110 accepts any): every activation is P / 32 separate 32-channel tensors and a layer is
     # its (input block i, output block j) pairs on the fused C = 32 kernels -- act(sum_i sum_s (S_s H_i) W_s[i, j]) (TE:143-149):
@@ -1113,7 +1166,7 @@ class SconePlan:
         return hs, y0
 
     def _wide_backward(self, saved, logp, d_logp, last_dev, w, grads):
-        hs, bhs, y0, _, _, _ = saved
+        hs, bhs, y0 = saved.hs, saved.bh, saved.y0
         k, L = len(hs[-1]), len(hs) - 1
         # the readout's gradient block by block (d_logits depends on the summed logits only), each into its own pooled all-zero buffer
         tops = [self._readout_grad(hs[-1][j], bhs[j], logp, d_logp, last_dev, [w[-1][32 * j:32 * j + 32]], [grads[-1][32 * j:32 * j + 32]])
@@ -1160,10 +1213,7 @@ class SconePlan:
         dz_top = pool.pop() if pool else (torch.empty_like(H) if small else torch.zeros_like(H))
         d_logits = torch.empty_like(logp)
         d_logp = d_logp.contiguous()
-        check(lib.scn_readout_backward(S, ns, E, C, _dev(H), _dev(weights[-1]), _dev(self.nbr, torch.int32),
-                                       self.n_nodes, self.max_deg, _dev(last_dev, torch.int32),
-                                       _dev(self.inc_ptr, torch.int32), _dev(self.inc_edge, torch.int32),
-                                       _dev(self.inc_sign), _dev(self.edge_nodes, torch.int32), _dev(bh),
+        check(lib.scn_readout_backward(S, ns, E, C, _dev(H), _dev(weights[-1]), *self._readout_args(last_dev, edge_nodes=True), _dev(bh),
                                        _dev(d_logp), _dev(logp), ACT[self.act], _dev(d_logits), _dev(dz_top), 2 if small else 1,
                                        _dev(grads[-1]), _stream()), "scn_readout_backward")
         return dz_top, key
@@ -1175,25 +1225,14 @@ class SconePlan:
         if dz_top.numel() * 4 <= self.SMALL_DZ_BYTES:
             self._dz_zero.setdefault(key, []).append(dz_top)     # (may hold anything: see _readout_grad)
             return
-        check(_lib.load().scn_readout_clear_dz(S, ns, E, C, _dev(self.nbr, torch.int32), self.n_nodes, self.max_deg,
-                                               _dev(last_dev, torch.int32), _dev(self.inc_ptr, torch.int32),
-                                               _dev(self.inc_edge, torch.int32), _dev(self.edge_nodes, torch.int32),
+        check(_lib.load().scn_readout_clear_dz(S, ns, E, C, *self._readout_args(last_dev, sign=False, edge_nodes=True),
                                                _dev(dz_top), _stream()), "scn_readout_clear_dz")
         self._dz_zero.setdefault(key, []).append(dz_top)
 
-    def backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        """grads: list of tensors (same shapes as weights) accumulated into."""
-        wp = saved[4]
-        run = self._wide_backward if len(saved) == 6 else self._backward
-        if wp is not None:                              # promoted widths: gradients of the padded matrices, cut back afterwards
-            gp = [torch.zeros_like(w) if w is not w0 else g for w, w0, g in zip(wp, weights, grads)]
-            run(saved, logp, d_logp, last_dev, wp, gp)
-            demote_grads(grads, gp)
-            return grads
-        return run(saved, logp, d_logp, last_dev, weights, grads)
-
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        hs, bh, y0, activity, _ = saved
+        if saved.wide:
+            return self._wide_backward(saved, logp, d_logp, last_dev, weights, grads)
+        hs, bh, y0, activity = saved.hs, saved.bh, saved.y0, saved.activity
         dz_top, key = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
         S, E, ns, C = hs[-1].shape
         L = len(hs) - 1
@@ -1226,9 +1265,7 @@ class SconePlan:
             elif activity:
                 self._give_back(dz_in, wl_in)
         if activity:                                    # the forward's buffers go back to the pool, all-zero again
-            for l in range(1, L + 1):
-                self._give_back(hs[l], activity["fwd"][l - 1])
-            self._give_back(y0, activity["fwd"][0])
+            self._give_back_forward(saved)
         return grads
 
 
@@ -1237,6 +1274,7 @@ class PowerPlan(SconePlan):
     where the rows of the square no longer fit the LDS-blocked plan (> 128 distinct sources).  The square is never formed:
     per layer  G1 = S H,  G2 = S G1  on the LDS-blocked SpMM, then  act(H W0 + G1 W1 + G2 W2)  and its backward on the dense
     term kernels (scn_dense_terms_*) -- the same composition the Bunch plan uses."""
+    fused_conv = False            # self.op is S alone (self.conv is None)
 
     def _init_operators(self, S_lower, S_upper):
         E = self.n_edges
@@ -1273,7 +1311,7 @@ class PowerPlan(SconePlan):
         return hs, y0
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        hs, bh, y0, _, _ = saved
+        hs, bh, y0 = saved.hs, saved.bh, saved.y0
         dz_top, key = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
         L = len(hs) - 1
         dz = dz_top
@@ -1296,23 +1334,6 @@ class PowerPlan(SconePlan):
         return grads
 
 
-class _SconeFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, plan, x, last_dev, *weights):
-        logp, saved = plan.forward(x, last_dev, weights)
-        ctx.plan, ctx.saved, ctx.last_dev = plan, saved, last_dev
-        ctx.save_for_backward(logp, *weights)
-        return logp
-
-    @staticmethod
-    def backward(ctx, d_logp):
-        logp, *weights = ctx.saved_tensors
-        grads = [torch.zeros_like(w) for w in weights]
-        ctx.plan.backward(ctx.saved, logp, d_logp, ctx.last_dev, weights, grads)
-        ctx.saved = None
-        return (None, None, None, *grads)
-
-
 # ----------------------------------------------------------------------------------------------
 # bunch
 # ----------------------------------------------------------------------------------------------
@@ -1321,11 +1342,12 @@ BUNCH_SRC = [0, 1, 0, 1, 2, 1, 2]      # input level of weight slot k   (TE:184-
 BUNCH_DST = [0, 0, 1, 1, 1, 2, 2]      # output level of weight slot k
 
 
-class BunchPlan:
+class BunchPlan(Plan):
     """Device state of the Bunch (SCCONV) model.  Each of the seven shifts S_k (and its transpose for the backward) is a
     single-operator ConvOp served by the LDS-blocked SpMM; the per-level sum over shifts, the weights and the relu are
     one dense kernel (scn_dense_terms_*).  Shapes the blocked SpMM does not take (ns*C > 128) fall back to the generic
     multi-group kernels (one operator per output / input level)."""
+    weights_per_layer = 7
 
     def __init__(self, shifts, nbrhoods, device):
         assert len(shifts) == 7 and all(isinstance(s, Shift) for s in shifts)
@@ -1333,6 +1355,7 @@ class BunchPlan:
         self.device = device
         self.sizes = self.layout.sizes
         self.n_edges = int(self.sizes[1])
+        self.n_rows = sum(self.sizes)
         dev = [s.device_csr() for s in shifts]
         hints = self.layout.block_starts
         # a level without simplices (a complex without faces: B2 has no columns, BMM:71-135 still yields the seven shapes) carries
@@ -1350,6 +1373,7 @@ class BunchPlan:
         self._generic = None
         self._terms = None                              # fused-layer operators (forward, transposed), built on first use
         self._terms_nf = None                           # forward operator of a layer whose face output nothing reads
+        self._terms_bwd_nf = None                       # transposed operator of a layer whose faces carry no gradient
         nb = np.asarray(nbrhoods)
         pn = self.layout.perm[0]
         # padding index -1 wraps to the LAST node of the caller's numbering (TE:201); resolve it here, in device order
@@ -1375,19 +1399,24 @@ class BunchPlan:
         if self._terms is None and not all(self._live):
             self._terms = False                          # an empty level: the per-shift path (nothing to fuse across three levels)
         if self._terms is None:
-            dev = self._dev_csr
-            try:
-                # bins: rows of (nodes, edges, faces) a block holds = the natural 0.37 : 1 : 0.67 proportions in wave units
-                fwd = TermsOp(self.sizes, {(BUNCH_DST[k], BUNCH_SRC[k]): dev[k] for k in range(7)}, self.layout.merged,
-                              (12, 32, 20), 4)
-                bwd = TermsOp(self.sizes, {(BUNCH_SRC[k], BUNCH_DST[k]): dev[k].T.tocsr() for k in range(7)}, self.layout.merged,
-                              (16, 32, 16), 8)
-                self._terms = (fwd, bwd)
-            except _lib.SconeHipError as e:
-                if e.status != _lib.SCN_ERR_UNSUPPORTED:
-                    raise
-                self._terms = False
+            # bins: rows of (nodes, edges, faces) a block holds = the natural 0.37 : 1 : 0.67 proportions in wave units
+            fwd = self._optional_terms(False, range(7), (12, 32, 20), 4)
+            bwd = fwd and self._optional_terms(True, range(7), (16, 32, 16), 8)
+            self._terms = (fwd, bwd) if bwd else False
         return self._terms or None
+
+    def _optional_terms(self, transposed, slots, bins, rows_per_wave):
+        """TermsOp of these shifts (transposed: of their transposes), or False when the plan builder cannot hold it
+        (SCN_ERR_UNSUPPORTED): the caller then does without."""
+        dev = self._dev_csr
+        blocks = {(BUNCH_SRC[k], BUNCH_DST[k]): dev[k].T.tocsr() for k in slots} if transposed else \
+                 {(BUNCH_DST[k], BUNCH_SRC[k]): dev[k] for k in slots}
+        try:
+            return TermsOp(self.sizes, blocks, self.layout.merged, bins, rows_per_wave)
+        except _lib.SconeHipError as e:
+            if e.status != _lib.SCN_ERR_UNSUPPORTED:
+                raise
+            return False
 
     def _terms_fwd_for(self, want):
         """Forward fused-layer operator for the wanted output levels: when the faces are not wanted (the layer before the last
@@ -1397,14 +1426,7 @@ class BunchPlan:
         if want[2] or not (want[0] and want[1]):
             return fwd
         if self._terms_nf is None:
-            dev = self._dev_csr
-            blocks = {(BUNCH_DST[k], BUNCH_SRC[k]): dev[k] for k in range(7) if BUNCH_DST[k] != 2}
-            try:
-                self._terms_nf = TermsOp(self.sizes, blocks, self.layout.merged, (16, 48, 0), 4)
-            except _lib.SconeHipError as e:
-                if e.status != _lib.SCN_ERR_UNSUPPORTED:
-                    raise
-                self._terms_nf = False
+            self._terms_nf = self._optional_terms(False, [k for k in range(7) if BUNCH_DST[k] != 2], (16, 48, 0), 4)
         return self._terms_nf or fwd
 
     def _terms_bwd_for(self, dz_present):
@@ -1414,15 +1436,8 @@ class BunchPlan:
         bwd = self._terms_ops()[1]
         if dz_present[2] or not (dz_present[0] and dz_present[1]):
             return bwd
-        if getattr(self, "_terms_bwd_nf", None) is None:
-            dev = self._dev_csr
-            blocks = {(BUNCH_SRC[k], BUNCH_DST[k]): dev[k].T.tocsr() for k in range(7) if BUNCH_DST[k] != 2}
-            try:
-                self._terms_bwd_nf = TermsOp(self.sizes, blocks, self.layout.merged, (16, 32, 16), 8)
-            except _lib.SconeHipError as e:
-                if e.status != _lib.SCN_ERR_UNSUPPORTED:
-                    raise
-                self._terms_bwd_nf = False
+        if self._terms_bwd_nf is None:
+            self._terms_bwd_nf = self._optional_terms(True, [k for k in range(7) if BUNCH_DST[k] != 2], (16, 32, 16), 8)
         return self._terms_bwd_nf or bwd
 
     def _fused_ok(self, ns, widths_out, widths_in):
@@ -1440,6 +1455,7 @@ class BunchPlan:
         return spmm_chunked(op, x)
 
     def conv_stack(self, x, weights):
+        """(states, zeros, first_g, fold): the fields of BunchState that the layers fill."""
         n_layers = len(weights) / 7
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:177-178
         S, E, ns, _ = x.shape
@@ -1456,13 +1472,12 @@ class BunchPlan:
                 if self._live[k] and need[i + 1][BUNCH_DST[k]]:
                     need[i][BUNCH_SRC[k]] = True
         states, zeros = [cur], [zero]
-        first_g = {}
-        self._fold = None
+        first_g, fold = {}, None
         if self._fold_ok(x, weights, L, ns):
-            cur, zero = self._fold_forward(x, weights, need[2])
+            cur, zero, fold = self._fold_forward(x, weights, need[2])
             states += [[None] * 3, cur]                     # the first layer's output is never materialised
             zeros += [[False] * 3, zero]
-        for i in range(2 if self._fold is not None else 0, L):
+        for i in range(2 if fold is not None else 0, L):
             nxt, nzero = [], []
             c_outs = {weights[7 * i + k].shape[1] for k in range(7)}
             c_ins = {cur[l].shape[3] for l in range(3) if not zero[l] and cur[l] is not None}
@@ -1514,9 +1529,7 @@ class BunchPlan:
             cur, zero = nxt, nzero
             states.append(cur)
             zeros.append(zero)
-        self._zeros = zeros
-        self._first_g = first_g
-        return states
+        return states, zeros, first_g, fold
 
     # -- the first TWO layers without a 32-channel gather --------------------------------------------------------------
     # bunch_func starts from [0, flow, 0] (TE:179): after the first layer every level is relu of ONE rank-one term,
@@ -1565,8 +1578,7 @@ class BunchPlan:
                 Gs += [sp, sm]
                 Ws += [ap, am]
             outs.append(dense_terms_forward(Gs, Ws, c2, "relu"))
-        self._fold = terms
-        return outs, [o is None for o in outs]
+        return outs, [o is None for o in outs], terms
 
     def _fold_backward(self, fold, dz, dzero, weights, grads):
         """Weight gradients of the first two layers from dz = the gradient of the second layer's pre-activation per level."""
@@ -1587,15 +1599,16 @@ class BunchPlan:
                                              _dev(grads[7 + k2]), _dev(grads[k1]), _stream()), "scn_fold1_backward")
 
     def promotion(self, weights):
-        if len(weights) < 14 or len(weights) % 7:
+        shapes = _shapes(weights)
+        if len(shapes) < 14 or len(shapes) % 7:
             return None
-        return promoted_width([w.shape[1] for w in weights[:-7]], wide=True)   # above 32: multiples of 32 (32 x 32 MFMA blocks of the dense terms)
+        return promoted_width([sh[1] for sh in shapes[:-7]], wide=True)   # above 32: multiples of 32 (32 x 32 MFMA blocks of the dense terms)
 
     def forward(self, x, last_dev, weights):
         lib = _lib.load()
         P = self.promotion(weights)
         wp = promote_weights(weights, 7, 7, P) if P else None
-        states = self.conv_stack(x, wp if P else weights)
+        states, zeros, first_g, fold = self.conv_stack(x, wp if P else weights)
         nodes_out = states[-1][0]
         S, V, ns, C = nodes_out.shape
         assert C == 1, "bunch readout needs one output channel (TE:198-201)"
@@ -1604,20 +1617,11 @@ class BunchPlan:
         check(lib.scn_node_readout_forward(S, ns, V, _dev(nodes_out), _dev(self.nbr, torch.int32), self.max_deg,
                                            _dev(last_dev, torch.int32), _dev(logits), _dev(logp), _stream()),
               "scn_node_readout_forward")
-        return logp, (states, self._zeros, self._first_g, wp, self._fold)
-
-    def backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        wp = saved[3]
-        if wp is not None:                              # promoted widths (see promote_weights)
-            gp = [torch.zeros_like(w) if w is not w0 else g for w, w0, g in zip(wp, weights, grads)]
-            self._backward(saved, logp, d_logp, last_dev, wp, gp)
-            demote_grads(grads, gp)
-            return grads
-        return self._backward(saved, logp, d_logp, last_dev, weights, grads)
+        return logp, BunchState(states, zeros, first_g, fold, wp)
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         lib = _lib.load()
-        states, zeros, first_g, _, fold = saved
+        states, zeros, first_g, fold = saved.states, saved.zeros, saved.first_g, saved.fold
         nodes_out = states[-1][0]
         S, V, ns, _ = nodes_out.shape
         dz = [torch.empty_like(nodes_out), None, None]
@@ -1697,11 +1701,12 @@ class BunchPlan:
         return grads
 
 
-class _BunchFn(torch.autograd.Function):
+class PlanFn(torch.autograd.Function):
+    """plan.forward / plan.backward of either family under autograd (the model functions of trajectory_experiments)."""
     @staticmethod
     def forward(ctx, plan, x, last_dev, *weights):
-        logp, states = plan.forward(x, last_dev, weights)
-        ctx.plan, ctx.states, ctx.last_dev = plan, states, last_dev
+        logp, saved = plan.forward(x, last_dev, weights)
+        ctx.plan, ctx.saved, ctx.last_dev = plan, saved, last_dev
         ctx.save_for_backward(logp, *weights)
         return logp
 
@@ -1709,8 +1714,8 @@ class _BunchFn(torch.autograd.Function):
     def backward(ctx, d_logp):
         logp, *weights = ctx.saved_tensors
         grads = [torch.zeros_like(w) for w in weights]
-        ctx.plan.backward(ctx.states, logp, d_logp, ctx.last_dev, weights, grads)
-        ctx.states = None
+        ctx.plan.backward(ctx.saved, logp, d_logp, ctx.last_dev, weights, grads)
+        ctx.saved = None
         return (None, None, None, *grads)
 
 
@@ -1858,14 +1863,9 @@ def step_tables(plan, nbrhoods, E_lookup, rule):
 
 
 def forward_micro_batch(plan, weights, n):
-    """Trajectories per forward launch of a multi-hop level (multiple of NS): the training micro-batch rule (micro_batch_size)."""
-    k = 7 if type(plan) is BunchPlan else 3
-    widths = [1] + [int(weights[k * i].shape[1]) for i in range(len(weights) // k)]
-    P = plan.promotion(weights)
-    if P:
-        widths = [w if w == 1 else P for w in widths]
-    rows = sum(plan.sizes) if type(plan) is BunchPlan else plan.n_edges
-    return micro_batch_size(rows, widths, n, device=plan.device)
+    """Trajectories per forward of the model functions and of a multi-hop level (multiple of NS): the training micro-batch rule
+    (micro_batch_size) on the widths the plan runs."""
+    return micro_batch_size(plan.n_rows, plan.layer_widths(weights), n, device=plan.device)
 
 
 def forward_logp(plan, x, last_dev, weights):

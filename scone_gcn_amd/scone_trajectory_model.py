@@ -152,6 +152,7 @@ class Scone_GCN():
         self.use_eval_cache = True
         self._eval = None
         self._wver = 0                                 # bumped by the raw-pointer Adam launch (torch's own version counter sees the rest)
+        self._lookup_cache = None                      # _edge_lookup of the last readout operand
 
     # ------------------------------------------------------------------ weights
     def generate_weights(self, in_channels, hidden_layers, out_channels):
@@ -192,7 +193,7 @@ class Scone_GCN():
 
     def _drop_graphs(self, keep=0):
         """Forget captured steps (oldest first) down to `keep`; a graph may still be replaying, so the device is drained first."""
-        if len(getattr(self, "_graphs", {})) > keep:
+        if len(self._graphs) > keep:
             torch.cuda.synchronize()
             while len(self._graphs) > keep:
                 self._graphs.pop(next(iter(self._graphs)))
@@ -281,8 +282,7 @@ class Scone_GCN():
         if not self.use_eval_cache or plan is None or self.skip_mode != "dense" or ops.KernelTimer._stack:
             return False
         widest = max(max(sh) for sh in self._shapes)
-        rows = sum(plan.sizes) if type(plan) is ops.BunchPlan else plan.n_edges
-        return rows * ops.pad_count(_n_samples(inputs[-1])) * (plan.promotion(self.weights) or widest) <= self.EVAL_CACHE_ELEMS
+        return plan.n_rows * ops.pad_count(_n_samples(inputs[-1])) * (plan.promotion(self.weights) or widest) <= self.EVAL_CACHE_ELEMS
 
     def _predict(self, weights, inputs, idx=None):
         """log-probabilities (n, D, 1) for trajectories idx (all when None), no autograd."""
@@ -354,6 +354,7 @@ class Scone_GCN():
     # reduce the leaf probabilities -- are csrc/scn_hops.hip.  The caller's flows are never written (the reference writes into them,
     # STM:149-150) and the evaluation cache is not touched.
     multi_hop_micro_batch = None
+    _multi_hop_trace = None            # a list set on the instance collects what every hop / beam level saw (the tests' window)
 
     def _multihop_plan(self, inputs):
         if self.model_type != 'bunch' and not isinstance(inputs[0], Bconds):
@@ -428,7 +429,7 @@ class Scone_GCN():
         plan = self._multihop_plan(inputs)
         tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
         choice, _ = self._rollout(inputs, np.asarray(last_nodes), np.asarray(n_nbrs), int(hops), tab, advance=False, fill=-100.0,
-                                  trace=getattr(self, "_multi_hop_trace", None))
+                                  trace=self._multi_hop_trace)
         m = np.asarray(mask) == 1
         target = np.argmax(np.asarray(y)[m], axis=1).reshape(-1)
         return float(np.average(choice[m] == target))
@@ -447,7 +448,7 @@ class Scone_GCN():
         if E_lookup is None:
             E_lookup = self._edge_lookup(inputs)
         tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
-        _, nodes = self._rollout(inputs, None, None, int(hops), tab, advance=True, fill=float("-inf"), trace=getattr(self, "_multi_hop_trace", None))
+        _, nodes = self._rollout(inputs, None, None, int(hops), tab, advance=True, fill=float("-inf"), trace=self._multi_hop_trace)
         return nodes.T.copy()
 
     def predict_paths_beam(self, inputs, hops, beam, nbrhoods=None, E_lookup=None):
@@ -476,7 +477,7 @@ class Scone_GCN():
             raise ValueError("last nodes need one entry per trajectory of inputs (%d)" % N)
         if N * beam * D >= ops.INT32_MAX:
             raise ValueError("beam level of %d x %d entries is too large" % (N, beam))
-        trace = getattr(self, "_multi_hop_trace", None)
+        trace = self._multi_hop_trace
         root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)          # a copy: the caller's flows stay as they are
         i32, f32 = (lambda *s: torch.empty(s, device=dev, dtype=torch.int32)), (lambda *s: torch.empty(s, device=dev, dtype=torch.float32))
         p = lambda t: None if t is None else ops._dev(t, t.dtype)
@@ -534,7 +535,7 @@ class Scone_GCN():
 
     def _edge_lookup(self, inputs):
         src = inputs[0] if self.model_type != 'bunch' else resolve_operands('bunch', self.shifts, inputs[0])[0][1]
-        hit = getattr(self, "_lookup_cache", None)
+        hit = self._lookup_cache
         if hit is not None and hit[0] is src:
             return hit[1]
         if self.model_type != 'bunch':
@@ -620,12 +621,7 @@ class Scone_GCN():
         skip = self.skip_mode if skip is None else skip
         plan = self._plan(inputs)
         device = self._flat_w.device
-        k = 7 if self.model_type == 'bunch' else 3
-        widths = [1] + [self._shapes[k * i][1] for i in range(len(self._shapes) // k)]
-        P = plan.promotion(self.weights)                # hidden widths the kernels do not take are zero-padded (ops.promote_weights)
-        if P:
-            widths = [w if w == 1 else P for w in widths]
-        rows = sum(plan.sizes) if self.model_type == 'bunch' else plan.n_edges
+        widths = plan.layer_widths(self._shapes)        # (hidden widths the kernels do not take count zero-padded, ops.promote_weights)
         budget = None
         if self.model_type == 'bunch' and ops.FOLD_BUNCH and len(widths) > 3 and widths[1] == widths[2] == 32:
             # the first hidden layer is never materialised (rank-one fold, DESIGN.md section 3.1 / profiles/HISTORY.md section 3.1) and levels the loss cannot see are not
@@ -633,7 +629,7 @@ class Scone_GCN():
             # (119 GB at peak) instead of 64, +3.4 % on configs[4] (tools/mb_sweep.py)
             widths = [widths[0]] + widths[2:]
             budget = 0.5 * torch.cuda.mem_get_info(device)[1]
-        mb = ops.micro_batch_size(rows, widths, len(idx), budget_bytes=budget, device=device)
+        mb = ops.micro_batch_size(plan.n_rows, widths, len(idx), budget_bytes=budget, device=device)
         staged = []
         for c0 in range(0, len(idx), mb):
             sel = idx[c0:c0 + mb]
@@ -706,8 +702,7 @@ class Scone_GCN():
         if type(plan) not in (ops.SconePlan, ops.BunchPlan) or getattr(plan, "_probed", False):
             return False
         widest = max(max(sh) for sh in self._shapes)
-        rows = sum(plan.sizes) if type(plan) is ops.BunchPlan else plan.n_edges
-        return rows * ops.pad_count(n_traj) * (plan.promotion(self.weights) or widest) <= self.GRAPH_MAX_ELEMS
+        return plan.n_rows * ops.pad_count(n_traj) * (plan.promotion(self.weights) or widest) <= self.GRAPH_MAX_ELEMS
 
     def _adam_in_graph(self, apply):
         """The optimiser step rides inside the captured graph when nothing has to happen between the gradient and the update (one

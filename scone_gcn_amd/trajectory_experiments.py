@@ -69,18 +69,17 @@ def _prep_batch(last_node, flow):
     return ln, f, single
 
 
-def _run_batched(fn_cls, plan, weights, last_nodes, flow, widths, rows_total):
+def _run_batched(plan, weights, last_nodes, flow):
     device = plan.device
     w = ops.as_device_weights(weights, device)
     x, N = ops.flows_to_slabs(flow, plan.layout, device)
     if len(last_nodes) != N:
         raise ValueError("last_node and flow disagree on the number of trajectories")
     last_dev = ops._last_nodes_dev(last_nodes, x.shape[0] * ops.NS, device)
-    mb = ops.micro_batch_size(rows_total, widths, N, device=device)
-    sl = mb // ops.NS
+    sl = ops.forward_micro_batch(plan, w, N) // ops.NS
     outs = []
     for s0 in range(0, x.shape[0], sl):
-        outs.append(fn_cls.apply(plan, x[s0:s0 + sl], last_dev[s0 * ops.NS:(s0 + sl) * ops.NS], *w))
+        outs.append(ops.PlanFn.apply(plan, x[s0:s0 + sl], last_dev[s0 * ops.NS:(s0 + sl) * ops.NS], *w))
     logp = torch.cat(outs) if len(outs) > 1 else outs[0]
     return logp[:N].unsqueeze(-1)
 
@@ -113,8 +112,7 @@ def _scone_like(weights, S_lower, S_upper, Bcond_func, last_node, flow, act):
     plan = ops.get_scone_plan(S_lower, S_upper, bconds, act, ops.default_device())
     ln, f, single = _prep_batch(last_node, flow)
     ln = ops.remap_last_nodes(plan, ln)
-    widths = [1] + [int(weights[3 * i].shape[1]) for i in range(int(n_layers))]
-    out = _run_batched(ops._SconeFn, plan, weights, ln, f, widths, plan.n_edges)
+    out = _run_batched(plan, weights, ln, f)
     return out[0] if single else out
 
 
@@ -135,8 +133,7 @@ def bunch_func(weights, S_00, S_10, S_01, S_11, S_21, S_12, S_22, nbrhoods, last
     shifts, nbrhoods = resolve_operands('bunch', [S_00, S_10, S_01, S_11, S_21, S_12, S_22], nbrhoods)
     plan = ops.get_bunch_plan(shifts, nbrhoods, ops.default_device())
     ln, f, single = _prep_batch(last_node, flow)
-    widths = [1] + [int(weights[7 * i].shape[1]) for i in range(int(n_layers))]
-    out = _run_batched(ops._BunchFn, plan, weights, ln, f, widths, sum(plan.sizes))
+    out = _run_batched(plan, weights, ln, f)
     return out[0] if single else out
 
 
