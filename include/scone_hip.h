@@ -528,6 +528,37 @@ int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32
                   int32_t* c_node, float* c_score, int32_t* c_parent, int32_t* c_slot, int32_t* c_path_row, float* c_path_sign,
                   int32_t* err, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Field-of-view work lists of a multi-hop level, built on the device.  The readout of a leaf reads the last layer only on the
+ * edges around the leaf's node, and every layer below needs one more hop of the operator's pattern: with the two block-level CSR
+ * tables (host-built once per plan, then device arrays; block indices ascending in every row)
+ *   top: node  -> T(v), the plan blocks holding a row the readout of node v reads,
+ *   adj: block -> A(b), the plan blocks holding a source row some row of block b stages, b itself included,
+ * the lists of the leaves of slab s are  list_L(s) = union of T(node of leaf),  list_l(s) = A(list_{l+1}(s)),  l = L - 1 .. 0.
+ * list_l, l >= 1, is the forward work list of layer l and list_0 the blocks of the input that layer 1 stages.  A listed item of
+ * layer l + 1 stages rows of listed items of layer l only, so the listed items hold the dense values and nothing else is read.
+ *
+ * scn_field_lists: leaf i < n belongs to slab i / ns and stands on node[i]; a node < 0 (dead beam entry, padding) contributes
+ *   nothing, a node >= n_nodes is a caller's error that is only guarded against (nothing is read through it).  Per level
+ *   l < n_levels (n_levels = L + 1: level n_levels - 1 is the top, level 0 the input) the output is a scn_work_list in CANONICAL
+ *   order -- listed blocks ascending, blocks without a slab left out, each block's slabs ascending -- in block[l][n_blocks],
+ *   ptr[l][n_blocks + 1], slab[l][cap], and counts[l] = (n_work, items).  counts stays on the device (the caller copies it back
+ *   once per call).  A level whose items exceed cap gets its counts and nothing else; an empty level likewise.  Integer work only,
+ *   no atomics, all launches on `stream`, no allocation and no synchronisation; the same inputs give the same bytes.
+ *   SCN_ERR_UNSUPPORTED (workspace query: 0) when n_blocks * n_slabs * n_levels reaches 2^27 - 1, n_slabs = ceil(n / ns) (at least 1).
+ * scn_tree_slabs_list: scn_tree_slabs restricted to the items of `wl` (a level-0 list in canonical order, blocks of `conv`'s plan):
+ *   for every listed (block, slab) all rows of the block get the slab's 4 columns -- the root's column of root_x, then those of the
+ *   leaf's path entries whose (block of the row, slab) is listed, in level order (the last write wins).  Nothing else of x is
+ *   written: x may be an UNINITIALISED scratch buffer, because the first layer run with the level-1 list of the same call stages
+ *   rows of level-0 items only.  n_rows must be conv's row count, ns 4. */
+size_t scn_field_lists_workspace(int32_t n_blocks, int32_t n_slabs, int32_t n_levels);
+int scn_field_lists(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
+                    int32_t n_blocks, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t n_levels, int32_t* block, int32_t* ptr,
+                    int32_t* slab, int64_t cap, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int scn_tree_slabs_list(scn_conv_t conv, int32_t n_leaves, int32_t n_slabs, int32_t h, const int32_t* root, const int32_t* path_row,
+                        const float* path_sign, int32_t n_roots, const float* root_x, int32_t n_rows, int32_t ns, float* x,
+                        const scn_work_list* wl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

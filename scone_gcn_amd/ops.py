@@ -185,6 +185,62 @@ class WorkList:
         return ctypes.byref(self.desc)
 
 
+class DeviceWorkList:
+    """A work list scn_field_lists left on the device: the same ref() / n_work / items as WorkList, over slices of the arrays that
+    call filled (block, ptr, slab of one level); n_work and items come from the call's one copy back of its counts."""
+
+    def __init__(self, block, ptr, slab, n_work, items):
+        self.block, self.ptr, self.slab = block, ptr, slab
+        self.n_work, self.items = int(n_work), int(items)
+        self.desc = WorkListDesc(self.n_work, block.data_ptr(), ptr.data_ptr(), slab.data_ptr())
+
+    def ref(self):
+        return ctypes.byref(self.desc)
+
+
+def field_tables(row0, pattern_csr, nbr, inc_ptr, inc_edge):
+    """The two block-level CSR tables of the field-of-view lists (scn_field_lists), int32, block indices ascending in every row:
+    ((top_ptr, top_blk), (adj_ptr, adj_blk)).
+      top: node v -> T(v), the blocks holding a row the readout of v reads = the edges incident to a neighbour of v
+           (nbr (V, D) padded with -1; inc_ptr / inc_edge: node -> rows of its incident edges);
+      adj: block b -> A(b), the blocks holding a column some row of b has a pattern entry in, b itself included.
+    row0: first row of every block and the row count (n_blocks + 1 entries); pattern_csr: the operator's STORED pattern, a scipy
+    CSR matrix (explicit zeros count) or (rowptr, cols) -- rows read columns, so a non-symmetric pattern gives a non-symmetric A."""
+    import scipy.sparse as sp
+    row0 = np.asarray(row0, np.int64)
+    nb, E = len(row0) - 1, int(row0[-1])
+    blk_of = np.searchsorted(row0, np.arange(E), side="right") - 1
+    rowptr, cols = (pattern_csr.indptr, pattern_csr.indices) if hasattr(pattern_csr, "indptr") else pattern_csr
+    rowptr, cols = np.asarray(rowptr, np.int64), np.asarray(cols, np.int64)
+    assert len(rowptr) == E + 1, "the pattern's rows are the blocks' rows"
+    rows = np.repeat(np.arange(E), np.diff(rowptr))
+    A = sp.csr_matrix((np.ones(len(rows) + nb, np.int32), (np.concatenate([blk_of[rows], np.arange(nb)]),
+                                                         np.concatenate([blk_of[cols], np.arange(nb)]))), shape=(nb, nb))
+    nbr, inc_ptr, inc_edge = np.asarray(nbr, np.int64), np.asarray(inc_ptr, np.int64), np.asarray(inc_edge, np.int64)
+    V = nbr.shape[0]
+    v, j = np.nonzero(nbr >= 0)
+    u = nbr[v, j]
+    deg = inc_ptr[u + 1] - inc_ptr[u]
+    start = np.cumsum(deg) - deg
+    pos = np.arange(int(deg.sum())) - np.repeat(start, deg) + np.repeat(inc_ptr[u], deg)     # the incidence ranges of every (v, u), in a row
+    T = sp.csr_matrix((np.ones(len(pos), np.int32), (np.repeat(v, deg), blk_of[inc_edge[pos]])), shape=(V, nb))
+    out = []
+    for M in (T, A):
+        M.sum_duplicates()
+        M.sort_indices()
+        out.append((np.ascontiguousarray(M.indptr, np.int32), np.ascontiguousarray(M.indices, np.int32)))
+    return tuple(out)
+
+
+class FieldTables(NamedTuple):
+    """Device copies of field_tables for one plan."""
+    n_blocks: int
+    top_ptr: object
+    top_blk: object
+    adj_ptr: object
+    adj_blk: object
+
+
 class ConvOp:
     """One shift-convolution operator (scn_conv_t).  groups: list of dicts
     {"mats": [scipy csr in DEVICE order] (0..2, same shape), "identity": bool, "n_cols": int}."""
@@ -845,6 +901,7 @@ class SconePlan(Plan):
         self._zero_pool = {}                            # zero-skipping mode: all-zero activation / gradient buffers
         self._blocks = None                             # (block of row, block adjacency), built on first use
         self._act_cache = None                          # _trajectory_supports of the last data set
+        self._field = None                              # device copies of field_tables, built on first use (field_tables_dev)
         self._upload_readout()
 
     def _upload_readout(self):
@@ -863,6 +920,7 @@ class SconePlan(Plan):
         inc_deg = np.diff(np.asarray(ptr)).astype(np.int64)             # readout items of a last node: incident edges of its neighbours
         self.max_items = int(np.where(nbr >= 0, inc_deg[np.maximum(nbr, 0)], 0).sum(axis=1).max()) if inc_deg.size else 0
         self._ro_rows = None
+        self._field = None                              # (its node -> blocks table follows the readout tables)
         self._readout_version = getattr(bconds, "version", 0)
         self._probed = hasattr(bconds, "prepare")
 
@@ -875,6 +933,7 @@ class SconePlan(Plan):
         lo, up = S_lower.device_csr(), S_upper.device_csr()
         hint = self.layout.block_starts[S_lower.row_level]
         self._pattern = (abs(lo) + abs(up)).tocsr()
+        self._shift_pair = (S_lower, S_upper)
         self.conv = ConvOp(E, [{"mats": [lo, up], "identity": True, "n_cols": E}], hint)
         if S_lower.is_symmetric() and S_upper.is_symmetric():
             self.conv_T = self.conv
@@ -1024,6 +1083,20 @@ class SconePlan(Plan):
         total = S * c["nb"]
         return {"fwd": fwd, "bwd": bwd, "mode": mode,
                 "active_fraction": {"fwd": [w.items / total for w in fwd], "bwd": [w.items / total for w in bwd[1:]]}}
+
+    def field_tables_dev(self):
+        """FieldTables of this plan (built and uploaded once; dropped with the readout tables), or None where activity() serves
+        nothing either: no blocked plan, a probed Bcond_func closure.  The pattern is the one `conv` stores (union_pattern of the two
+        shifts, explicit zeros included): what a block's rows stage, and for non-symmetric shifts nothing more."""
+        if self.conv is None or not self.conv.plan_info()[0] or self._probed:
+            return None
+        if self._field is None:
+            rowptr, cols, _ = union_pattern([s.device_csr() for s in self._shift_pair])
+            (tp, tb), (ap, ab) = field_tables(self.conv.plan_blocks(), (rowptr, cols), self._h_nbr, self._h_inc_ptr, self._h_inc_edge)
+            # (an empty table still needs a valid pointer: one unused element)
+            to = lambda a: torch.from_numpy(np.ascontiguousarray(np.append(a, 0), np.int32)).to(self.device)
+            self._field = FieldTables(len(ap) - 1, to(tp), to(tb), to(ap), to(ab))
+        return self._field
 
     def _zeros(self, shape):
         pool = self._zero_pool.setdefault(tuple(shape), [])
@@ -1292,6 +1365,9 @@ class PowerPlan(SconePlan):
         return spmm_chunked(op, x)
 
     def activity(self, *a, **k):
+        return None
+
+    def field_tables_dev(self):
         return None
 
     def conv_stack(self, x, weights, activity=None):
@@ -1868,33 +1944,91 @@ def forward_micro_batch(plan, weights, n):
     return micro_batch_size(plan.n_rows, plan.layer_widths(weights), n, device=plan.device)
 
 
-def forward_logp(plan, x, last_dev, weights):
-    """Dense forward only (no autograd, nothing kept): log-probabilities [S * NS, D] of the slabs x."""
+def field_served(plan, weights):
+    """Hidden width (16 or 32) when the field-of-view lists serve this model on this plan, else None -- the conditions under which
+    SconePlan.activity() serves a data set: a scone / ebli plan with a blocked fused operator (not PowerPlan, not Bunch, no probed
+    closure), one 1-channel input and one hidden width of 16 or 32 throughout."""
+    if not isinstance(plan, SconePlan) or plan.field_tables_dev() is None:
+        return None
+    shapes = _shapes(weights)
+    L = (len(shapes) - 1) // 3
+    if L < 1 or len(shapes) != 3 * L + 1:
+        return None
+    h = shapes[0][1]
+    ok = h in (16, 32) and shapes == [(1, h)] * 3 + [(h, h)] * (3 * (L - 1)) + [(h, 1)]
+    return h if ok else None
+
+
+def field_activity(plan, node_dev, n, n_layers):
+    """Field-of-view work lists of one forward over the n leaves node_dev[:n] (int32 device tensor; slab = leaf // NS; -1 = no leaf:
+    a dead beam entry, padding), built on the device by scn_field_lists: {"fwd": the lists of layers 1 .. L, "input": the blocks
+    of x layer 1 stages, "mode": "field", "active_fraction"}, in the form plan.forward takes as `activity`.  One small copy back (the
+    counts).  None when the plan serves no lists (field_tables_dev) or the library does not take the size: the caller runs dense."""
+    tabs = plan.field_tables_dev() if isinstance(plan, SconePlan) else None
+    if tabs is None or n <= 0:
+        return None
+    lib = _lib.load()
+    nb, S, n_levels = tabs.n_blocks, pad_count(n) // NS, n_layers + 1
+    nbytes = int(lib.scn_field_lists_workspace(nb, S, n_levels))
+    if nbytes == 0:
+        return None
+    dev = plan.device
+    cap = nb * S                                            # every (block, slab): a level always fits
+    i32 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.int32)
+    block, ptr, slab, counts = i32(n_levels, nb), i32(n_levels, nb + 1), i32(n_levels, cap), i32(n_levels, 2)
+    p = lambda t: _dev(t, torch.int32)
+    check(lib.scn_field_lists(n, NS, p(node_dev), plan.n_nodes, p(tabs.top_ptr), p(tabs.top_blk), nb, p(tabs.adj_ptr), p(tabs.adj_blk),
+                              n_levels, p(block), p(ptr), p(slab), cap, p(counts), *_workspace(nbytes, dev), _stream()), "scn_field_lists")
+    cnt = counts.cpu().numpy()
+    lists = [DeviceWorkList(block[l], ptr[l], slab[l], cnt[l, 0], cnt[l, 1]) for l in range(n_levels)]
+    total = float(S * nb)
+    return {"fwd": lists[1:], "input": lists[0], "mode": "field",
+            "active_fraction": {"fwd": [w.items / total for w in lists[1:]], "input": lists[0].items / total}}
+
+
+def forward_logp(plan, x, last_dev, weights, activity=None):
+    """Forward only (no autograd, nothing kept): log-probabilities [S * NS, D] of the slabs x.  activity: work lists
+    (field_activity) -- only the listed items are computed, in pooled all-zero buffers that go back all-zero (plan.release)."""
     with torch.no_grad():
+        if activity:
+            logp, saved = plan.forward(x, last_dev, weights, activity)
+            plan.release(saved)
+            return logp
         logp, saved = plan.forward(x, last_dev, weights)
         del saved
     return logp
 
 
-def tree_level_logp(plan, weights, root_x, n_roots, root, node, path_row, path_sign, mb):
+def tree_level_logp(plan, weights, root_x, n_roots, root, node, path_row, path_sign, mb, field_node=None, fractions=None):
     """Log-probabilities [L, D] of the L leaves of one tree level: per chunk of mb leaves, scn_tree_slabs builds the input slabs
     from the resident root slabs and the leaves' path entries, and the dense forward reads them with the leaves' nodes as last
-    nodes."""
+    nodes.  field_node (the leaves' nodes, -1 for a dead entry): per chunk the field-of-view lists of its leaves (field_activity);
+    scn_tree_slabs_list then fills only the listed items of the scratch input and the forward computes only its listed items.
+    fractions: a list that collects every chunk's active fractions."""
     lib = _lib.load()
     L, h = int(root.shape[0]), int(path_row.shape[1])
     E = root_x.shape[1]
     mb = min(mb, pad_count(L))
+    n_layers = (len(weights) - 1) // 3
     x = torch.empty((mb // NS, E, NS, 1), device=root_x.device, dtype=torch.float32)
     last = torch.zeros((mb,), device=root_x.device, dtype=torch.int32)
     out = torch.empty((L, plan.max_deg), device=root_x.device, dtype=torch.float32)
     for c0 in range(0, L, mb):
         n = min(mb, L - c0)
         S = pad_count(n) // NS
-        check(lib.scn_tree_slabs(n, S, h, _dev(root[c0:c0 + n], torch.int32), _dev(path_row[c0:c0 + n], torch.int32) if h else None,
-                                 _dev(path_sign[c0:c0 + n]) if h else None, n_roots, _dev(root_x), E, NS, _dev(x), _stream()),
-              "scn_tree_slabs")
+        activity = field_activity(plan, field_node[c0:c0 + n], n, n_layers) if field_node is not None else None
+        rows = _dev(path_row[c0:c0 + n], torch.int32) if h else None
+        signs = _dev(path_sign[c0:c0 + n]) if h else None
+        if activity:
+            if fractions is not None:
+                fractions.append(activity["active_fraction"])
+            check(lib.scn_tree_slabs_list(plan.conv.handle, n, S, h, _dev(root[c0:c0 + n], torch.int32), rows, signs, n_roots, _dev(root_x),
+                                          E, NS, _dev(x), activity["input"].ref(), _stream()), "scn_tree_slabs_list")
+        else:
+            check(lib.scn_tree_slabs(n, S, h, _dev(root[c0:c0 + n], torch.int32), rows, signs, n_roots, _dev(root_x), E, NS, _dev(x),
+                                     _stream()), "scn_tree_slabs")
         if n < S * NS:
             last[n:S * NS].zero_()
         last[:n].copy_(node[c0:c0 + n])
-        out[c0:c0 + n] = forward_logp(plan, x[:S], last[:S * NS], weights)[:n]
+        out[c0:c0 + n] = forward_logp(plan, x[:S], last[:S * NS], weights, activity)[:n]
     return out

@@ -121,11 +121,18 @@ class _StaticStage:
 
 
 class Scone_GCN():
-    def __init__(self, epochs, step_size, batch_size, weight_decay, verbose=True, process_group=None, skip_mode="dense"):
+    def __init__(self, epochs, step_size, batch_size, weight_decay, verbose=True, process_group=None, skip_mode="dense",
+                 multi_hop_skip="dense"):
         # skip_mode: "dense" (every block of every slab, the reference's formulation), "zeros" (skip work items whose
         # values are exactly zero) or "field" (also skip what the loss cannot see); same results, see SconePlan.activity
         assert skip_mode in ("dense", "zeros", "field")
         self.skip_mode = skip_mode
+        # multi_hop_skip: "dense" or "field" -- the forwards of multi-hop prediction compute only what the readouts of a level's
+        # leaves can see, from work lists built on the device at every hop (ops.field_activity); same results.  Models the lists
+        # do not serve (ops.field_served: Bunch, a composed Ebli plan, hidden widths other than 16 / 32) run dense under either value.
+        if multi_hop_skip not in ("dense", "field"):
+            raise ValueError("multi_hop_skip must be 'dense' or 'field'")
+        self.multi_hop_skip = multi_hop_skip
         self.random_targets = None
         self.trained = False
         self.model = None
@@ -355,6 +362,7 @@ class Scone_GCN():
     # STM:149-150) and the evaluation cache is not touched.
     multi_hop_micro_batch = None
     _multi_hop_trace = None            # a list set on the instance collects what every hop / beam level saw (the tests' window)
+    _multi_hop_fractions = None        # a list set on the instance collects the active fractions of every field-of-view forward
 
     def _multihop_plan(self, inputs):
         if self.model_type != 'bunch' and not isinstance(inputs[0], Bconds):
@@ -369,11 +377,22 @@ class Scone_GCN():
         mb = self.multi_hop_micro_batch or ops.forward_micro_batch(plan, self.weights, n)
         return max(ops.NS, ops.pad_count(int(mb)))
 
-    def _forward_all(self, plan, x, last, mb):
-        """logp [S * NS, D] of all slabs x, mb trajectories per launch."""
+    def _field(self, plan):
+        """Whether this call's forwards run on field-of-view lists (multi_hop_skip = "field" and the lists serve the model)."""
+        return self.multi_hop_skip == "field" and ops.field_served(plan, self.weights) is not None
+
+    def _forward_all(self, plan, x, last, mb, n=None):
+        """logp [S * NS, D] of all slabs x, mb trajectories per launch.  n: the first n trajectories are real and every launch
+        computes only what the readouts at their last nodes can see (field-of-view lists, built from `last` as it stands)."""
         sl = mb // ops.NS
-        outs = [ops.forward_logp(plan, x[s0:s0 + sl], last[s0 * ops.NS:(s0 + sl) * ops.NS], self.weights)
-                for s0 in range(0, x.shape[0], sl)]
+        n_layers = (len(self.weights) - 1) // 3
+        outs = []
+        for s0 in range(0, x.shape[0], sl):
+            last_c = last[s0 * ops.NS:(s0 + sl) * ops.NS]
+            activity = None if n is None else ops.field_activity(plan, last_c, min(int(last_c.shape[0]), n - s0 * ops.NS), n_layers)
+            if activity and self._multi_hop_fractions is not None:
+                self._multi_hop_fractions.append(activity["active_fraction"])
+            outs.append(ops.forward_logp(plan, x[s0:s0 + sl], last_c, self.weights, activity))
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     def _rollout(self, inputs, cur_nodes, n_limit, hops, tab, advance, fill, trace=None):
@@ -394,8 +413,9 @@ class Scone_GCN():
         nodes = torch.empty((hops, N), device=dev, dtype=torch.int32) if advance else None
         err = torch.empty((1,), device=dev, dtype=torch.int32)
         mb = self._mb(plan, N)
+        field_n = N if self._field(plan) else None                           # the lists follow `last` at every hop; x stays dense
         for h in range(hops):
-            logp = self._forward_all(plan, x, last, mb)
+            logp = self._forward_all(plan, x, last, mb, field_n)
             rec = None if trace is None else (ops.slabs_to_batch(x, plan.layout, 1, N)[:, :, 0].cpu().numpy(), last[:N].cpu().numpy(),
                                               logp[:N].cpu().numpy())
             final = h == hops - 1
@@ -488,10 +508,12 @@ class Scone_GCN():
         path_row, path_sign = i32(N, 0), f32(N, 0)
         err = torch.full((hops,), ops.INT32_MAX, device=dev, dtype=torch.int32)
         levels = []                                                          # per level: (entry nodes, children's parents, nodes)
+        field = self._field(plan)
         for h in range(hops):
-            # dead entries (node -1: zero flow column) ride along with last node 0; their output is never read
+            # dead entries (node -1: zero flow column) ride along with last node 0; their output is never read (and they list nothing)
             logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node.clamp(min=0), path_row, path_sign,
-                                       self._mb(plan, N * W))
+                                       self._mb(plan, N * W), field_node=node if field else None,
+                                       fractions=self._multi_hop_fractions)
             W2 = min(beam, W * D)
             final = h == hops - 1
             c_root, c_node, c_score, c_parent, c_slot = i32(N * W2), i32(N * W2), f32(N * W2), i32(N * W2), i32(N * W2)
@@ -569,9 +591,11 @@ class Scone_GCN():
         path_sign = torch.empty((N, 0), device=dev, dtype=torch.float32)
         err = torch.empty((1,), device=dev, dtype=torch.int32)
         D = plan.max_deg
+        field = self._field(plan)
         for h in range(int(hops)):
             L = int(root.shape[0])
-            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node, path_row, path_sign, self._mb(plan, L))
+            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node, path_row, path_sign, self._mb(plan, L),
+                                       field_node=node if field else None, fractions=self._multi_hop_fractions)
             if h == int(hops) - 1:
                 break
             cnt = tab.deg[node.long()]

@@ -32,6 +32,7 @@ def hyperparams(args=None):
           'data_folder_suffix': 'working', 'multi_graph': '', 'holes': 1,
           'skip_mode': 'dense',          # not in the reference: dense | zeros | field (exact zero-skipping, Scone_GCN)
           'multi_hop': 0,                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
+          'multi_hop_skip': 'dense',     # not in the reference: dense | field (field-of-view work lists for the multi-hop forwards)
           'beam': 0}                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
@@ -39,7 +40,7 @@ def hyperparams(args=None):
             if name == 'hidden_layers':
                 nums = list(map(int, args[i + 1].split("_")))
                 hp['hidden_layers'] = [(nums[j], nums[j + 1]) for j in range(0, len(nums), 2)]
-            elif name in ['model_name', 'data_folder_suffix', 'multi_graph', 'model', 'skip_mode']:
+            elif name in ['model_name', 'data_folder_suffix', 'multi_graph', 'model', 'skip_mode', 'multi_hop_skip']:
                 hp[name] = str(args[i + 1])
             else:
                 try:
@@ -227,7 +228,7 @@ def train_model(hp=None):
     (inputs_1hop, inputs_2hop), (y_1hop, y_2hop) = inputs_all, y_all
     in_axes = tuple(([None] * len(shifts)) + [None, None, 0, 0])          # TE:325
     scone = Scone_GCN(hp['epochs'], hp['learning_rate'], hp['batch_size'], hp['weight_decay'],
-                      skip_mode=hp.get('skip_mode', 'dense'))
+                      skip_mode=hp.get('skip_mode', 'dense'), multi_hop_skip=hp.get('multi_hop_skip', 'dense'))
     if hp['model'] not in MODEL_FUNCS:
         raise Exception('invalid model')                                   # TE:445
     model_func = MODEL_FUNCS[hp['model']]

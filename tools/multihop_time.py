@@ -10,7 +10,10 @@
 Device-synchronised wall time (torch.cuda.synchronize around the call), after warm-up calls.  Prints one JSON line per case and
 writes them all to --out.
 
-    python tools/multihop_time.py [--case a|b|c|abc] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
+--skip dense|field|both runs cases (b) and (c) with Scone_GCN.multi_hop_skip set accordingly; `both` times the two in one process on
+one set of tensors and reports their ratio, whether the results agree, and the per-level active fractions of the field lists.
+
+    python tools/multihop_time.py [--case a|b|c|abc] [--skip dense] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
     python tools/multihop_time.py --kernel-stats profiles/multihop_c_kernel_stats.csv
 """
 import argparse
@@ -158,34 +161,79 @@ def _build_big(roots):
     return _net(shifts, inputs, y), inputs, targets, sc, E_lookup, last, nb, cx
 
 
-def case_b(reps, roots=4096):
+def _modes(skip):
+    return ["dense", "field"] if skip == "both" else [skip]
+
+
+def _skip_runs(net, skip, reps, call, leaves):
+    """call() under every mode of `skip`: {mode_s, mode_leaves_per_s, ...} plus, for "field", the active fractions (mean and
+    maximum over the forwards of one call, per list: the input and every layer) and, for "both", the ratio.  Returns (record, the
+    last result per mode)."""
+    rec, last = {}, {}
+    for mode in _modes(skip):
+        net.multi_hop_skip = mode
+        t_first = time.perf_counter()
+        call()                                                               # (field: builds and uploads the block tables)
+        torch.cuda.synchronize()
+        rec[mode + "_first_call_s"] = time.perf_counter() - t_first
+        out = []
+        t = _timed(lambda: out.append(call()), reps)
+        last[mode] = out[-1]
+        rec[mode + "_s"], rec[mode + "_leaves_per_s"] = t, leaves / t
+        if mode == "field":
+            net._multi_hop_fractions = fr = []
+            call()
+            net._multi_hop_fractions = None
+            per = np.array([[f["input"]] + list(f["fwd"]) for f in fr]) if fr else np.zeros((0, 1))
+            rec["field_forwards_per_call"] = len(fr)
+            rec["active_fraction_mean"] = per.mean(axis=0).tolist() if len(fr) else None      # [input, layer 1 .. L]
+            rec["active_fraction_max"] = per.max(axis=0).tolist() if len(fr) else None
+    net.multi_hop_skip = "dense"
+    if skip == "both":
+        rec["dense_over_field"] = rec["dense_s"] / rec["field_s"]
+    rec["device_s"] = rec[_modes(skip)[-1] + "_s"]
+    rec["leaves_per_s"] = leaves / rec["device_s"]
+    return rec, last
+
+
+def case_b(reps, roots=4096, skip="dense"):
     net, inputs, targets, sc, E_lookup, last, nb, cx = _big(roots)
+    net.multi_hop_skip = _modes(skip)[0]                                               # (--skip field: no dense forward in the run)
     t_tab = time.perf_counter()
     net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 1)        # builds and caches the step tables
     t_tab = time.perf_counter() - t_tab
     _say("step tables %.1f s; timing" % t_tab)
-    t = _timed(lambda: net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 2), reps)
     leaves = len(last) + int((nb[last] >= 0).sum())
-    return {"case": "b", "n_edges": int(cx.n_edges), "roots": len(last), "hops": 2, "leaves_evaluated": leaves, "device_s": t,
-            "leaves_per_s": leaves / t, "first_call_hops1_incl_step_tables_s": t_tab}
+    rec, res = _skip_runs(net, skip, reps, lambda: net.multi_hop_target_probs(inputs, targets, sc.nbrhoods, E_lookup, last, 2), leaves)
+    if skip == "both":
+        d, f = res["dense"], res["field"]
+        ok = ~np.isnan(d)
+        rec["nan_pattern_equal"] = bool(np.array_equal(np.isnan(d), np.isnan(f)))
+        rec["max_rel_diff_field_vs_dense"] = float((np.abs(f[ok] - d[ok]) / np.maximum(np.abs(d[ok]), 1e-300)).max()) if ok.any() else None
+    return {"case": "b", "skip": skip, "n_edges": int(cx.n_edges), "roots": len(last), "hops": 2, "leaves_evaluated": leaves,
+            "first_call_hops1_incl_step_tables_s": t_tab, **rec}
 
 
-def case_c(reps, roots=4096, hops=4, beam=8):
+def case_c(reps, roots=4096, hops=4, beam=8, skip="dense"):
     net, inputs, targets, sc, E_lookup, last, nb, cx = _big(roots)
+    net.multi_hop_skip = _modes(skip)[0]
     t_tab = time.perf_counter()
     net.predict_paths_beam(inputs, 1, 1, sc.nbrhoods, E_lookup)                        # builds and caches the step tables
     t_tab = time.perf_counter() - t_tab
     _say("step tables %.1f s; timing the beam" % t_tab)
-    out = []
-    t = _timed(lambda: out.append(net.predict_paths_beam(inputs, hops, beam, sc.nbrhoods, E_lookup)), reps)
-    paths, logp = out[-1]
     widths = [1]
     for _ in range(hops - 1):
         widths.append(min(beam, widths[-1] * sc.max_degree))
     leaves = len(last) * int(sum(widths))
-    return {"case": "c", "n_edges": int(cx.n_edges), "roots": len(last), "hops": hops, "beam": beam, "level_widths": widths,
-            "leaves_evaluated": leaves, "device_s": t, "leaves_per_s": leaves / t, "live_paths": int((paths[:, :, -1] >= 0).sum()),
-            "mean_best_logp": float(logp[:, 0].mean()), "first_call_hops1_incl_step_tables_s": t_tab}
+    rec, res = _skip_runs(net, skip, reps, lambda: net.predict_paths_beam(inputs, hops, beam, sc.nbrhoods, E_lookup), leaves)
+    paths, logp = res[_modes(skip)[-1]]
+    if skip == "both":
+        rec["paths_equal"] = bool(np.array_equal(res["dense"][0], res["field"][0]))
+        rec["max_abs_logp_diff_field_vs_dense"] = float(np.nanmax(np.abs(np.where(np.isfinite(res["dense"][1]),
+                                                                                   res["field"][1] - res["dense"][1], 0.0))))
+    return {"case": "c", "skip": skip, "n_edges": int(cx.n_edges), "roots": len(last), "hops": hops, "beam": beam,
+            "level_widths": widths, "leaves_evaluated": leaves, "live_paths": int((paths[:, :, -1] >= 0).sum()),
+            "mean_best_logp": float(logp[:, 0].mean()), "first_call_hops1_incl_step_tables_s": t_tab, **rec}
 
 
 def kernel_shares(path):
@@ -198,10 +246,15 @@ def kernel_shares(path):
     fwd = sum(t for n, _, t in rows if "scn::fwd_" in n or "scn::readout_fwd" in n)
     hops = {}
     for n, c, t in rows:
-        for k in ("beam_step", "hop_select", "tree_expand", "tree_copy", "tree_patch", "tree_target"):
+        for k in ("beam_step", "hop_select", "tree_expand", "tree_copy_list", "tree_patch_list", "tree_copy", "tree_patch", "tree_target",
+                  "field_mark", "field_hop", "field_count", "field_scan", "field_fill", "clear_list"):
             if k + "_kernel" in n:
                 hops[k] = {"calls": c, "total_ns": t, "share": t / total}
+                break
+    field = sum(v["total_ns"] for k, v in hops.items() if k.startswith("field_"))
+    slabs_list = sum(v["total_ns"] for k, v in hops.items() if k in ("tree_copy_list", "tree_patch_list"))
     return {"kernel_time_s": total / 1e9, "forward_share": fwd / total, "multihop_kernels": hops,
+            "scn_field_lists_share": field / total, "scn_tree_slabs_list_share": slabs_list / total,
             "other_share": 1.0 - (fwd + sum(v["total_ns"] for v in hops.values())) / total}
 
 
@@ -209,6 +262,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="ab")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--skip", default="dense", choices=["dense", "field", "both"], help="multi_hop_skip of cases b and c")
     ap.add_argument("--host-roots", type=int, default=40)
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-stats", default=None, help="a rocprofv3 kernel_stats.csv: print the shares of kernel time and exit")
@@ -222,10 +276,10 @@ def main():
         res.append(case_a(a.reps, a.host_roots))
         print(json.dumps(res[-1]), flush=True)
     if "b" in a.case:
-        res.append(case_b(a.reps))
+        res.append(case_b(a.reps, skip=a.skip))
         print(json.dumps(res[-1]), flush=True)
     if "c" in a.case:
-        res.append(case_c(a.reps))
+        res.append(case_c(a.reps, skip=a.skip))
         print(json.dumps(res[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
