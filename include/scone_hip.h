@@ -529,6 +529,52 @@ int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32
                   int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sampled paths (Monte-Carlo multi-hop prediction): S samples per root walk the model's own next-node distribution.  A level keeps
+ * one entry per DISTINCT path with the number of samples on it, in the layout of the probability tree: entries sorted by root,
+ * leaf_ptr[n_roots + 1] the entries of each root (local index k = l - leaf_ptr[r]), an entry = node, score (the fp32 sum of the
+ * log-probabilities along its path, one add per hop), its path as h (device row, value) pairs, logp[l][0..d) the forward's output.
+ * entry_of[r][s] is the local entry of sample s of root r, -1 for a dropped sample (level 0: all zeros, one entry per root).
+ *
+ * scn_sample_uniform (host): *u = the uniform of (seed, root r, sample s, hop h): Philox4x32-10 with counter (r, s, h, 0) and key
+ *   (seed & 0xffffffff, seed >> 32), u = (out[0] >> 8) * 2^-24 in [0, 1).  The kernels draw the same number: it depends on
+ *   (seed, r, s, h) and on nothing else.
+ * The slot rule of a sample in an entry on node v with lim = deg[v] live slots: m = the maximum of logp[0..lim) by the rule of
+ *   scn_hop_select (first maximum, a NaN counts as the maximum).  If inv_T is +inf (temperature 0) or m is NaN or +-inf, the slot
+ *   is that argmax.  Otherwise w_j = expf((logp_j - m) * inv_T) (one fp32 subtract, one fp32 multiply), c_j the fp32 running sum
+ *   in slot order, and the slot is the first j with c_j > u * c_{lim-1}; if none (rounding at the top end), the last j with
+ *   w_j > 0.  deg[v] == 0 or v outside [0, n_nodes): the sample is dropped and nothing is read through v.
+ * scn_sample_draw: level h, one workgroup per root.  pick[r][s] = k * d + j (k = entry_of[r][s], j by the slot rule with the
+ *   uniform of (seed, r, s, h)), -1 for a dropped sample; n_child[r] = the number of distinct picks of root r.  Every slot
+ *   j < deg of every entry on a valid node whose pair has no edge (step_edge < 0 or >= n_rows, or step_node < 0) lowers err[0] to
+ *   (global entry index) * d + j (atomicMin; the caller initialises it to INT32_MAX), drawn or not: the word does not depend on
+ *   the seed.
+ * scn_sample_expand: child_ptr = the exclusive scan of n_child (the caller's; its total n_children sizes the outputs).  The
+ *   children of root r go to child_ptr[r] + rank in ascending pick order (lower parent, then lower slot): c_root = r, c_node =
+ *   step_node[v][j], c_score = score[k] + logp[k][j] (one fp32 add), c_parent = k, c_slot = j, c_count = the samples with that pick
+ *   and -- unless c_path_row is NULL (final level) -- the parent's path plus (step_edge[v][j], step_sign[v][j]) ([c][h + 1]).
+ *   entry_of_next[r][s] = the rank of pick[r][s], -1 for -1.  A child across a pair without an edge is written as the tables give
+ *   it (see scn_beam_step); the caller reads err and discards the level.
+ * Both: max_entries is the caller's bound on the entries of one root (a root with more, or a leaf_ptr outside [0, n_leaves], is a
+ *   caller's error the library only guards against: the excess is ignored and samples in it are dropped).  Integer LDS atomics
+ *   only, no float atomics: the same inputs give the same bytes.  The outputs must not overlap the inputs.  Limits
+ *   (SCN_ERR_UNSUPPORTED beyond): n_samples <= SCN_SAMPLE_MAX, max_entries * d <= SCN_SAMPLE_PAIRS_MAX (the bits of the (entry,
+ *   slot) bitmap a workgroup keeps in LDS: 4096 entries of 32 slots), n_leaves * d and n_roots * n_samples below 2^31 - 1.  n_roots
+ *   == 0 returns SCN_OK. */
+#define SCN_SAMPLE_MAX 4096
+#define SCN_SAMPLE_PAIRS_MAX 131072
+int scn_sample_uniform(uint64_t seed, int32_t root, int32_t sample, int32_t hop, float* u);
+int scn_sample_draw(int32_t n_roots, int32_t n_samples, int32_t max_entries, int32_t n_leaves, int32_t h, int32_t d, uint64_t seed,
+                    float inv_T, const int32_t* leaf_ptr, const int32_t* node, const float* logp, const int32_t* entry_of,
+                    const int32_t* deg, int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, int32_t n_rows,
+                    int32_t* pick, int32_t* n_child, int32_t* err, void* stream);
+int scn_sample_expand(int32_t n_roots, int32_t n_samples, int32_t max_entries, int32_t n_leaves, int32_t h, int32_t d,
+                      const int32_t* leaf_ptr, const int32_t* node, const float* score, const int32_t* path_row, const float* path_sign,
+                      const float* logp, const int32_t* pick, const int32_t* child_ptr, int32_t n_children, int32_t n_nodes,
+                      const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t* c_root, int32_t* c_node,
+                      float* c_score, int32_t* c_parent, int32_t* c_slot, int32_t* c_count, int32_t* c_path_row, float* c_path_sign,
+                      int32_t* entry_of_next, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Field-of-view work lists of a multi-hop level, built on the device.  The readout of a leaf reads the last layer only on the
  * edges around the leaf's node, and every layer below needs one more hop of the operator's pattern: with the two block-level CSR
  * tables (host-built once per plan, then device arrays; block indices ascending in every row)

@@ -20,6 +20,8 @@ ACT = {"none": 0, "tanh": 1, "relu": 2, "leaky_relu": 3}
 SCN_ERR_BAD_ARG = -1              # include/scone_hip.h
 SCN_ERR_UNSUPPORTED = -4
 SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
+SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sample_expand
+SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
 
 
 class WorkListDesc(ctypes.Structure):          # scn_work_list (device pointers)
@@ -146,6 +148,12 @@ SIGNATURES = {
     "scn_beam_step": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_sample_uniform": (ctypes.c_int, [ctypes.c_uint64, c_i32, c_i32, c_i32, P_f32]),
+    "scn_sample_draw": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_uint64, c_f32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_sample_expand": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_field_lists_workspace": (c_size_t, [c_i32, c_i32, c_i32]),
     "scn_field_lists": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                        c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),

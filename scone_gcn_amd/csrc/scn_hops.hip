@@ -258,6 +258,187 @@ __global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int 
     }
 }
 
+
+// ---- sampled paths: one entry per distinct path with a count; a level step = draw (pick per sample) + expand (merge equal picks) ----
+constexpr int SAMPLE_THREADS = 256;
+constexpr int SAMPLE_WORDS = SCN_SAMPLE_PAIRS_MAX / 32;      // words of the per-root (entry, slot) bitmap in LDS
+
+// The slot rule of one sample in one entry (include/scone_hip.h): the masked argmax when inv_T is +inf or the maximum is not finite;
+// else the first slot whose fp32 running sum of expf((logp_j - m) * inv_T) exceeds u * total, and the last slot of positive weight
+// where rounding at the top end leaves none.  lim >= 1.  Every operation spelled out: one subtract, one multiply, no division.
+__device__ __forceinline__ int sample_slot(const float* __restrict__ row, int d, int lim, float inv_T, float u) {
+#pragma clang fp contract(off)
+    const int a = masked_argmax(row, d, lim, -__builtin_inff());
+    const float m = row[a];
+    if (isinf(inv_T) || !isfinite(m)) return a;
+    float total = 0.f;
+    for (int j = 0; j < lim; ++j) total += expf((row[j] - m) * inv_T);
+    const float thr = u * total;
+    float c = 0.f;
+    int last = a;
+    for (int j = 0; j < lim; ++j) {
+        const float w = expf((row[j] - m) * inv_T);
+        c += w;
+        if (c > thr) return j;
+        if (w > 0.f) last = j;
+    }
+    return last;
+}
+
+// the entries of root r: [l0, l0 + ne), clamped to the level and to max_entries (a longer range is a caller's error, guarded only)
+__device__ __forceinline__ void sample_range(const int32_t* __restrict__ leaf_ptr, int r, int n_leaves, int max_entries, int& l0, int& ne) {
+    const int a = leaf_ptr[r], b = leaf_ptr[r + 1];
+    l0 = a < 0 ? 0 : (a > n_leaves ? n_leaves : a);
+    const int l1 = b < l0 ? l0 : (b > n_leaves ? n_leaves : b);
+    ne = l1 - l0 < max_entries ? l1 - l0 : max_entries;
+}
+
+// one workgroup per root: the missing-edge word over every live (k, j), then every sample's pick and the bitmap of the used (k, j)
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_samples, int max_entries, int n_leaves, int h, int d,
+                                                                     uint64_t seed, float inv_T, const int32_t* __restrict__ leaf_ptr,
+                                                                     const int32_t* __restrict__ node, const float* __restrict__ logp,
+                                                                     const int32_t* __restrict__ entry_of, const int32_t* __restrict__ deg,
+                                                                     int n_nodes, const int32_t* __restrict__ step_node,
+                                                                     const int32_t* __restrict__ step_edge, int n_rows,
+                                                                     int32_t* __restrict__ pick, int32_t* __restrict__ n_child, int32_t* err) {
+    __shared__ unsigned s_bits[SAMPLE_WORDS];
+    __shared__ int s_total;
+    const int r = blockIdx.x, t = threadIdx.x;
+    int l0, ne;
+    sample_range(leaf_ptr, r, n_leaves, max_entries, l0, ne);
+    const int n_pairs = ne * d, n_words = (n_pairs + 31) >> 5;
+    for (int w = t; w < n_words; w += SAMPLE_THREADS) s_bits[w] = 0u;
+    if (t == 0) s_total = 0;
+    for (int c = t; c < n_pairs; c += SAMPLE_THREADS) {
+        const int k = c / d, j = c - k * d;
+        const int v = node[l0 + k];
+        if (v < 0 || v >= n_nodes || j >= deg[v]) continue;
+        const size_t q = (size_t)v * d + j;
+        const int e = step_edge[q];
+        if (e < 0 || e >= n_rows || step_node[q] < 0) atomicMin(err, (l0 + k) * d + j);
+    }
+    __syncthreads();
+    const size_t s0 = (size_t)r * n_samples;
+    for (int s = t; s < n_samples; s += SAMPLE_THREADS) {
+        const int k = entry_of[s0 + s];
+        int p = -1;
+        if (k >= 0 && k < ne) {
+            const int v = node[l0 + k];
+            const int dv = (v >= 0 && v < n_nodes) ? deg[v] : 0;
+            const int lim = dv > d ? d : dv;
+            if (lim > 0) {
+                const float u = scn::sample_uniform(seed, r, s, h);
+                p = k * d + sample_slot(logp + (size_t)(l0 + k) * d, d, lim, inv_T, u);
+                atomicOr(&s_bits[p >> 5], 1u << (p & 31));
+            }
+        }
+        pick[s0 + s] = p;
+    }
+    __syncthreads();
+    int cnt = 0;
+    for (int w = t; w < n_words; w += SAMPLE_THREADS) cnt += __popc(s_bits[w]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if ((t & 63) == 0 && cnt) atomicAdd(&s_total, cnt);
+    __syncthreads();
+    if (t == 0) n_child[r] = s_total;
+}
+
+// one workgroup per root: the bitmap again from the picks, its running population count, then one child per set bit at
+// child_ptr[r] + rank (ascending pick = lower parent, then lower slot) and every sample's rank
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_expand_kernel(int n_samples, int max_entries, int n_leaves, int h, int d,
+                                                                       const int32_t* __restrict__ leaf_ptr, const int32_t* __restrict__ node,
+                                                                       const float* __restrict__ score, const int32_t* __restrict__ path_row,
+                                                                       const float* __restrict__ path_sign, const float* __restrict__ logp,
+                                                                       const int32_t* __restrict__ pick, const int32_t* __restrict__ child_ptr,
+                                                                       int n_children, int n_nodes, const int32_t* __restrict__ step_node,
+                                                                       const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
+                                                                       int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
+                                                                       float* __restrict__ c_score, int32_t* __restrict__ c_parent,
+                                                                       int32_t* __restrict__ c_slot, int32_t* __restrict__ c_count,
+                                                                       int32_t* __restrict__ c_path_row, float* __restrict__ c_path_sign,
+                                                                       int32_t* __restrict__ entry_of_next) {
+    __shared__ unsigned s_bits[SAMPLE_WORDS];
+    __shared__ int s_before[SAMPLE_WORDS];           // set bits in the words before this one
+    __shared__ int s_count[SCN_SAMPLE_MAX];          // samples of the child of each rank (children <= samples)
+    __shared__ int s_wave[SAMPLE_THREADS / 64];
+    const int r = blockIdx.x, t = threadIdx.x;
+    int l0, ne;
+    sample_range(leaf_ptr, r, n_leaves, max_entries, l0, ne);
+    const int n_pairs = ne * d, n_words = (n_pairs + 31) >> 5;
+    for (int w = t; w < n_words; w += SAMPLE_THREADS) s_bits[w] = 0u;
+    for (int s = t; s < n_samples; s += SAMPLE_THREADS) s_count[s] = 0;
+    __syncthreads();
+    const size_t s0 = (size_t)r * n_samples;
+    // a pick outside the root's pairs, or through an entry that stands on no node, is no pick (only the draw's own output is in range)
+    auto valid = [&](int p) {
+        if (p < 0 || p >= n_pairs) return false;
+        const int v = node[l0 + p / d];
+        return v >= 0 && v < n_nodes;
+    };
+    for (int s = t; s < n_samples; s += SAMPLE_THREADS) {
+        const int p = pick[s0 + s];
+        if (valid(p)) atomicOr(&s_bits[p >> 5], 1u << (p & 31));
+    }
+    __syncthreads();
+    // exclusive scan of the words' population counts: thread t owns the words [t * per, (t + 1) * per)
+    const int per = (n_words + SAMPLE_THREADS - 1) / SAMPLE_THREADS;
+    const int w0 = t * per, w1 = w0 + per < n_words ? w0 + per : n_words;
+    int mine = 0;
+    for (int w = w0; w < w1; ++w) mine += __popc(s_bits[w]);
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int other = __shfl_up(incl, o, 64);
+        if ((t & 63) >= o) incl += other;
+    }
+    if ((t & 63) == 63) s_wave[t >> 6] = incl;
+    __syncthreads();
+    int run = incl - mine;
+    for (int q = 0; q < (t >> 6); ++q) run += s_wave[q];
+    for (int w = w0; w < w1; ++w) {
+        s_before[w] = run;
+        run += __popc(s_bits[w]);
+    }
+    __syncthreads();
+    for (int s = t; s < n_samples; s += SAMPLE_THREADS) {
+        const int p = pick[s0 + s];
+        int rank = -1;
+        if (valid(p)) {
+            rank = s_before[p >> 5] + __popc(s_bits[p >> 5] & ((1u << (p & 31)) - 1u));
+            atomicAdd(&s_count[rank], 1);
+        }
+        entry_of_next[s0 + s] = rank;
+    }
+    __syncthreads();
+    const int c0 = child_ptr[r];
+    for (int w = t; w < n_words; w += SAMPLE_THREADS) {
+        unsigned bits = s_bits[w];
+        int rank = s_before[w];
+        for (; bits; bits &= bits - 1u, ++rank) {
+            const int p = (w << 5) + __ffs(bits) - 1;
+            const int k = p / d, j = p - k * d;
+            const int c = c0 + rank;
+            if (c < 0 || c >= n_children) continue;                      // child_ptr is not the scan of the draw's n_child: guarded only
+            const size_t q = (size_t)node[l0 + k] * d + j;
+            c_root[c] = r;
+            c_node[c] = step_node[q];
+            c_score[c] = score[l0 + k] + logp[(size_t)(l0 + k) * d + j];
+            c_parent[c] = k;
+            c_slot[c] = j;
+            c_count[c] = s_count[rank];
+            if (c_path_row) {
+                const size_t dst = (size_t)c * (h + 1), src = (size_t)(l0 + k) * h;
+                for (int i = 0; i < h; ++i) {
+                    c_path_row[dst + i] = path_row[src + i];
+                    c_path_sign[dst + i] = path_sign[src + i];
+                }
+                c_path_row[dst + h] = step_edge[q];
+                c_path_sign[dst + h] = step_sign[q];
+            }
+        }
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -344,6 +525,59 @@ int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32
     hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, w_in, w_out, h, d, node, score,
                        path_row, path_sign, logp, deg, n_nodes, step_node, step_edge, step_sign, n_rows, c_root, c_node, c_score,
                        c_parent, c_slot, c_path_row, c_path_sign, err);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_sample_uniform(uint64_t seed, int32_t root, int32_t sample, int32_t hop, float* u) {
+    if (!u) return SCN_ERR_BAD_ARG;
+    *u = scn::sample_uniform(seed, root, sample, hop);
+    return SCN_OK;
+}
+
+static int sample_shape(int32_t n_roots, int32_t n_samples, int32_t max_entries, int32_t n_leaves, int32_t h, int32_t d, int32_t n_nodes,
+                        int32_t n_rows) {
+    if (n_roots < 0 || n_samples <= 0 || max_entries <= 0 || n_leaves < 0 || h < 0 || d <= 0 || n_nodes <= 0 || n_rows <= 0)
+        return SCN_ERR_BAD_SHAPE;
+    if (n_samples > SCN_SAMPLE_MAX || (int64_t)max_entries * d > SCN_SAMPLE_PAIRS_MAX) return SCN_ERR_UNSUPPORTED;
+    if ((int64_t)n_leaves * d >= INT_MAX || (int64_t)n_roots * n_samples >= INT_MAX) return SCN_ERR_UNSUPPORTED;
+    return SCN_OK;
+}
+
+int scn_sample_draw(int32_t n_roots, int32_t n_samples, int32_t max_entries, int32_t n_leaves, int32_t h, int32_t d, uint64_t seed,
+                    float inv_T, const int32_t* leaf_ptr, const int32_t* node, const float* logp, const int32_t* entry_of,
+                    const int32_t* deg, int32_t n_nodes, const int32_t* step_node, const int32_t* step_edge, int32_t n_rows,
+                    int32_t* pick, int32_t* n_child, int32_t* err, void* stream) {
+    const int st = sample_shape(n_roots, n_samples, max_entries, n_leaves, h, d, n_nodes, n_rows);
+    if (st != SCN_OK) return st;
+    if (!(inv_T >= 0.f)) return SCN_ERR_BAD_ARG;
+    if (n_roots == 0) return SCN_OK;
+    if (!leaf_ptr || !node || !logp || !entry_of || !deg || !step_node || !step_edge || !pick || !n_child || !err) return SCN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(sample_draw_kernel, dim3((unsigned)n_roots), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, n_samples, max_entries,
+                       n_leaves, h, d, seed, inv_T, leaf_ptr, node, logp, entry_of, deg, n_nodes, step_node, step_edge, n_rows, pick,
+                       n_child, err);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_sample_expand(int32_t n_roots, int32_t n_samples, int32_t max_entries, int32_t n_leaves, int32_t h, int32_t d,
+                      const int32_t* leaf_ptr, const int32_t* node, const float* score, const int32_t* path_row, const float* path_sign,
+                      const float* logp, const int32_t* pick, const int32_t* child_ptr, int32_t n_children, int32_t n_nodes,
+                      const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t* c_root, int32_t* c_node,
+                      float* c_score, int32_t* c_parent, int32_t* c_slot, int32_t* c_count, int32_t* c_path_row, float* c_path_sign,
+                      int32_t* entry_of_next, void* stream) {
+    const int st = sample_shape(n_roots, n_samples, max_entries, n_leaves, h, d, n_nodes, 1);
+    if (st != SCN_OK) return st;
+    if (n_children < 0) return SCN_ERR_BAD_SHAPE;
+    if (n_roots == 0) return SCN_OK;
+    if (!leaf_ptr || !node || !score || !logp || !pick || !child_ptr || !step_node || !step_edge || !step_sign || !entry_of_next)
+        return SCN_ERR_BAD_ARG;
+    if (n_children > 0 && (!c_root || !c_node || !c_score || !c_parent || !c_slot || !c_count)) return SCN_ERR_BAD_ARG;
+    if (c_path_row && (!c_path_sign || (h > 0 && (!path_row || !path_sign)))) return SCN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(sample_expand_kernel, dim3((unsigned)n_roots), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, n_samples,
+                       max_entries, n_leaves, h, d, leaf_ptr, node, score, path_row, path_sign, logp, pick, child_ptr, n_children,
+                       n_nodes, step_node, step_edge, step_sign, c_root, c_node, c_score, c_parent, c_slot, c_count, c_path_row,
+                       c_path_sign, entry_of_next);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

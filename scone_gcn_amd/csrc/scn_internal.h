@@ -124,6 +124,35 @@ __host__ __device__ __forceinline__ void adam_corrections(float b1, float b2, in
     c2 = 1.f - (float)pow((double)b2, (double)(i + 1));
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): the counter-based generator behind the sampled multi-hop decoder, one definition for the
+// host entry point (scn_sample_uniform) and the kernels.  out = the block function of (counter, key).
+__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0;
+    out[1] = c1;
+    out[2] = c2;
+    out[3] = c3;
+}
+// The uniform of (seed, root, sample, hop) in [0, 1), 24 bits: keyed by these four and by nothing else (not the launch, the chunk or
+// the entry the sample sits in).
+__host__ __device__ __forceinline__ float sample_uniform(uint64_t seed, int32_t root, int32_t sample, int32_t hop) {
+    const uint32_t ctr[4] = {(uint32_t)root, (uint32_t)sample, (uint32_t)hop, 0u};
+    const uint32_t key[2] = {(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32)};
+    uint32_t out[4];
+    philox4x32_10(ctr, key, out);
+    return (float)(out[0] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
+}
+
 struct Group {
     int32_t n_cols = 0, identity = 0, n_vals = 0;
     int64_t nnz = 0;

@@ -13,6 +13,7 @@ fp32 buffer so that the gradient all-reduce and the fused Adam/ridge kernel see 
 sharded over ranks when torch.distributed is initialised (scone_gcn_amd/distributed.py).
 """
 import ctypes
+import gc
 
 import numpy as np
 import torch
@@ -555,6 +556,154 @@ class Scone_GCN():
         hit = np.any((end >= 0) & (end == np.asarray(target_nodes).reshape(-1, 1)), axis=1)
         return float(np.average(hit[np.asarray(mask) == 1]))
 
+    def _sample_levels(self, inputs, hops, n_samples, seed, temperature, nbrhoods, E_lookup):
+        """The sampled decoder's levels on the device.  A level keeps one entry per distinct path with the number of samples on it
+        (the probability tree's layout: entries sorted by trajectory, leaf_ptr); one batched forward over the entries
+        (ops.tree_level_logp), then scn_sample_draw picks every sample's slot inside the entry it sits in and scn_sample_expand
+        merges equal picks into one child (include/scone_hip.h) -- sample by sample what n_samples independent chains give, at the
+        cost of the distinct paths.  One size copy back per level; the error words of all levels are read once, at the end.
+        Returns (levels, final): levels[h] = (leaf_ptr [N + 1], node [L_h], entry_of [N, S]) for h = 0 .. hops (level 0 = the
+        roots), final = (leaf_ptr, node, score, count) of the last level, all device tensors."""
+        hops, S = int(hops), int(n_samples)
+        if hops < 1:
+            raise ValueError("hops must be at least 1")
+        if S < 1 or S > _lib.SCN_SAMPLE_MAX:
+            raise ValueError("n_samples must be between 1 and %d (SCN_SAMPLE_MAX)" % _lib.SCN_SAMPLE_MAX)
+        if not float(temperature) >= 0.0:
+            raise ValueError("temperature must not be negative")
+        inv_T = float("inf") if float(temperature) == 0.0 else float(np.float32(1.0) / np.float32(temperature))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        plan = self._multihop_plan(inputs)
+        if nbrhoods is None:
+            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
+        if E_lookup is None:
+            E_lookup = self._edge_lookup(inputs)
+        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
+        lib = _lib.load()
+        dev = plan.device
+        N, D = _n_samples(inputs[-1]), plan.max_deg
+        if len(np.asarray(inputs[1]).reshape(-1)) != N:
+            raise ValueError("last nodes need one entry per trajectory of inputs (%d)" % N)
+        if S * D > _lib.SCN_SAMPLE_PAIRS_MAX or N * S * D >= ops.INT32_MAX:
+            raise ValueError("sampled level of %d x %d entries of %d slots is too large" % (N, S, D))
+        trace = self._multi_hop_trace
+        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)          # a copy: the caller's flows stay as they are
+        i32, f32 = (lambda *s: torch.empty(s, device=dev, dtype=torch.int32)), (lambda *s: torch.empty(s, device=dev, dtype=torch.float32))
+        p = lambda t: None if t is None else ops._dev(t, t.dtype)
+        root = torch.arange(N, device=dev, dtype=torch.int32)
+        node = torch.from_numpy(np.ascontiguousarray(np.asarray(inputs[1]).reshape(-1), np.int32)).to(dev)
+        score = torch.zeros((N,), device=dev, dtype=torch.float32)
+        count = torch.full((N,), S, device=dev, dtype=torch.int32)
+        path_row, path_sign = i32(N, 0), f32(N, 0)
+        leaf_ptr = torch.arange(N + 1, device=dev, dtype=torch.int32)
+        entry_of = torch.zeros((N, S), device=dev, dtype=torch.int32)
+        err = torch.full((hops,), ops.INT32_MAX, device=dev, dtype=torch.int32)
+        levels = [(leaf_ptr, node, entry_of)]
+        field = self._field(plan)
+        for h in range(hops):
+            L = int(node.shape[0])
+            if L == 0:                                                       # every sample has been dropped: the level stays empty
+                levels.append((leaf_ptr, node, torch.full_like(entry_of, -1)))
+                continue
+            # an entry on node -1 (the child of a pair without an edge) rides along with last node 0; its samples are dropped
+            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node.clamp(min=0), path_row, path_sign, self._mb(plan, L),
+                                       field_node=node if field else None, fractions=self._multi_hop_fractions)
+            pick, n_child = i32(N, S), i32(N)
+            _lib.check(lib.scn_sample_draw(N, S, S, L, h, D, seed, inv_T, p(leaf_ptr), p(node), p(logp), p(entry_of), p(tab.deg),
+                                           tab.n_nodes, p(tab.node), p(tab.edge), plan.n_edges, p(pick), p(n_child), p(err[h:]),
+                                           ops._stream()), "scn_sample_draw")
+            child_ptr = torch.zeros((N + 1,), device=dev, dtype=torch.int32)
+            child_ptr[1:] = torch.cumsum(n_child, 0)
+            C = int(child_ptr[-1].item())                                    # the one copy back per level: the next level's size
+            final = h == hops - 1
+            c_root, c_node, c_score, c_parent, c_slot, c_count = i32(C), i32(C), f32(C), i32(C), i32(C), i32(C)
+            c_row, c_sign = (None, None) if final else (i32(C, h + 1), f32(C, h + 1))
+            entry_next = i32(N, S)
+            _lib.check(lib.scn_sample_expand(N, S, S, L, h, D, p(leaf_ptr), p(node), p(score), p(path_row) if h else None,
+                                             p(path_sign) if h else None, p(logp), p(pick), p(child_ptr), C, tab.n_nodes, p(tab.node),
+                                             p(tab.edge), p(tab.sign), p(c_root), p(c_node), p(c_score), p(c_parent), p(c_slot),
+                                             p(c_count), p(c_row), p(c_sign), p(entry_next), ops._stream()), "scn_sample_expand")
+            if trace is not None:
+                trace.append({"leaf_ptr": leaf_ptr.cpu().numpy(), "node": node.cpu().numpy(), "score": score.cpu().numpy(),
+                              "count": count.cpu().numpy(), "logp": logp.cpu().numpy(), "entry_of": entry_of.cpu().numpy(),
+                              "pick": pick.cpu().numpy(), "child_ptr": child_ptr.cpu().numpy(), "parent": c_parent.cpu().numpy(),
+                              "slot": c_slot.cpu().numpy(), "child_count": c_count.cpu().numpy()})
+            root, node, score, count, path_row, path_sign, leaf_ptr, entry_of = c_root, c_node, c_score, c_count, c_row, c_sign, \
+                child_ptr, entry_next
+            levels.append((leaf_ptr, node, entry_of))
+        errs = err.cpu().numpy()
+        for h in np.flatnonzero(errs != ops.INT32_MAX)[:1]:
+            t = int(errs[h])
+            v = int(levels[h][1][t // D].item())
+            raise KeyError((v, int(tab.h_node[v, t % D])))
+        return levels, (leaf_ptr, node, score, count)
+
+    def sample_paths(self, inputs, hops, n_samples, seed=0, temperature=1.0, nbrhoods=None, E_lookup=None):
+        """Monte-Carlo multi-hop prediction with the semantics of predict_paths (current and readout node advance, a step SETS its
+        edge, backtracking allowed, "binary" step tables, same defaults): n_samples paths per trajectory, every step drawn from the
+        model's own next-node distribution at `temperature` (0 = the greedy rollout) -- the slot rule and the generator are in
+        include/scone_hip.h; the draw of (trajectory, sample, hop) depends on `seed` and these three alone.  Returns
+        (paths (N, n_samples, hops) int64 node ids, logp (N, n_samples) float64 = the summed log-probabilities), sample s in
+        column s; a dropped sample (it reached a node without neighbours) is -1 / -inf.  Samples on the same path share one
+        forward: a level costs its distinct paths (_sample_levels).  Paths are rebuilt on the device, one copy at the end."""
+        levels, (leaf_ptr, node, score, _) = self._sample_levels(inputs, hops, n_samples, seed, temperature, nbrhoods, E_lookup)
+        dead = levels[-1][2] < 0
+        steps = []
+        for ptr, nodes, entry_of in levels[1:]:
+            at = ptr[:-1, None].long() + entry_of.clamp(min=0).long()
+            steps.append(nodes.long()[at.clamp(max=max(int(nodes.shape[0]) - 1, 0))] if nodes.shape[0] else
+                         torch.full_like(at, -1))
+        paths = torch.stack(steps, dim=2).masked_fill(dead[:, :, None], -1)
+        at = leaf_ptr[:-1, None].long() + levels[-1][2].clamp(min=0).long()
+        lp = score.double()[at.clamp(max=max(int(score.shape[0]) - 1, 0))] if score.shape[0] else torch.zeros_like(at, dtype=torch.float64)
+        lp = lp.masked_fill(dead, float("-inf"))
+        return paths.cpu().numpy(), lp.cpu().numpy()
+
+    def _sample_end_counts(self, inputs, hops, n_samples, seed, temperature):
+        """Per distinct (trajectory, end node) of the final level the number of samples there: (trajectory [M], node [M],
+        samples [M]) int64 device tensors, sorted by trajectory, then node."""
+        _, (leaf_ptr, node, _, count) = self._sample_levels(inputs, hops, n_samples, seed, temperature, None, None)
+        N = int(leaf_ptr.shape[0]) - 1
+        V = int(node.max().item()) + 2 if node.shape[0] else 1
+        root = torch.repeat_interleave(torch.arange(N, device=node.device), (leaf_ptr[1:] - leaf_ptr[:-1]).long())
+        live = node >= 0
+        key, inv = torch.unique(root[live] * V + node[live].long(), return_inverse=True)
+        total = torch.zeros(key.shape, device=node.device, dtype=torch.int64).index_add_(0, inv, count[live].long())
+        return torch.div(key, V, rounding_mode="floor"), key % V, total
+
+    def multi_hop_reach_probs(self, inputs, hops, n_samples, seed=0, temperature=1.0):
+        """Where sample_paths' samples end, without building the paths: (nodes (N, K) int64, freq (N, K) float64) = per trajectory
+        the distinct end nodes after `hops` steps and their share of the n_samples samples (dropped samples count in the
+        denominator), highest share first, ties by the lower node id; the tail past a trajectory's distinct end nodes is -1 / 0.
+        Computed from the final level's entries and counts."""
+        r, v, c = self._sample_end_counts(inputs, hops, n_samples, seed, temperature)
+        N = _n_samples(inputs[-1])
+        order = torch.sort(-c, stable=True)[1]                                # (r, v) ascending already; stable sorts keep the ties
+        order = order[torch.sort(r[order], stable=True)[1]]
+        r, v, c = r[order].cpu().numpy(), v[order].cpu().numpy(), c[order].cpu().numpy()
+        start = np.searchsorted(r, np.arange(N))
+        K = int(np.bincount(r, minlength=N).max()) if len(r) else 0
+        nodes, freq = np.full((N, K), -1, np.int64), np.zeros((N, K), np.float64)
+        col = np.arange(len(r)) - start[r]
+        nodes[r, col], freq[r, col] = v, c / np.float64(int(n_samples))
+        return nodes, freq
+
+    def multi_hop_target_probs_sampled(self, inputs, target_nodes, hops, n_samples, seed=0):
+        """(N,) float64: the share of trajectory i's n_samples sampled paths (sample_paths at temperature 1) that end at
+        target_nodes[i] after `hops` steps -- an unbiased estimate of the probability of REACHING the target, the SUM of the
+        probabilities of all paths that end there.  This is not what multi_hop_target_probs returns: the reference's tree divides
+        that sum by the NUMBER of paths that reach the target (scn_tree_target), and is NaN where none does; this one estimates the
+        sum itself and is 0 there."""
+        r, v, c = (t.cpu().numpy() for t in self._sample_end_counts(inputs, hops, n_samples, seed, 1.0))
+        target = np.asarray(target_nodes).reshape(-1)
+        N = _n_samples(inputs[-1])
+        if len(target) != N:
+            raise ValueError("target_nodes needs one entry per trajectory of inputs (%d)" % N)
+        hit = np.zeros(N, np.int64)
+        m = v == target[r]
+        hit[r[m]] = c[m]
+        return hit / np.float64(int(n_samples))
+
     def _edge_lookup(self, inputs):
         src = inputs[0] if self.model_type != 'bunch' else resolve_operands('bunch', self.shifts, inputs[0])[0][1]
         hit = self._lookup_cache
@@ -759,8 +908,18 @@ class Scone_GCN():
         loss = body()                                    # eager: this call's result, and the warm-up of the capture
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            part = body()
+        # torch.cuda.graph no longer collects garbage before a capture (torch >= 2.9): a dead cycle that still holds a captured graph
+        # or device memory would be freed whenever the collector next runs, and a free inside the capture invalidates it
+        # (hipErrorStreamCaptureInvalidated at the next launch).  Collect now, and keep the collector out of the capture.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                part = body()
+        finally:
+            if gc_was_on:
+                gc.enable()
         self._drop_graphs(self.GRAPH_CACHE - 1)
         self._graphs[key] = (g, part, staged, plan)
         return loss

@@ -33,7 +33,8 @@ def hyperparams(args=None):
           'skip_mode': 'dense',          # not in the reference: dense | zeros | field (exact zero-skipping, Scone_GCN)
           'multi_hop': 0,                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
           'multi_hop_skip': 'dense',     # not in the reference: dense | field (field-of-view work lists for the multi-hop forwards)
-          'beam': 0}                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
+          'beam': 0,                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
+          'multi_hop_samples': 0}        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
@@ -279,6 +280,10 @@ def train_model(hp=None):
             results["multi_hop_topk"] = [scone.multi_hop_accuracy_topk(inputs_1hop, target_nodes_all[1], m, 2, int(hp['beam']))
                                          for m in (train_mask, test_mask)]
             print('Multi hop top-%d accs:' % int(hp['beam']), results["multi_hop_topk"])
+        if int(hp.get('multi_hop_samples', 0)) > 0:                        # not in the reference: the share of sampled paths ending at the target (seed 0)
+            tp = scone.multi_hop_target_probs_sampled(inputs_1hop, target_nodes_all[1], 2, int(hp['multi_hop_samples']))
+            results["multi_hop_sampled"] = [float(np.average(tp[np.asarray(m) == 1])) for m in (train_mask, test_mask)]
+            print('Multi hop sampled target probs (%d samples):' % int(hp['multi_hop_samples']), results["multi_hop_sampled"])
     scone.experiment_results = results
     return scone, (train_loss, train_acc, test_loss, test_acc)
 

@@ -1,5 +1,5 @@
-"""Timing of the device multi-hop probability tree (Scone_GCN.multi_hop_accuracy_dist, STM:154-206) and of the beam search
-(Scone_GCN.predict_paths_beam).
+"""Timing of the device multi-hop probability tree (Scone_GCN.multi_hop_accuracy_dist, STM:154-206), of the beam search
+(Scone_GCN.predict_paths_beam) and of the sampled decoder (Scone_GCN.sample_paths).
 
   (a) the 400-point generated data set, 1000 paths, dist with hops = 2: the device pipeline against a host loop that calls
       scone_func once per tree leaf (what the reference does with model_single);
@@ -7,13 +7,18 @@
   (c) the complex and roots of (b), beam search with hops = 4 and beam = 8: leaves per second (every entry a level pushes through
       the forward is a leaf), to be read against (b) of the same run.  The share of kernel time the forward kernels take comes from
       a run of `--case c` alone under `rocprofv3 --kernel-trace --stats`, whose kernel table `--kernel-stats FILE` sums up.
+  (d) the complex and roots of (b), sampled paths with hops = 8 and 256 samples per root (--d-roots R: the first R of the roots):
+      seconds per call, leaves evaluated (the distinct entries of every level that goes through the forward) and leaves per
+      second, to be read against (b) and (c) of the same run, and per level the distinct entries against the live samples.  The
+      share of kernel time of sample_draw_kernel / sample_expand_kernel comes from a run of `--case d` alone under
+      `rocprofv3 --kernel-trace --stats`, summed by `--kernel-stats FILE`.
 Device-synchronised wall time (torch.cuda.synchronize around the call), after warm-up calls.  Prints one JSON line per case and
 writes them all to --out.
 
 --skip dense|field|both runs cases (b) and (c) with Scone_GCN.multi_hop_skip set accordingly; `both` times the two in one process on
 one set of tensors and reports their ratio, whether the results agree, and the per-level active fractions of the field lists.
 
-    python tools/multihop_time.py [--case a|b|c|abc] [--skip dense] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
+    python tools/multihop_time.py [--case a|b|c|d|abcd] [--d-roots 4096] [--skip dense] [--reps 3] [--host-roots 40] [--out profiles/multihop_time.json]
     python tools/multihop_time.py --kernel-stats profiles/multihop_c_kernel_stats.csv
 """
 import argparse
@@ -236,6 +241,34 @@ def case_c(reps, roots=4096, hops=4, beam=8, skip="dense"):
             "mean_best_logp": float(logp[:, 0].mean()), "first_call_hops1_incl_step_tables_s": t_tab, **rec}
 
 
+def case_d(reps, roots=4096, hops=8, samples=256, skip="dense", d_roots=None):
+    net, inputs, targets, sc, E_lookup, last, nb, cx = _big(roots)
+    R = len(last) if not d_roots else min(int(d_roots), len(last))
+    if R < len(last):
+        inputs = [inputs[0], np.asarray(last)[:R], inputs[2].select(np.arange(R))]
+    net.multi_hop_skip = _modes(skip)[0]
+    t_tab = time.perf_counter()
+    net.sample_paths(inputs, 1, 1, nbrhoods=sc.nbrhoods, E_lookup=E_lookup)            # builds and caches the step tables
+    t_tab = time.perf_counter() - t_tab
+    _say("step tables %.1f s; counting the levels" % t_tab)
+    levels, _ = net._sample_levels(inputs, hops, samples, 0, 1.0, sc.nbrhoods, E_lookup)
+    entries = [int(l[1].shape[0]) for l in levels]                                     # level 0 .. hops; the last one is not evaluated
+    live = [int((l[2] >= 0).sum().item()) for l in levels]
+    del levels
+    leaves = int(sum(entries[:hops]))
+    _say("entries per level %s; timing" % entries)
+    rec, res = _skip_runs(net, skip, reps, lambda: net.sample_paths(inputs, hops, samples, nbrhoods=sc.nbrhoods, E_lookup=E_lookup),
+                          leaves)
+    paths, logp = res[_modes(skip)[-1]]
+    if skip == "both":
+        rec["paths_equal"] = bool(np.array_equal(res["dense"][0], res["field"][0]))
+    return {"case": "d", "skip": skip, "n_edges": int(cx.n_edges), "roots": R, "hops": hops, "samples": samples,
+            "level_entries": entries, "level_live_samples": live,
+            "entries_per_sample": [e / max(s, 1) for e, s in zip(entries, live)], "leaves_evaluated": leaves,
+            "leaves_if_unmerged": int(sum(live[:hops])), "live_paths": int((paths[:, :, -1] >= 0).sum()),
+            "mean_logp": float(logp[np.isfinite(logp)].mean()), "first_call_hops1_incl_step_tables_s": t_tab, **rec}
+
+
 def kernel_shares(path):
     """Shares of kernel time from a `rocprofv3 --kernel-trace --stats` kernel table (Name, Calls, TotalDurationNs, ...): the forward
     kernels (the fused layer kernels `scn::fwd_*` and the readout) and every multi-hop kernel of csrc/scn_hops.hip by name."""
@@ -246,7 +279,7 @@ def kernel_shares(path):
     fwd = sum(t for n, _, t in rows if "scn::fwd_" in n or "scn::readout_fwd" in n)
     hops = {}
     for n, c, t in rows:
-        for k in ("beam_step", "hop_select", "tree_expand", "tree_copy_list", "tree_patch_list", "tree_copy", "tree_patch", "tree_target",
+        for k in ("sample_draw", "sample_expand", "beam_step", "hop_select", "tree_expand", "tree_copy_list", "tree_patch_list", "tree_copy", "tree_patch", "tree_target",
                   "field_mark", "field_hop", "field_count", "field_scan", "field_fill", "clear_list"):
             if k + "_kernel" in n:
                 hops[k] = {"calls": c, "total_ns": t, "share": t / total}
@@ -264,6 +297,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip", default="dense", choices=["dense", "field", "both"], help="multi_hop_skip of cases b and c")
     ap.add_argument("--host-roots", type=int, default=40)
+    ap.add_argument("--d-roots", type=int, default=0, help="case d on the first R roots of case b's (0: all of them)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-stats", default=None, help="a rocprofv3 kernel_stats.csv: print the shares of kernel time and exit")
     a = ap.parse_args()
@@ -280,6 +314,9 @@ def main():
         print(json.dumps(res[-1]), flush=True)
     if "c" in a.case:
         res.append(case_c(a.reps, skip=a.skip))
+        print(json.dumps(res[-1]), flush=True)
+    if "d" in a.case:
+        res.append(case_d(a.reps, skip=a.skip, d_roots=a.d_roots))
         print(json.dumps(res[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
