@@ -140,14 +140,7 @@ __global__ __launch_bounds__(FL_THREADS) void tree_copy_list_kernel(PlanDev P, W
         for (int i = threadIdx.x; i < total; i += FL_THREADS) {
             const int s = wl.slab[k0 + i / rows], r = row0 + i % rows;
             if (s < 0 || s >= n_slabs || r >= n_rows) continue;
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int64_t l = (int64_t)s * 4 + q;
-                const int rt = l < n_leaves ? root[l] : -1;
-                v[q] = (rt >= 0 && rt < n_roots) ? root_x[((size_t)(rt >> 2) * n_rows + r) * 4 + (rt & 3)] : 0.f;
-            }
-            *reinterpret_cast<float4*>(x + ((size_t)s * n_rows + r) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+            *reinterpret_cast<float4*>(x + ((size_t)s * n_rows + r) * 4) = scn::root_columns(s, r, n_leaves, root, n_roots, root_x, n_rows);
         }
     }
 }

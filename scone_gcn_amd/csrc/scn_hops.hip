@@ -24,28 +24,96 @@ __device__ __forceinline__ int masked_argmax(const float* __restrict__ row, int 
     return best;
 }
 
-__global__ __launch_bounds__(256) void hop_select_kernel(int n, int d, const float* __restrict__ logp, const int32_t* __restrict__ n_limit,
-                                                         float fill, const int32_t* __restrict__ deg, int32_t* cur, int32_t* last, int n_nodes,
-                                                         const int32_t* __restrict__ step_node, const int32_t* __restrict__ step_edge,
-                                                         const float* __restrict__ step_sign, int n_rows, int ns, float* x, int advance,
-                                                         int32_t* __restrict__ choice, int32_t* __restrict__ next_node, int32_t* err) {
+// The step tables of a call (multihop.StepTables: node / edge / sign [n_nodes, d] and deg [n_nodes]) and the bounds a lookup is held to.
+// Each kernel used to clamp a degree its own way -- not at all, at both ends, at the upper end only; they agree wherever
+// 0 <= deg <= d, which is every table the host builds (and a slot index never reaches d), so the one clamp of live_deg serves all.
+// A wrapper whose ABI has no deg, edge, sign or n_rows fills that member with NULL / 0: its kernel then must not call the method
+// that reads it (live_deg reads deg; no_edge reads edge, node and n_rows).  tree_target calls live_deg only, sample_draw both but
+// never reads sign, sample_expand neither.
+struct StepTab {
+    const int32_t* deg;
+    const int32_t* node;
+    const int32_t* edge;
+    const float* sign;
+    int n_nodes, d, n_rows;
+    // the slots of node v that are candidates: 0 for a node outside [0, n_nodes) (a dead entry), else deg[v] clamped to [0, d]
+    __device__ __forceinline__ int live_deg(int v) const {
+        if (v < 0 || v >= n_nodes) return 0;
+        const int dv = deg[v];
+        return dv < 0 ? 0 : (dv > d ? d : dv);
+    }
+    // slot j of the live node v has no edge (KeyError in the reference)
+    __device__ __forceinline__ bool no_edge(int v, int j) const {
+        const size_t k = (size_t)v * d + j;
+        return edge[k] < 0 || edge[k] >= n_rows || node[k] < 0;
+    }
+};
+
+// The entries of the next level, as the callers allocate them: parent / slot / count where the decoder keeps them, no paths on a final level
+struct Children {
+    int32_t* root;
+    int32_t* node;
+    float* score;
+    int32_t* parent;
+    int32_t* slot;
+    int32_t* count;
+    int32_t* path_row;
+    float* path_sign;
+};
+
+// Child c: the entry itself (by lane 0), then the h path entries of its parent (from src of path_row / path_sign) with (edge, sign)
+// appended -- by one thread, or lane-strided by the `stride` lanes of a wave that owns the child
+__device__ __forceinline__ void write_child(const Children& ch, size_t c, int root, int node, float score, int parent, int slot, int count,
+                                            const int32_t* __restrict__ path_row, const float* __restrict__ path_sign, size_t src, int h,
+                                            int edge, float sign, int lane = 0, int stride = 1) {
+    if (lane == 0) {
+        ch.root[c] = root;
+        ch.node[c] = node;
+        ch.score[c] = score;
+        if (ch.parent) ch.parent[c] = parent;
+        if (ch.slot) ch.slot[c] = slot;
+        if (ch.count) ch.count[c] = count;
+    }
+    if (!ch.path_row) return;
+    const size_t dst = c * (size_t)(h + 1);
+    for (int q = lane; q <= h; q += stride) {
+        ch.path_row[dst + q] = q < h ? path_row[src + q] : edge;
+        ch.path_sign[dst + q] = q < h ? path_sign[src + q] : sign;
+    }
+}
+
+// child c of a beam that has fewer candidates than entries: dead
+__device__ __forceinline__ void write_dead_child(const Children& ch, size_t c, int h) {
+    ch.root[c] = -1;
+    ch.node[c] = -1;
+    ch.score[c] = -__builtin_inff();
+    ch.parent[c] = -1;
+    ch.slot[c] = -1;
+    if (!ch.path_row) return;
+    for (int q = 0; q <= h; ++q) {
+        ch.path_row[c * (size_t)(h + 1) + q] = -1;
+        ch.path_sign[c * (size_t)(h + 1) + q] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void hop_select_kernel(int n, StepTab tab, const float* __restrict__ logp,
+                                                         const int32_t* __restrict__ n_limit, float fill, int32_t* cur, int32_t* last, int ns,
+                                                         float* x, int advance, int32_t* __restrict__ choice,
+                                                         int32_t* __restrict__ next_node, int32_t* err) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int v = cur[i];
-    const bool v_ok = v >= 0 && v < n_nodes;
-    const int lim = n_limit ? n_limit[i] : (v_ok ? deg[v] : 0);
-    const int c = masked_argmax(logp + (size_t)i * d, d, lim, fill);
+    const int v = cur[i], d = tab.d;
+    const int c = masked_argmax(logp + (size_t)i * d, d, n_limit ? n_limit[i] : tab.live_deg(v), fill);
     choice[i] = c;
-    if (!step_edge) return;                                          // final hop of the accuracy: no lookup (STM:121-122)
-    const size_t k = (size_t)v * d + c;
-    const int e = v_ok ? step_edge[k] : -1;
-    const int u = v_ok ? step_node[k] : -1;
-    if (e < 0 || e >= n_rows || u < 0) {                              // the pair has no edge (KeyError in the reference): nothing written
+    if (!tab.edge) return;                                           // final hop of the accuracy: no lookup (STM:121-122)
+    if (v < 0 || v >= tab.n_nodes || tab.no_edge(v, c)) {             // the pair has no edge: nothing written
         atomicMin(err, i);
         return;
     }
+    const size_t k = (size_t)v * d + c;
+    const int u = tab.node[k];
     if (next_node) next_node[i] = u;
-    if (x) x[((size_t)(i / ns) * n_rows + e) * ns + (i % ns)] = step_sign[k];     // SET, not add (STM:149-150)
+    if (x) x[((size_t)(i / ns) * tab.n_rows + tab.edge[k]) * ns + (i % ns)] = tab.sign[k];     // SET, not add (STM:149-150)
     if (advance) {
         cur[i] = u;
         last[i] = u;
@@ -53,37 +121,25 @@ __global__ __launch_bounds__(256) void hop_select_kernel(int n, int d, const flo
 }
 
 // one thread per (leaf, slot): the children of leaf l go to offset[l] + j, leaf-major and slot-minor (STM:176-198)
-__global__ __launch_bounds__(256) void tree_expand_kernel(int n_leaves, int h, int d, const int32_t* __restrict__ root,
+__global__ __launch_bounds__(256) void tree_expand_kernel(int n_leaves, int h, StepTab tab, const int32_t* __restrict__ root,
                                                           const int32_t* __restrict__ node, const float* __restrict__ prob,
                                                           const int32_t* __restrict__ path_row, const float* __restrict__ path_sign,
                                                           const float* __restrict__ logp, const int32_t* __restrict__ offset,
-                                                          const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
-                                                          const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
-                                                          int n_rows, int n_children, int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
-                                                          float* __restrict__ c_prob, int32_t* __restrict__ c_path_row,
-                                                          float* __restrict__ c_path_sign, int32_t* err) {
+                                                          int n_children, Children ch, int32_t* err) {
+    const int d = tab.d;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)n_leaves * d) return;
     const int l = (int)(t / d), j = (int)(t % d);
     const int v = node[l];
-    if (v < 0 || v >= n_nodes || j >= deg[v]) return;
+    if (j >= tab.live_deg(v)) return;
     const size_t k = (size_t)v * d + j;
-    const int e = step_edge[k];
-    const int u = step_node[k];
     const int c = offset[l] + j;
-    if (e < 0 || e >= n_rows || u < 0 || c < 0 || c >= n_children) {
+    if (tab.no_edge(v, j) || c < 0 || c >= n_children) {
         atomicMin(err, (int)t);
         return;
     }
-    c_root[c] = root[l];
-    c_node[c] = u;
-    c_prob[c] = prob[l] * expf(logp[(size_t)l * d + j]);
-    for (int q = 0; q < h; ++q) {
-        c_path_row[(size_t)c * (h + 1) + q] = path_row[(size_t)l * h + q];
-        c_path_sign[(size_t)c * (h + 1) + q] = path_sign[(size_t)l * h + q];
-    }
-    c_path_row[(size_t)c * (h + 1) + h] = e;
-    c_path_sign[(size_t)c * (h + 1) + h] = step_sign[k];
+    write_child(ch, c, root[l], tab.node[k], prob[l] * expf(logp[(size_t)l * d + j]), 0, 0, 0, path_row, path_sign, (size_t)l * h, h,
+                tab.edge[k], tab.sign[k]);
 }
 
 // one thread per (slab, row) of the output: the ns = 4 leaves' root columns, one 16-byte store
@@ -92,14 +148,7 @@ __global__ __launch_bounds__(256) void tree_copy_kernel(int n_leaves, int64_t n_
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_items; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s = t / n_rows;
         const int r = (int)(t % n_rows);
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t l = s * 4 + q;
-            const int rt = l < n_leaves ? root[l] : -1;
-            v[q] = (rt >= 0 && rt < n_roots) ? root_x[((size_t)(rt >> 2) * n_rows + r) * 4 + (rt & 3)] : 0.f;
-        }
-        *reinterpret_cast<float4*>(x + (size_t)t * 4) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(x + (size_t)t * 4) = scn::root_columns(s, r, n_leaves, root, n_roots, root_x, n_rows);
     }
 }
 
@@ -116,21 +165,19 @@ __global__ __launch_bounds__(256) void tree_patch_kernel(int n_leaves, int h, co
 
 // one wave per root over its contiguous leaves; lane partial sums in a fixed order, then a fixed shuffle tree: bitwise repeatable
 __global__ __launch_bounds__(64) void tree_target_kernel(int n_roots, const int32_t* __restrict__ leaf_ptr, const int32_t* __restrict__ node,
-                                                         const float* __restrict__ prob, const float* __restrict__ logp, int d,
-                                                         const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
+                                                         const float* __restrict__ prob, const float* __restrict__ logp, StepTab tab,
                                                          const int32_t* __restrict__ target, float* __restrict__ out) {
     const int r = blockIdx.x;
-    const int lane = threadIdx.x;
+    const int lane = threadIdx.x, d = tab.d;
     if (r >= n_roots) return;
     const int tg = target[r];
     float s = 0.f;
     int cnt = 0;
     for (int l = leaf_ptr[r] + lane; l < leaf_ptr[r + 1]; l += 64) {
         const int v = node[l];
-        if (v < 0 || v >= n_nodes) continue;
-        const int dv = deg[v];
+        const int dv = tab.live_deg(v);
         for (int j = 0; j < dv; ++j) {
-            if (step_node[(size_t)v * d + j] == tg) {
+            if (tab.node[(size_t)v * d + j] == tg) {
                 s += prob[l] * expf(logp[(size_t)l * d + j]);
                 ++cnt;
             }
@@ -160,27 +207,20 @@ __device__ __forceinline__ unsigned long long beam_key(float s, int c) {
 
 // one wave per root.  Round o finds, lane-strided over the root's w_in * d candidates and then by a shuffle butterfly, the highest key
 // strictly below round o - 1's winner: no bookkeeping, any d, and nothing depends on the order lanes or blocks run in.
-__global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int h, int d, const int32_t* __restrict__ node,
+__global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int h, StepTab tab, const int32_t* __restrict__ node,
                                                        const float* __restrict__ score, const int32_t* __restrict__ path_row,
-                                                       const float* __restrict__ path_sign, const float* __restrict__ logp,
-                                                       const int32_t* __restrict__ deg, int n_nodes, const int32_t* __restrict__ step_node,
-                                                       const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
-                                                       int n_rows, int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
-                                                       float* __restrict__ c_score, int32_t* __restrict__ c_parent,
-                                                       int32_t* __restrict__ c_slot, int32_t* __restrict__ c_path_row,
-                                                       float* __restrict__ c_path_sign, int32_t* err) {
+                                                       const float* __restrict__ path_sign, const float* __restrict__ logp, Children ch,
+                                                       int32_t* err) {
     __shared__ int s_node[SCN_BEAM_MAX];
     __shared__ int s_lim[SCN_BEAM_MAX];              // slots of entry k that are candidates: deg[node], 0 for a dead entry
     __shared__ float s_score[SCN_BEAM_MAX];
     const int r = blockIdx.x;
-    const int lane = threadIdx.x;
+    const int lane = threadIdx.x, d = tab.d;
     const size_t in0 = (size_t)r * w_in;
     for (int k = lane; k < w_in; k += 64) {
         const int v = node[in0 + k];
-        const bool live = v >= 0 && v < n_nodes;
-        const int dv = live ? deg[v] : 0;
-        s_node[k] = live ? v : -1;
-        s_lim[k] = dv < 0 ? 0 : (dv > d ? d : dv);
+        s_node[k] = (v >= 0 && v < tab.n_nodes) ? v : -1;
+        s_lim[k] = tab.live_deg(v);
         s_score[k] = score[in0 + k];
     }
     __syncthreads();
@@ -189,11 +229,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int 
     // candidate c = k * d + j of lane `lane` advances by 64: (k, j) += (64 / d, 64 % d) with one carry
     const int k0 = lane / d, j0 = lane % d, dk = 64 / d, dj = 64 % d;
     for (int c = lane, k = k0, j = j0; c < n_cand; c += 64) {
-        if (j < s_lim[k]) {
-            const size_t t = (size_t)s_node[k] * d + j;
-            const int e = step_edge[t];
-            if (e < 0 || e >= n_rows || step_node[t] < 0) atomicMin(err, (int)(in0 * d) + c);
-        }
+        if (j < s_lim[k] && tab.no_edge(s_node[k], j)) atomicMin(err, (int)(in0 * d) + c);
         k += dk;
         j += dj;
         if (j >= d) {
@@ -228,34 +264,10 @@ __global__ __launch_bounds__(64) void beam_step_kernel(int w_in, int w_out, int 
         const int c = 0x7fffffff - (int)(unsigned)(best & 0xffffffffu);
         const int k = c / d, j = c - k * d;
         const size_t t = (size_t)s_node[k] * d + j;
-        if (lane == 0) {
-            c_root[out0 + o] = r;
-            c_node[out0 + o] = step_node[t];
-            c_score[out0 + o] = s_score[k] + lp[c];
-            c_parent[out0 + o] = k;
-            c_slot[out0 + o] = j;
-        }
-        if (c_path_row) {
-            const size_t dst = (out0 + o) * (size_t)(h + 1), src = (in0 + k) * (size_t)h;
-            for (int q = lane; q <= h; q += 64) {
-                c_path_row[dst + q] = q < h ? path_row[src + q] : step_edge[t];
-                c_path_sign[dst + q] = q < h ? path_sign[src + q] : step_sign[t];
-            }
-        }
+        write_child(ch, out0 + o, r, tab.node[t], s_score[k] + lp[c], k, j, 0, path_row, path_sign, (in0 + k) * (size_t)h, h, tab.edge[t],
+                    tab.sign[t], lane, 64);
     }
-    for (int p = o + lane; p < w_out; p += 64) {                          // fewer than w_out candidates: the rest are dead
-        c_root[out0 + p] = -1;
-        c_node[out0 + p] = -1;
-        c_score[out0 + p] = -__builtin_inff();
-        c_parent[out0 + p] = -1;
-        c_slot[out0 + p] = -1;
-        if (c_path_row) {
-            for (int q = 0; q <= h; ++q) {
-                c_path_row[(out0 + p) * (size_t)(h + 1) + q] = -1;
-                c_path_sign[(out0 + p) * (size_t)(h + 1) + q] = 0.f;
-            }
-        }
-    }
+    for (int p = o + lane; p < w_out; p += 64) write_dead_child(ch, out0 + p, h);      // fewer than w_out candidates: the rest are dead
 }
 
 
@@ -294,16 +306,14 @@ __device__ __forceinline__ void sample_range(const int32_t* __restrict__ leaf_pt
 }
 
 // one workgroup per root: the missing-edge word over every live (k, j), then every sample's pick and the bitmap of the used (k, j)
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_samples, int max_entries, int n_leaves, int h, int d,
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_samples, int max_entries, int n_leaves, int h,
                                                                      uint64_t seed, float inv_T, const int32_t* __restrict__ leaf_ptr,
                                                                      const int32_t* __restrict__ node, const float* __restrict__ logp,
-                                                                     const int32_t* __restrict__ entry_of, const int32_t* __restrict__ deg,
-                                                                     int n_nodes, const int32_t* __restrict__ step_node,
-                                                                     const int32_t* __restrict__ step_edge, int n_rows,
+                                                                     const int32_t* __restrict__ entry_of, StepTab tab,
                                                                      int32_t* __restrict__ pick, int32_t* __restrict__ n_child, int32_t* err) {
     __shared__ unsigned s_bits[SAMPLE_WORDS];
     __shared__ int s_total;
-    const int r = blockIdx.x, t = threadIdx.x;
+    const int r = blockIdx.x, t = threadIdx.x, d = tab.d;
     int l0, ne;
     sample_range(leaf_ptr, r, n_leaves, max_entries, l0, ne);
     const int n_pairs = ne * d, n_words = (n_pairs + 31) >> 5;
@@ -312,10 +322,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_sampl
     for (int c = t; c < n_pairs; c += SAMPLE_THREADS) {
         const int k = c / d, j = c - k * d;
         const int v = node[l0 + k];
-        if (v < 0 || v >= n_nodes || j >= deg[v]) continue;
-        const size_t q = (size_t)v * d + j;
-        const int e = step_edge[q];
-        if (e < 0 || e >= n_rows || step_node[q] < 0) atomicMin(err, (l0 + k) * d + j);
+        if (j < tab.live_deg(v) && tab.no_edge(v, j)) atomicMin(err, (l0 + k) * d + j);
     }
     __syncthreads();
     const size_t s0 = (size_t)r * n_samples;
@@ -323,9 +330,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_sampl
         const int k = entry_of[s0 + s];
         int p = -1;
         if (k >= 0 && k < ne) {
-            const int v = node[l0 + k];
-            const int dv = (v >= 0 && v < n_nodes) ? deg[v] : 0;
-            const int lim = dv > d ? d : dv;
+            const int lim = tab.live_deg(node[l0 + k]);
             if (lim > 0) {
                 const float u = scn::sample_uniform(seed, r, s, h);
                 p = k * d + sample_slot(logp + (size_t)(l0 + k) * d, d, lim, inv_T, u);
@@ -346,23 +351,17 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(int n_sampl
 
 // one workgroup per root: the bitmap again from the picks, its running population count, then one child per set bit at
 // child_ptr[r] + rank (ascending pick = lower parent, then lower slot) and every sample's rank
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_expand_kernel(int n_samples, int max_entries, int n_leaves, int h, int d,
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_expand_kernel(int n_samples, int max_entries, int n_leaves, int h, StepTab tab,
                                                                        const int32_t* __restrict__ leaf_ptr, const int32_t* __restrict__ node,
                                                                        const float* __restrict__ score, const int32_t* __restrict__ path_row,
                                                                        const float* __restrict__ path_sign, const float* __restrict__ logp,
                                                                        const int32_t* __restrict__ pick, const int32_t* __restrict__ child_ptr,
-                                                                       int n_children, int n_nodes, const int32_t* __restrict__ step_node,
-                                                                       const int32_t* __restrict__ step_edge, const float* __restrict__ step_sign,
-                                                                       int32_t* __restrict__ c_root, int32_t* __restrict__ c_node,
-                                                                       float* __restrict__ c_score, int32_t* __restrict__ c_parent,
-                                                                       int32_t* __restrict__ c_slot, int32_t* __restrict__ c_count,
-                                                                       int32_t* __restrict__ c_path_row, float* __restrict__ c_path_sign,
-                                                                       int32_t* __restrict__ entry_of_next) {
+                                                                       int n_children, Children ch, int32_t* __restrict__ entry_of_next) {
     __shared__ unsigned s_bits[SAMPLE_WORDS];
     __shared__ int s_before[SAMPLE_WORDS];           // set bits in the words before this one
     __shared__ int s_count[SCN_SAMPLE_MAX];          // samples of the child of each rank (children <= samples)
     __shared__ int s_wave[SAMPLE_THREADS / 64];
-    const int r = blockIdx.x, t = threadIdx.x;
+    const int r = blockIdx.x, t = threadIdx.x, d = tab.d, n_nodes = tab.n_nodes;
     int l0, ne;
     sample_range(leaf_ptr, r, n_leaves, max_entries, l0, ne);
     const int n_pairs = ne * d, n_words = (n_pairs + 31) >> 5;
@@ -421,21 +420,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_expand_kernel(int n_sam
             const int c = c0 + rank;
             if (c < 0 || c >= n_children) continue;                      // child_ptr is not the scan of the draw's n_child: guarded only
             const size_t q = (size_t)node[l0 + k] * d + j;
-            c_root[c] = r;
-            c_node[c] = step_node[q];
-            c_score[c] = score[l0 + k] + logp[(size_t)(l0 + k) * d + j];
-            c_parent[c] = k;
-            c_slot[c] = j;
-            c_count[c] = s_count[rank];
-            if (c_path_row) {
-                const size_t dst = (size_t)c * (h + 1), src = (size_t)(l0 + k) * h;
-                for (int i = 0; i < h; ++i) {
-                    c_path_row[dst + i] = path_row[src + i];
-                    c_path_sign[dst + i] = path_sign[src + i];
-                }
-                c_path_row[dst + h] = step_edge[q];
-                c_path_sign[dst + h] = step_sign[q];
-            }
+            write_child(ch, c, r, tab.node[q], score[l0 + k] + logp[(size_t)(l0 + k) * d + j], k, j, s_count[rank], path_row, path_sign,
+                        (size_t)(l0 + k) * h, h, tab.edge[q], tab.sign[q]);
         }
     }
 }
@@ -453,8 +439,9 @@ int scn_hop_select(int32_t n, int32_t d, const float* logp, const int32_t* n_lim
     if (advance && (!step_edge || !last)) return SCN_ERR_BAD_ARG;
     if (x && !step_edge) return SCN_ERR_BAD_ARG;
     if (n == 0) return SCN_OK;
-    hipLaunchKernelGGL(hop_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d, logp, n_limit,
-                       fill, deg, cur, last, n_nodes, step_node, step_edge, step_sign, n_rows, ns, x, advance, choice, next_node, err);
+    hipLaunchKernelGGL(hop_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                       StepTab{deg, step_node, step_edge, step_sign, n_nodes, d, n_rows}, logp, n_limit, fill, cur, last, ns, x, advance,
+                       choice, next_node, err);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -471,9 +458,9 @@ int scn_tree_expand(int32_t n_leaves, int32_t h, int32_t d, const int32_t* root,
     if (h > 0 && (!path_row || !path_sign)) return SCN_ERR_BAD_ARG;
     if (n_children > 0 && (!c_root || !c_node || !c_prob || !c_path_row || !c_path_sign)) return SCN_ERR_BAD_ARG;
     const int64_t items = (int64_t)n_leaves * d;
-    hipLaunchKernelGGL(tree_expand_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_leaves, h, d, root,
-                       node, prob, path_row, path_sign, logp, offset, deg, n_nodes, step_node, step_edge, step_sign, n_rows, n_children,
-                       c_root, c_node, c_prob, c_path_row, c_path_sign, err);
+    hipLaunchKernelGGL(tree_expand_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_leaves, h,
+                       StepTab{deg, step_node, step_edge, step_sign, n_nodes, d, n_rows}, root, node, prob, path_row, path_sign, logp, offset,
+                       n_children, Children{c_root, c_node, c_prob, nullptr, nullptr, nullptr, c_path_row, c_path_sign}, err);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -505,7 +492,7 @@ int scn_tree_target(int32_t n_roots, const int32_t* leaf_ptr, const int32_t* nod
     if (n_roots == 0) return SCN_OK;
     if (!leaf_ptr || !node || !prob || !logp || !deg || !step_node || !target || !out) return SCN_ERR_BAD_ARG;
     hipLaunchKernelGGL(tree_target_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, n_roots, leaf_ptr, node, prob, logp,
-                       d, deg, n_nodes, step_node, target, out);
+                       StepTab{deg, step_node, nullptr, nullptr, n_nodes, d, 0}, target, out);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -522,9 +509,9 @@ int scn_beam_step(int32_t n_roots, int32_t w_in, int32_t w_out, int32_t h, int32
     if (!node || !score || !logp || !deg || !step_node || !step_edge || !step_sign || !err) return SCN_ERR_BAD_ARG;
     if (!c_root || !c_node || !c_score || !c_parent || !c_slot) return SCN_ERR_BAD_ARG;
     if (c_path_row && (!c_path_sign || (h > 0 && (!path_row || !path_sign)))) return SCN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, w_in, w_out, h, d, node, score,
-                       path_row, path_sign, logp, deg, n_nodes, step_node, step_edge, step_sign, n_rows, c_root, c_node, c_score,
-                       c_parent, c_slot, c_path_row, c_path_sign, err);
+    hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)n_roots), dim3(64), 0, (hipStream_t)stream, w_in, w_out, h,
+                       StepTab{deg, step_node, step_edge, step_sign, n_nodes, d, n_rows}, node, score, path_row, path_sign, logp,
+                       Children{c_root, c_node, c_score, c_parent, c_slot, nullptr, c_path_row, c_path_sign}, err);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -554,8 +541,8 @@ int scn_sample_draw(int32_t n_roots, int32_t n_samples, int32_t max_entries, int
     if (n_roots == 0) return SCN_OK;
     if (!leaf_ptr || !node || !logp || !entry_of || !deg || !step_node || !step_edge || !pick || !n_child || !err) return SCN_ERR_BAD_ARG;
     hipLaunchKernelGGL(sample_draw_kernel, dim3((unsigned)n_roots), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, n_samples, max_entries,
-                       n_leaves, h, d, seed, inv_T, leaf_ptr, node, logp, entry_of, deg, n_nodes, step_node, step_edge, n_rows, pick,
-                       n_child, err);
+                       n_leaves, h, seed, inv_T, leaf_ptr, node, logp, entry_of, StepTab{deg, step_node, step_edge, nullptr, n_nodes, d, n_rows},
+                       pick, n_child, err);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -575,9 +562,9 @@ int scn_sample_expand(int32_t n_roots, int32_t n_samples, int32_t max_entries, i
     if (n_children > 0 && (!c_root || !c_node || !c_score || !c_parent || !c_slot || !c_count)) return SCN_ERR_BAD_ARG;
     if (c_path_row && (!c_path_sign || (h > 0 && (!path_row || !path_sign)))) return SCN_ERR_BAD_ARG;
     hipLaunchKernelGGL(sample_expand_kernel, dim3((unsigned)n_roots), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, n_samples,
-                       max_entries, n_leaves, h, d, leaf_ptr, node, score, path_row, path_sign, logp, pick, child_ptr, n_children,
-                       n_nodes, step_node, step_edge, step_sign, c_root, c_node, c_score, c_parent, c_slot, c_count, c_path_row,
-                       c_path_sign, entry_of_next);
+                       max_entries, n_leaves, h, StepTab{nullptr, step_node, step_edge, step_sign, n_nodes, d, 0}, leaf_ptr, node, score,
+                       path_row, path_sign, logp, pick, child_ptr, n_children,
+                       Children{c_root, c_node, c_score, c_parent, c_slot, c_count, c_path_row, c_path_sign}, entry_of_next);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

@@ -153,6 +153,20 @@ __host__ __device__ __forceinline__ float sample_uniform(uint64_t seed, int32_t 
     return (float)(out[0] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
 }
 
+// Row r of slab s of a tree level's input: the root columns of its ns = 4 leaves 4 s .. 4 s + 3 (0 past the last leaf and for a leaf
+// without a root), as the one 16-byte store the slab builders of scn_hops.hip and scn_field.hip make of them.
+__device__ __forceinline__ float4 root_columns(int64_t s, int r, int n_leaves, const int32_t* __restrict__ root, int n_roots,
+                                               const float* __restrict__ root_x, int n_rows) {
+    float v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t l = s * 4 + q;
+        const int rt = l < n_leaves ? root[l] : -1;
+        v[q] = (rt >= 0 && rt < n_roots) ? root_x[((size_t)(rt >> 2) * n_rows + r) * 4 + (rt & 3)] : 0.f;
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
 struct Group {
     int32_t n_cols = 0, identity = 0, n_vals = 0;
     int64_t nnz = 0;

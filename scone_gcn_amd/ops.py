@@ -1861,81 +1861,10 @@ def default_device():
 
 
 # ----------------------------------------------------------------------------------------------
-# multi-hop prediction (STM:110-206): step tables and the forward-only level driver (csrc/scn_hops.hip does the steps between)
+# multi-hop prediction (multihop.py): the plan-level pieces -- the forward-only call, its micro-batch rule and the field-of-view lists
 # ----------------------------------------------------------------------------------------------
 
 INT32_MAX = (1 << 31) - 1
-_STEP_TABLES = {}
-
-
-class StepTables:
-    """Where a step from node v through slot j leads, as scn_hop_select / scn_tree_expand read it (include/scone_hip.h):
-    node / edge / sign [V, D] (edge = DEVICE row, -1 where the pair has no edge) and deg [V], on the device and on the host.
-    rule "binary" (STM:139-147): slot j of nbrhoods[v] as it is; +1 on E_lookup[(v, u)] if that key exists, else -1 on
-    E_lookup[(u, v)].  rule "dist" (STM:160, 176-187): the real neighbours of v left-aligned (the -1 padding dropped), -1 / +1 on
-    E_lookup[sorted(v, u)] by whether v > u."""
-
-    def __init__(self, nbrhoods, E_lookup, edge_perm, rule, device):
-        nb = np.asarray(nbrhoods, np.int64)
-        if nb.ndim != 2:
-            raise ValueError("nbrhoods must be a (V, D) table padded with -1")
-        V, D = nb.shape
-        if rule == "dist":
-            real = nb >= 0
-            order = np.argsort(~real, axis=1, kind="stable")
-            nb = np.where(np.take_along_axis(real, order, 1), np.take_along_axis(nb, order, 1), -1)
-        elif rule != "binary":
-            raise ValueError("rule must be 'binary' or 'dist'")
-        n = len(E_lookup)
-        keys = np.fromiter((c for k in E_lookup.keys() for c in k), np.int64, 2 * n).reshape(n, 2)
-        vals = np.fromiter(E_lookup.values(), np.int64, n)
-        M = int(max(V, keys.max() + 1 if n else 0, 1))
-        code = keys[:, 0] * M + keys[:, 1]
-        srt = np.argsort(code, kind="stable")
-        code, vals = code[srt], vals[srt]
-
-        def lookup(a, b):                                       # E_lookup[(a, b)] elementwise, -1 where the key is missing
-            if n == 0:
-                return np.full(np.shape(a), -1, np.int64)
-            ok = (a >= 0) & (b >= 0) & (a < M) & (b < M)
-            c = np.where(ok, a * M + b, -1)
-            pos = np.minimum(np.searchsorted(code, c), n - 1)
-            return np.where(ok & (code[pos] == c), vals[pos], -1)
-        v = np.broadcast_to(np.arange(V, dtype=np.int64)[:, None], nb.shape)
-        if rule == "binary":
-            fwd, bwd = lookup(v, nb), lookup(nb, v)
-            edge = np.where(fwd >= 0, fwd, bwd)
-            sign = np.where(fwd >= 0, 1.0, -1.0)
-        else:
-            edge = lookup(np.minimum(v, nb), np.maximum(v, nb))
-            sign = np.where(v < nb, 1.0, -1.0)
-        edge = np.where(nb >= 0, edge, -1)
-        E = len(edge_perm)
-        if np.any(edge >= E):
-            raise ValueError("E_lookup holds an edge index outside the complex's %d edges" % E)
-        row = np.where(edge >= 0, np.asarray(edge_perm)[np.maximum(edge, 0)], -1)
-        self.rule, self.n_nodes, self.width = rule, V, D
-        self.h_node, self.h_edge = nb, row
-        self.h_deg = (nb >= 0).sum(axis=1)
-        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(device)
-        self.node, self.edge = to(nb, np.int32), to(row, np.int32)
-        self.sign = to(np.where(edge >= 0, sign, 0.0), np.float32)
-        self.deg = to(self.h_deg, np.int32)
-
-
-def step_tables(plan, nbrhoods, E_lookup, rule):
-    """StepTables of (plan, nbrhoods, E_lookup, rule), cached on the objects' identity (treated as immutable while cached)."""
-    key = (id(plan), id(nbrhoods), id(E_lookup), rule)
-    hit = _STEP_TABLES.get(key)
-    if hit is not None and hit[0] is nbrhoods and hit[1] is E_lookup and hit[2] is plan:
-        return hit[3]
-    tab = StepTables(nbrhoods, E_lookup, plan.layout.perm[1], rule, plan.device)
-    if tab.width != plan.max_deg:
-        raise ValueError("nbrhoods has %d slots, the model's readout %d" % (tab.width, plan.max_deg))
-    if len(_STEP_TABLES) >= 8:
-        _STEP_TABLES.pop(next(iter(_STEP_TABLES)))
-    _STEP_TABLES[key] = (nbrhoods, E_lookup, plan, tab)
-    return tab
 
 
 def forward_micro_batch(plan, weights, n):
@@ -1997,38 +1926,3 @@ def forward_logp(plan, x, last_dev, weights, activity=None):
         logp, saved = plan.forward(x, last_dev, weights)
         del saved
     return logp
-
-
-def tree_level_logp(plan, weights, root_x, n_roots, root, node, path_row, path_sign, mb, field_node=None, fractions=None):
-    """Log-probabilities [L, D] of the L leaves of one tree level: per chunk of mb leaves, scn_tree_slabs builds the input slabs
-    from the resident root slabs and the leaves' path entries, and the dense forward reads them with the leaves' nodes as last
-    nodes.  field_node (the leaves' nodes, -1 for a dead entry): per chunk the field-of-view lists of its leaves (field_activity);
-    scn_tree_slabs_list then fills only the listed items of the scratch input and the forward computes only its listed items.
-    fractions: a list that collects every chunk's active fractions."""
-    lib = _lib.load()
-    L, h = int(root.shape[0]), int(path_row.shape[1])
-    E = root_x.shape[1]
-    mb = min(mb, pad_count(L))
-    n_layers = (len(weights) - 1) // 3
-    x = torch.empty((mb // NS, E, NS, 1), device=root_x.device, dtype=torch.float32)
-    last = torch.zeros((mb,), device=root_x.device, dtype=torch.int32)
-    out = torch.empty((L, plan.max_deg), device=root_x.device, dtype=torch.float32)
-    for c0 in range(0, L, mb):
-        n = min(mb, L - c0)
-        S = pad_count(n) // NS
-        activity = field_activity(plan, field_node[c0:c0 + n], n, n_layers) if field_node is not None else None
-        rows = _dev(path_row[c0:c0 + n], torch.int32) if h else None
-        signs = _dev(path_sign[c0:c0 + n]) if h else None
-        if activity:
-            if fractions is not None:
-                fractions.append(activity["active_fraction"])
-            check(lib.scn_tree_slabs_list(plan.conv.handle, n, S, h, _dev(root[c0:c0 + n], torch.int32), rows, signs, n_roots, _dev(root_x),
-                                          E, NS, _dev(x), activity["input"].ref(), _stream()), "scn_tree_slabs_list")
-        else:
-            check(lib.scn_tree_slabs(n, S, h, _dev(root[c0:c0 + n], torch.int32), rows, signs, n_roots, _dev(root_x), E, NS, _dev(x),
-                                     _stream()), "scn_tree_slabs")
-        if n < S * NS:
-            last[n:S * NS].zero_()
-        last[:n].copy_(node[c0:c0 + n])
-        out[c0:c0 + n] = forward_logp(plan, x[:S], last[:S * NS], weights, activity)[:n]
-    return out

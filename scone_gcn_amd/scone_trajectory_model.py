@@ -18,9 +18,8 @@ import gc
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, multihop, ops
 from . import distributed as dp
-from .complex import Bconds
 from .synthetic_data_gen import SparseFlows
 from .trajectory_experiments import MODEL_ACT, MODEL_FUNCS, resolve_operands
 
@@ -356,101 +355,18 @@ class Scone_GCN():
         t, r = true_probs[m], random_probs[m]
         return float((np.sum(t > r) + 0.5 * np.sum(t == r)) / np.sum(m))
 
-    # ------------------------------------------------------------------ multi-hop prediction (STM:110-206)
-    # Each hop / tree level is ONE batched dense forward over all its trajectories / leaves (chunked by ops.forward_micro_batch, or
-    # by multi_hop_micro_batch when set); the steps between -- choose the next node, set the edge it crosses, build the children,
-    # reduce the leaf probabilities -- are csrc/scn_hops.hip.  The caller's flows are never written (the reference writes into them,
-    # STM:149-150) and the evaluation cache is not touched.
+    # ------------------------------------------------------------------ multi-hop prediction (STM:110-206): the decoders are multihop.py
     multi_hop_micro_batch = None
     _multi_hop_trace = None            # a list set on the instance collects what every hop / beam level saw (the tests' window)
     _multi_hop_fractions = None        # a list set on the instance collects the active fractions of every field-of-view forward
-
-    def _multihop_plan(self, inputs):
-        if self.model_type != 'bunch' and not isinstance(inputs[0], Bconds):
-            raise TypeError("multi-hop prediction needs the Bconds object of SimplicialComplex.bconds() (what data_setup returns) as "
-                            "the readout operand: a plain Bcond_func closure only knows the last nodes it has been probed at")
-        plan = self._plan(inputs)
-        if plan is None:
-            raise TypeError("multi-hop prediction runs the native model functions (scone_func / ebli_func / bunch_func) only")
-        return plan
-
-    def _mb(self, plan, n):
-        mb = self.multi_hop_micro_batch or ops.forward_micro_batch(plan, self.weights, n)
-        return max(ops.NS, ops.pad_count(int(mb)))
-
-    def _field(self, plan):
-        """Whether this call's forwards run on field-of-view lists (multi_hop_skip = "field" and the lists serve the model)."""
-        return self.multi_hop_skip == "field" and ops.field_served(plan, self.weights) is not None
-
-    def _forward_all(self, plan, x, last, mb, n=None):
-        """logp [S * NS, D] of all slabs x, mb trajectories per launch.  n: the first n trajectories are real and every launch
-        computes only what the readouts at their last nodes can see (field-of-view lists, built from `last` as it stands)."""
-        sl = mb // ops.NS
-        n_layers = (len(self.weights) - 1) // 3
-        outs = []
-        for s0 in range(0, x.shape[0], sl):
-            last_c = last[s0 * ops.NS:(s0 + sl) * ops.NS]
-            activity = None if n is None else ops.field_activity(plan, last_c, min(int(last_c.shape[0]), n - s0 * ops.NS), n_layers)
-            if activity and self._multi_hop_fractions is not None:
-                self._multi_hop_fractions.append(activity["active_fraction"])
-            outs.append(ops.forward_logp(plan, x[s0:s0 + sl], last_c, self.weights, activity))
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
-
-    def _rollout(self, inputs, cur_nodes, n_limit, hops, tab, advance, fill, trace=None):
-        """Greedy rollout on the device: returns (choices [N] of the final hop, nodes [hops, N] or None).  trace: list that gets, per
-        hop, (flows (N, E) in the caller's edge order, readout last nodes, logp (N, D)) as the forward saw them and the choices."""
-        plan = self._multihop_plan(inputs)
-        lib = _lib.load()
-        N = _n_samples(inputs[-1])
-        if len(np.asarray(inputs[1]).reshape(-1)) != N or any(a is not None and len(np.asarray(a).reshape(-1)) != N
-                                                              for a in (cur_nodes, n_limit)):
-            raise ValueError("last nodes and n_nbrs need one entry per trajectory of inputs (%d)" % N)
-        dev = plan.device
-        x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)               # a copy: the caller's flows stay as they are
-        last = ops._last_nodes_dev(inputs[1], x.shape[0] * ops.NS, dev)
-        cur = last[:N].clone() if cur_nodes is None else torch.from_numpy(np.ascontiguousarray(cur_nodes, np.int32)).to(dev)
-        lim = None if n_limit is None else torch.from_numpy(np.ascontiguousarray(n_limit, np.int32)).to(dev)
-        choice = torch.empty((N,), device=dev, dtype=torch.int32)
-        nodes = torch.empty((hops, N), device=dev, dtype=torch.int32) if advance else None
-        err = torch.empty((1,), device=dev, dtype=torch.int32)
-        mb = self._mb(plan, N)
-        field_n = N if self._field(plan) else None                           # the lists follow `last` at every hop; x stays dense
-        for h in range(hops):
-            logp = self._forward_all(plan, x, last, mb, field_n)
-            rec = None if trace is None else (ops.slabs_to_batch(x, plan.layout, 1, N)[:, :, 0].cpu().numpy(), last[:N].cpu().numpy(),
-                                              logp[:N].cpu().numpy())
-            final = h == hops - 1
-            lookup = advance or not final                                   # the accuracy's final hop looks nothing up (STM:121-122)
-            err.fill_(ops.INT32_MAX)
-            cur_h = cur.cpu().numpy() if lookup else None
-            _lib.check(lib.scn_hop_select(N, plan.max_deg, ops._dev(logp), ops._dev(lim, torch.int32) if lim is not None else None,
-                                          fill, ops._dev(tab.deg, torch.int32), ops._dev(cur, torch.int32), ops._dev(last, torch.int32),
-                                          tab.n_nodes, ops._dev(tab.node, torch.int32), ops._dev(tab.edge, torch.int32) if lookup else None,
-                                          ops._dev(tab.sign), plan.n_edges, ops.NS, None if final else ops._dev(x),
-                                          1 if (advance and not final) else 0, ops._dev(choice, torch.int32),
-                                          ops._dev(nodes[h], torch.int32) if advance else None, ops._dev(err, torch.int32),
-                                          ops._stream()), "scn_hop_select")
-            if rec is not None:
-                trace.append(rec + (choice.cpu().numpy(),))
-            if lookup:
-                i = int(err.item())
-                if i != ops.INT32_MAX:
-                    v = int(cur_h[i])
-                    c = int(choice[i].item())
-                    raise KeyError((v, int(tab.h_node[v, c]) if 0 <= v < tab.n_nodes else -1))
-        return choice.cpu().numpy(), (nodes.cpu().numpy().astype(np.int64) if advance else None)
 
     def multi_hop_accuracy_binary(self, shifts, inputs, y, mask, nbrhoods, E_lookup, last_nodes, n_nbrs, hops):
         """Accuracy of greedy multi-hop predictions (STM:110-152), quirks included: the current node (last_nodes) and the readout's
         last node (inputs[1]) never advance, and n_nbrs stays that of the original node.  Unlike the reference, the caller's flows
         are not written, and hops < 1 raises ValueError (the reference returns None).  A step across a pair without an edge raises
         KeyError((node, neighbour)) like the reference's E_lookup."""
-        if int(hops) < 1:
-            raise ValueError("hops must be at least 1")
-        plan = self._multihop_plan(inputs)
-        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
-        choice, _ = self._rollout(inputs, np.asarray(last_nodes), np.asarray(n_nbrs), int(hops), tab, advance=False, fill=-100.0,
-                                  trace=self._multi_hop_trace)
+        choice, _ = multihop.rollout(self, inputs, hops, nbrhoods, E_lookup, np.asarray(last_nodes), np.asarray(n_nbrs),
+                                     advance=False, fill=-100.0, defaults=False)
         m = np.asarray(mask) == 1
         target = np.argmax(np.asarray(y)[m], axis=1).reshape(-1)
         return float(np.average(choice[m] == target))
@@ -461,15 +377,7 @@ class Scone_GCN():
         log-probability lies below the reference's -100 fill).  Returns (N, hops) int64 node ids in the caller's
         numbering.  nbrhoods / E_lookup default to the complex's own (the Bconds object's; for bunch, the nbrhoods table of
         inputs[0] and the edges of the B1 pattern, keyed (lower id, higher id) as this project's data sets store them)."""
-        if int(hops) < 1:
-            raise ValueError("hops must be at least 1")
-        plan = self._multihop_plan(inputs)
-        if nbrhoods is None:
-            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
-        if E_lookup is None:
-            E_lookup = self._edge_lookup(inputs)
-        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
-        _, nodes = self._rollout(inputs, None, None, int(hops), tab, advance=True, fill=float("-inf"), trace=self._multi_hop_trace)
+        _, nodes = multihop.rollout(self, inputs, hops, nbrhoods, E_lookup)
         return nodes.T.copy()
 
     def predict_paths_beam(self, inputs, hops, beam, nbrhoods=None, E_lookup=None):
@@ -480,73 +388,7 @@ class Scone_GCN():
         entries per trajectory (W_0 = 1), a size the host knows without a copy back: one batched forward over N * W_h entries, then
         scn_beam_step keeps the best W_{h+1} children per trajectory (order: include/scone_hip.h).  beam = 1 is predict_paths, a
         beam as wide as the tree is the probability tree.  The error words of all levels are read once, at the end."""
-        hops, beam = int(hops), int(beam)
-        if hops < 1:
-            raise ValueError("hops must be at least 1")
-        if beam < 1 or beam > _lib.SCN_BEAM_MAX:
-            raise ValueError("beam must be between 1 and %d (SCN_BEAM_MAX)" % _lib.SCN_BEAM_MAX)
-        plan = self._multihop_plan(inputs)
-        if nbrhoods is None:
-            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
-        if E_lookup is None:
-            E_lookup = self._edge_lookup(inputs)
-        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
-        lib = _lib.load()
-        dev = plan.device
-        N, D = _n_samples(inputs[-1]), plan.max_deg
-        if len(np.asarray(inputs[1]).reshape(-1)) != N:
-            raise ValueError("last nodes need one entry per trajectory of inputs (%d)" % N)
-        if N * beam * D >= ops.INT32_MAX:
-            raise ValueError("beam level of %d x %d entries is too large" % (N, beam))
-        trace = self._multi_hop_trace
-        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)          # a copy: the caller's flows stay as they are
-        i32, f32 = (lambda *s: torch.empty(s, device=dev, dtype=torch.int32)), (lambda *s: torch.empty(s, device=dev, dtype=torch.float32))
-        p = lambda t: None if t is None else ops._dev(t, t.dtype)
-        W = 1
-        root = torch.arange(N, device=dev, dtype=torch.int32)
-        node = torch.from_numpy(np.ascontiguousarray(np.asarray(inputs[1]).reshape(-1), np.int32)).to(dev)
-        score = torch.zeros((N,), device=dev, dtype=torch.float32)
-        path_row, path_sign = i32(N, 0), f32(N, 0)
-        err = torch.full((hops,), ops.INT32_MAX, device=dev, dtype=torch.int32)
-        levels = []                                                          # per level: (entry nodes, children's parents, nodes)
-        field = self._field(plan)
-        for h in range(hops):
-            # dead entries (node -1: zero flow column) ride along with last node 0; their output is never read (and they list nothing)
-            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node.clamp(min=0), path_row, path_sign,
-                                       self._mb(plan, N * W), field_node=node if field else None,
-                                       fractions=self._multi_hop_fractions)
-            W2 = min(beam, W * D)
-            final = h == hops - 1
-            c_root, c_node, c_score, c_parent, c_slot = i32(N * W2), i32(N * W2), f32(N * W2), i32(N * W2), i32(N * W2)
-            c_row, c_sign = (None, None) if final else (i32(N * W2, h + 1), f32(N * W2, h + 1))
-            _lib.check(lib.scn_beam_step(N, W, W2, h, D, p(node), p(score), p(path_row) if h else None, p(path_sign) if h else None,
-                                         p(logp), p(tab.deg), tab.n_nodes, p(tab.node), p(tab.edge), p(tab.sign), plan.n_edges,
-                                         p(c_root), p(c_node), p(c_score), p(c_parent), p(c_slot), p(c_row), p(c_sign), p(err[h:]),
-                                         ops._stream()), "scn_beam_step")
-            if trace is not None:
-                trace.append({"node": node.view(N, W).cpu().numpy(), "score": score.view(N, W).cpu().numpy(),
-                              "logp": logp.view(N, W, D).cpu().numpy(), "parent": c_parent.view(N, W2).cpu().numpy(),
-                              "slot": c_slot.view(N, W2).cpu().numpy()})
-            levels.append((node, c_parent.view(N, W2), c_node.view(N, W2)))
-            root, node, score, path_row, path_sign, W = c_root, c_node, c_score, c_row, c_sign, W2
-        errs = err.cpu().numpy()
-        for h in np.flatnonzero(errs != ops.INT32_MAX)[:1]:
-            t = int(errs[h])
-            v = int(levels[h][0][t // D].item())
-            raise KeyError((v, int(tab.h_node[v, t % D])))
-        # node paths from the per-level parents, on the device: walk every final entry back to its root
-        dead = (levels[-1][2] < 0)
-        k = torch.arange(W, device=dev).expand(N, W)
-        steps = []
-        for _, parent, nodes in reversed(levels):
-            steps.append(torch.gather(nodes, 1, k))
-            k = torch.gather(parent, 1, k).clamp(min=0).long()
-        paths = torch.stack(steps[::-1], dim=2).long().masked_fill(dead[:, :, None], -1)
-        out_paths = np.full((N, beam, hops), -1, np.int64)
-        out_logp = np.full((N, beam), -np.inf, np.float64)
-        out_paths[:, :W] = paths.cpu().numpy()
-        out_logp[:, :W] = score.view(N, W).cpu().numpy()
-        return out_paths, out_logp
+        return multihop.beam_paths(self, inputs, hops, beam, nbrhoods, E_lookup)
 
     def multi_hop_accuracy_topk(self, inputs, target_nodes, mask, hops, beam):
         """Fraction of the trajectories of mask whose target_nodes[i] is the end node of one of their `beam` best paths of `hops`
@@ -556,88 +398,6 @@ class Scone_GCN():
         hit = np.any((end >= 0) & (end == np.asarray(target_nodes).reshape(-1, 1)), axis=1)
         return float(np.average(hit[np.asarray(mask) == 1]))
 
-    def _sample_levels(self, inputs, hops, n_samples, seed, temperature, nbrhoods, E_lookup):
-        """The sampled decoder's levels on the device.  A level keeps one entry per distinct path with the number of samples on it
-        (the probability tree's layout: entries sorted by trajectory, leaf_ptr); one batched forward over the entries
-        (ops.tree_level_logp), then scn_sample_draw picks every sample's slot inside the entry it sits in and scn_sample_expand
-        merges equal picks into one child (include/scone_hip.h) -- sample by sample what n_samples independent chains give, at the
-        cost of the distinct paths.  One size copy back per level; the error words of all levels are read once, at the end.
-        Returns (levels, final): levels[h] = (leaf_ptr [N + 1], node [L_h], entry_of [N, S]) for h = 0 .. hops (level 0 = the
-        roots), final = (leaf_ptr, node, score, count) of the last level, all device tensors."""
-        hops, S = int(hops), int(n_samples)
-        if hops < 1:
-            raise ValueError("hops must be at least 1")
-        if S < 1 or S > _lib.SCN_SAMPLE_MAX:
-            raise ValueError("n_samples must be between 1 and %d (SCN_SAMPLE_MAX)" % _lib.SCN_SAMPLE_MAX)
-        if not float(temperature) >= 0.0:
-            raise ValueError("temperature must not be negative")
-        inv_T = float("inf") if float(temperature) == 0.0 else float(np.float32(1.0) / np.float32(temperature))
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        plan = self._multihop_plan(inputs)
-        if nbrhoods is None:
-            nbrhoods = inputs[0] if self.model_type == 'bunch' else inputs[0].nbrhoods
-        if E_lookup is None:
-            E_lookup = self._edge_lookup(inputs)
-        tab = ops.step_tables(plan, nbrhoods, E_lookup, "binary")
-        lib = _lib.load()
-        dev = plan.device
-        N, D = _n_samples(inputs[-1]), plan.max_deg
-        if len(np.asarray(inputs[1]).reshape(-1)) != N:
-            raise ValueError("last nodes need one entry per trajectory of inputs (%d)" % N)
-        if S * D > _lib.SCN_SAMPLE_PAIRS_MAX or N * S * D >= ops.INT32_MAX:
-            raise ValueError("sampled level of %d x %d entries of %d slots is too large" % (N, S, D))
-        trace = self._multi_hop_trace
-        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)          # a copy: the caller's flows stay as they are
-        i32, f32 = (lambda *s: torch.empty(s, device=dev, dtype=torch.int32)), (lambda *s: torch.empty(s, device=dev, dtype=torch.float32))
-        p = lambda t: None if t is None else ops._dev(t, t.dtype)
-        root = torch.arange(N, device=dev, dtype=torch.int32)
-        node = torch.from_numpy(np.ascontiguousarray(np.asarray(inputs[1]).reshape(-1), np.int32)).to(dev)
-        score = torch.zeros((N,), device=dev, dtype=torch.float32)
-        count = torch.full((N,), S, device=dev, dtype=torch.int32)
-        path_row, path_sign = i32(N, 0), f32(N, 0)
-        leaf_ptr = torch.arange(N + 1, device=dev, dtype=torch.int32)
-        entry_of = torch.zeros((N, S), device=dev, dtype=torch.int32)
-        err = torch.full((hops,), ops.INT32_MAX, device=dev, dtype=torch.int32)
-        levels = [(leaf_ptr, node, entry_of)]
-        field = self._field(plan)
-        for h in range(hops):
-            L = int(node.shape[0])
-            if L == 0:                                                       # every sample has been dropped: the level stays empty
-                levels.append((leaf_ptr, node, torch.full_like(entry_of, -1)))
-                continue
-            # an entry on node -1 (the child of a pair without an edge) rides along with last node 0; its samples are dropped
-            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node.clamp(min=0), path_row, path_sign, self._mb(plan, L),
-                                       field_node=node if field else None, fractions=self._multi_hop_fractions)
-            pick, n_child = i32(N, S), i32(N)
-            _lib.check(lib.scn_sample_draw(N, S, S, L, h, D, seed, inv_T, p(leaf_ptr), p(node), p(logp), p(entry_of), p(tab.deg),
-                                           tab.n_nodes, p(tab.node), p(tab.edge), plan.n_edges, p(pick), p(n_child), p(err[h:]),
-                                           ops._stream()), "scn_sample_draw")
-            child_ptr = torch.zeros((N + 1,), device=dev, dtype=torch.int32)
-            child_ptr[1:] = torch.cumsum(n_child, 0)
-            C = int(child_ptr[-1].item())                                    # the one copy back per level: the next level's size
-            final = h == hops - 1
-            c_root, c_node, c_score, c_parent, c_slot, c_count = i32(C), i32(C), f32(C), i32(C), i32(C), i32(C)
-            c_row, c_sign = (None, None) if final else (i32(C, h + 1), f32(C, h + 1))
-            entry_next = i32(N, S)
-            _lib.check(lib.scn_sample_expand(N, S, S, L, h, D, p(leaf_ptr), p(node), p(score), p(path_row) if h else None,
-                                             p(path_sign) if h else None, p(logp), p(pick), p(child_ptr), C, tab.n_nodes, p(tab.node),
-                                             p(tab.edge), p(tab.sign), p(c_root), p(c_node), p(c_score), p(c_parent), p(c_slot),
-                                             p(c_count), p(c_row), p(c_sign), p(entry_next), ops._stream()), "scn_sample_expand")
-            if trace is not None:
-                trace.append({"leaf_ptr": leaf_ptr.cpu().numpy(), "node": node.cpu().numpy(), "score": score.cpu().numpy(),
-                              "count": count.cpu().numpy(), "logp": logp.cpu().numpy(), "entry_of": entry_of.cpu().numpy(),
-                              "pick": pick.cpu().numpy(), "child_ptr": child_ptr.cpu().numpy(), "parent": c_parent.cpu().numpy(),
-                              "slot": c_slot.cpu().numpy(), "child_count": c_count.cpu().numpy()})
-            root, node, score, count, path_row, path_sign, leaf_ptr, entry_of = c_root, c_node, c_score, c_count, c_row, c_sign, \
-                child_ptr, entry_next
-            levels.append((leaf_ptr, node, entry_of))
-        errs = err.cpu().numpy()
-        for h in np.flatnonzero(errs != ops.INT32_MAX)[:1]:
-            t = int(errs[h])
-            v = int(levels[h][1][t // D].item())
-            raise KeyError((v, int(tab.h_node[v, t % D])))
-        return levels, (leaf_ptr, node, score, count)
-
     def sample_paths(self, inputs, hops, n_samples, seed=0, temperature=1.0, nbrhoods=None, E_lookup=None):
         """Monte-Carlo multi-hop prediction with the semantics of predict_paths (current and readout node advance, a step SETS its
         edge, backtracking allowed, "binary" step tables, same defaults): n_samples paths per trajectory, every step drawn from the
@@ -645,48 +405,15 @@ class Scone_GCN():
         include/scone_hip.h; the draw of (trajectory, sample, hop) depends on `seed` and these three alone.  Returns
         (paths (N, n_samples, hops) int64 node ids, logp (N, n_samples) float64 = the summed log-probabilities), sample s in
         column s; a dropped sample (it reached a node without neighbours) is -1 / -inf.  Samples on the same path share one
-        forward: a level costs its distinct paths (_sample_levels).  Paths are rebuilt on the device, one copy at the end."""
-        levels, (leaf_ptr, node, score, _) = self._sample_levels(inputs, hops, n_samples, seed, temperature, nbrhoods, E_lookup)
-        dead = levels[-1][2] < 0
-        steps = []
-        for ptr, nodes, entry_of in levels[1:]:
-            at = ptr[:-1, None].long() + entry_of.clamp(min=0).long()
-            steps.append(nodes.long()[at.clamp(max=max(int(nodes.shape[0]) - 1, 0))] if nodes.shape[0] else
-                         torch.full_like(at, -1))
-        paths = torch.stack(steps, dim=2).masked_fill(dead[:, :, None], -1)
-        at = leaf_ptr[:-1, None].long() + levels[-1][2].clamp(min=0).long()
-        lp = score.double()[at.clamp(max=max(int(score.shape[0]) - 1, 0))] if score.shape[0] else torch.zeros_like(at, dtype=torch.float64)
-        lp = lp.masked_fill(dead, float("-inf"))
-        return paths.cpu().numpy(), lp.cpu().numpy()
-
-    def _sample_end_counts(self, inputs, hops, n_samples, seed, temperature):
-        """Per distinct (trajectory, end node) of the final level the number of samples there: (trajectory [M], node [M],
-        samples [M]) int64 device tensors, sorted by trajectory, then node."""
-        _, (leaf_ptr, node, _, count) = self._sample_levels(inputs, hops, n_samples, seed, temperature, None, None)
-        N = int(leaf_ptr.shape[0]) - 1
-        V = int(node.max().item()) + 2 if node.shape[0] else 1
-        root = torch.repeat_interleave(torch.arange(N, device=node.device), (leaf_ptr[1:] - leaf_ptr[:-1]).long())
-        live = node >= 0
-        key, inv = torch.unique(root[live] * V + node[live].long(), return_inverse=True)
-        total = torch.zeros(key.shape, device=node.device, dtype=torch.int64).index_add_(0, inv, count[live].long())
-        return torch.div(key, V, rounding_mode="floor"), key % V, total
+        forward: a level costs its distinct paths (multihop.sample_levels).  Paths are rebuilt on the device, one copy at the end."""
+        return multihop.sample_paths(self, inputs, hops, n_samples, seed, temperature, nbrhoods, E_lookup)
 
     def multi_hop_reach_probs(self, inputs, hops, n_samples, seed=0, temperature=1.0):
         """Where sample_paths' samples end, without building the paths: (nodes (N, K) int64, freq (N, K) float64) = per trajectory
         the distinct end nodes after `hops` steps and their share of the n_samples samples (dropped samples count in the
         denominator), highest share first, ties by the lower node id; the tail past a trajectory's distinct end nodes is -1 / 0.
         Computed from the final level's entries and counts."""
-        r, v, c = self._sample_end_counts(inputs, hops, n_samples, seed, temperature)
-        N = _n_samples(inputs[-1])
-        order = torch.sort(-c, stable=True)[1]                                # (r, v) ascending already; stable sorts keep the ties
-        order = order[torch.sort(r[order], stable=True)[1]]
-        r, v, c = r[order].cpu().numpy(), v[order].cpu().numpy(), c[order].cpu().numpy()
-        start = np.searchsorted(r, np.arange(N))
-        K = int(np.bincount(r, minlength=N).max()) if len(r) else 0
-        nodes, freq = np.full((N, K), -1, np.int64), np.zeros((N, K), np.float64)
-        col = np.arange(len(r)) - start[r]
-        nodes[r, col], freq[r, col] = v, c / np.float64(int(n_samples))
-        return nodes, freq
+        return multihop.reach_probs(self, inputs, hops, n_samples, seed, temperature)
 
     def multi_hop_target_probs_sampled(self, inputs, target_nodes, hops, n_samples, seed=0):
         """(N,) float64: the share of trajectory i's n_samples sampled paths (sample_paths at temperature 1) that end at
@@ -694,15 +421,7 @@ class Scone_GCN():
         probabilities of all paths that end there.  This is not what multi_hop_target_probs returns: the reference's tree divides
         that sum by the NUMBER of paths that reach the target (scn_tree_target), and is NaN where none does; this one estimates the
         sum itself and is 0 there."""
-        r, v, c = (t.cpu().numpy() for t in self._sample_end_counts(inputs, hops, n_samples, seed, 1.0))
-        target = np.asarray(target_nodes).reshape(-1)
-        N = _n_samples(inputs[-1])
-        if len(target) != N:
-            raise ValueError("target_nodes needs one entry per trajectory of inputs (%d)" % N)
-        hit = np.zeros(N, np.int64)
-        m = v == target[r]
-        hit[r[m]] = c[m]
-        return hit / np.float64(int(n_samples))
+        return multihop.target_probs_sampled(self, inputs, target_nodes, hops, n_samples, seed)
 
     def _edge_lookup(self, inputs):
         src = inputs[0] if self.model_type != 'bunch' else resolve_operands('bunch', self.shifts, inputs[0])[0][1]
@@ -722,61 +441,7 @@ class Scone_GCN():
     def multi_hop_target_probs(self, inputs, target_nodes, nbrhoods, E_lookup, last_nodes, hops):
         """Per-trajectory probability of reaching target_nodes[i] in `hops` steps (STM:154-204): every path of the probability
         tree is a leaf of its own; NaN where no leaf ends at the target (0 / 0 in the reference)."""
-        if int(hops) < 1:
-            raise ValueError("hops must be at least 1")
-        plan = self._multihop_plan(inputs)
-        tab = ops.step_tables(plan, nbrhoods, E_lookup, "dist")
-        lib = _lib.load()
-        dev = plan.device
-        N = _n_samples(inputs[-1])
-        if len(np.asarray(last_nodes).reshape(-1)) != N or len(np.asarray(target_nodes).reshape(-1)) != N:
-            raise ValueError("last_nodes and target_nodes need one entry per trajectory of inputs (%d)" % N)
-        root_x, _ = ops.flows_to_slabs(inputs[-1], plan.layout, dev)
-        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
-        root = torch.arange(N, device=dev, dtype=torch.int32)
-        node = i32(np.asarray(last_nodes).reshape(-1))
-        prob = torch.ones((N,), device=dev, dtype=torch.float32)
-        path_row = torch.empty((N, 0), device=dev, dtype=torch.int32)
-        path_sign = torch.empty((N, 0), device=dev, dtype=torch.float32)
-        err = torch.empty((1,), device=dev, dtype=torch.int32)
-        D = plan.max_deg
-        field = self._field(plan)
-        for h in range(int(hops)):
-            L = int(root.shape[0])
-            logp = ops.tree_level_logp(plan, self.weights, root_x, N, root, node, path_row, path_sign, self._mb(plan, L),
-                                       field_node=node if field else None, fractions=self._multi_hop_fractions)
-            if h == int(hops) - 1:
-                break
-            cnt = tab.deg[node.long()]
-            offset = (torch.cumsum(cnt, 0) - cnt).to(torch.int32)
-            C = int(cnt.sum().item())                                     # the one copy back per level: the next level's size
-            if C >= ops.INT32_MAX // max(D, 1):
-                raise ValueError("tree level of %d leaves is too large" % C)
-            c_root = torch.empty((C,), device=dev, dtype=torch.int32)
-            c_node = torch.empty_like(c_root)
-            c_prob = torch.empty((C,), device=dev, dtype=torch.float32)
-            c_row = torch.empty((C, h + 1), device=dev, dtype=torch.int32)
-            c_sign = torch.empty((C, h + 1), device=dev, dtype=torch.float32)
-            err.fill_(ops.INT32_MAX)
-            _lib.check(lib.scn_tree_expand(L, h, D, ops._dev(root, torch.int32), ops._dev(node, torch.int32), ops._dev(prob),
-                                           ops._dev(path_row, torch.int32) if h else None, ops._dev(path_sign) if h else None,
-                                           ops._dev(logp), ops._dev(offset, torch.int32), ops._dev(tab.deg, torch.int32), tab.n_nodes,
-                                           ops._dev(tab.node, torch.int32), ops._dev(tab.edge, torch.int32), ops._dev(tab.sign),
-                                           plan.n_edges, C, ops._dev(c_root, torch.int32), ops._dev(c_node, torch.int32),
-                                           ops._dev(c_prob), ops._dev(c_row, torch.int32), ops._dev(c_sign), ops._dev(err, torch.int32),
-                                           ops._stream()), "scn_tree_expand")
-            t = int(err.item())
-            if t != ops.INT32_MAX:
-                v = int(node[t // D].item())
-                raise KeyError(tuple(sorted((v, int(tab.h_node[v, t % D])))))
-            root, node, prob, path_row, path_sign = c_root, c_node, c_prob, c_row, c_sign
-        leaf_ptr = torch.searchsorted(root, torch.arange(N + 1, device=dev, dtype=torch.int32)).to(torch.int32)
-        out = torch.empty((N,), device=dev, dtype=torch.float32)
-        _lib.check(lib.scn_tree_target(N, ops._dev(leaf_ptr, torch.int32), ops._dev(node, torch.int32), ops._dev(prob), ops._dev(logp), D,
-                                       ops._dev(tab.deg, torch.int32), tab.n_nodes, ops._dev(tab.node, torch.int32),
-                                       ops._dev(i32(np.asarray(target_nodes).reshape(-1)), torch.int32), ops._dev(out), ops._stream()),
-                   "scn_tree_target")
-        return out.cpu().numpy().astype(np.float64)
+        return multihop.target_probs(self, inputs, target_nodes, nbrhoods, E_lookup, last_nodes, hops)
 
     def multi_hop_accuracy_dist(self, shifts, inputs, target_nodes, masks, nbrhoods, E_lookup, last_nodes, prefixes, hops):
         """[average target probability over the trajectories of mask for mask in masks] (STM:154-206; prefixes is unused, as in

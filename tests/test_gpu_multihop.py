@@ -215,6 +215,42 @@ def test_missing_pair_raises_key_error_and_flows_stay(data):
     assert net.accuracy(None, s["full"][0][0], s["full"][1][0], s["full"][2], s["full"][8]) == acc0
 
 
+def _without(E_lookup, *pairs):
+    """A copy of E_lookup without the key of every (a, b) of pairs, whichever way round it is stored."""
+    lookup = dict(E_lookup)
+    for a, b in pairs:
+        del lookup[(a, b) if (a, b) in lookup else (b, a)]
+    return lookup
+
+
+def test_rollout_key_error_names_the_lowest_trajectorys_unsorted_pair(data):
+    s = _setup(data, "scone")
+    net, nbrhoods = s["net"], s["inputs"][0].nbrhoods
+    first = net.predict_paths(s["inputs"], 1)[:, 0]
+    steps = [(int(v), int(u)) for v, u in zip(s["last"], first)]
+    v0, u0 = steps[0]
+    # trajectory 0's pair and the first other pair a later trajectory steps across: both fail at the first hop, the lowest is named
+    other = next(p for p in steps[1:] if set(p) != {v0, u0})
+    with pytest.raises(KeyError) as exc:
+        net.predict_paths(s["inputs"], 2, nbrhoods, _without(s["E_lookup"], (v0, u0), other))
+    assert exc.value.args == ((v0, u0),)                                       # (current node, chosen neighbour), not sorted
+
+
+def test_tree_key_error_names_the_sorted_pair_and_spares_the_last_level(data):
+    s = _setup(data, "scone")
+    net = s["net"]
+    v0 = int(s["last"][0])
+    u0 = int(next(u for u in s["nbrhoods"][v0] if u >= 0))
+    lookup = _without(s["E_lookup"], (v0, u0))
+    with pytest.raises(KeyError) as exc:
+        net.multi_hop_target_probs(s["inputs"], s["targets"], s["nbrhoods"], lookup, s["last"], 2)
+    assert exc.value.args == (tuple(sorted((v0, u0))),)
+    # the last level is never expanded: one hop looks no edge up
+    got = net.multi_hop_target_probs(s["inputs"], s["targets"], s["nbrhoods"], lookup, s["last"], 1)
+    want = net.multi_hop_target_probs(s["inputs"], s["targets"], s["nbrhoods"], s["E_lookup"], s["last"], 1)
+    assert np.array_equal(got.view(np.int64), want.view(np.int64))
+
+
 def test_level_split_over_chunks_gives_the_same_result(data):
     s = _setup(data, "scone")
     net = s["net"]

@@ -150,7 +150,7 @@ def test_restatement_keeps_nan_for_unreachable_targets():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# step tables (ops.StepTables) against a direct walk of the dicts, on a complex with a non-identity edge layout
+# step tables (multihop.StepTables) against a direct walk of the dicts, on a complex with a non-identity edge layout
 # ------------------------------------------------------------------------------------------------------------------
 
 def _walk(nbrhoods, E_lookup, perm, rule):
@@ -178,7 +178,7 @@ def _walk(nbrhoods, E_lookup, perm, rule):
 
 @pytest.mark.parametrize("rule", ["binary", "dist"])
 def test_step_tables_match_a_dict_walk(rule):
-    from scone_gcn_amd import ops
+    from scone_gcn_amd import multihop
     from scone_gcn_amd import synthetic_data_gen as g
     from scone_gcn_amd.complex import SimplicialComplex
     cx = g.random_SC_graph(60)
@@ -194,7 +194,7 @@ def test_step_tables_match_a_dict_walk(rule):
     nb = np.array(sc.nbrhoods)
     v_mid = int(np.argmax((nb >= 0).sum(1)))
     nb[v_mid, 1:] = np.concatenate([[-1], nb[v_mid, 1:-1]])
-    tab = ops.StepTables(nb, E_lookup, perm, rule, torch.device("cpu"))
+    tab = multihop.StepTables(nb, E_lookup, perm, rule, torch.device("cpu"))
     node, edge, sign = _walk(nb, E_lookup, perm, rule)
     assert np.array_equal(tab.h_node, node) and np.array_equal(tab.node.numpy(), node)
     assert np.array_equal(tab.edge.numpy(), edge)

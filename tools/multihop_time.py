@@ -33,7 +33,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import scone_oracle as so                                     # noqa: E402
-from scone_gcn_amd import dataset_io, synthetic_data_gen as g, trajectory_experiments as te   # noqa: E402
+from scone_gcn_amd import dataset_io, multihop, synthetic_data_gen as g, trajectory_experiments as te   # noqa: E402
 from scone_gcn_amd.complex import SimplicialComplex                        # noqa: E402
 from scone_gcn_amd.scone_trajectory_model import Scone_GCN                # noqa: E402
 from scone_gcn_amd.synthetic_data_gen import SparseFlows                   # noqa: E402
@@ -251,9 +251,9 @@ def case_d(reps, roots=4096, hops=8, samples=256, skip="dense", d_roots=None):
     net.sample_paths(inputs, 1, 1, nbrhoods=sc.nbrhoods, E_lookup=E_lookup)            # builds and caches the step tables
     t_tab = time.perf_counter() - t_tab
     _say("step tables %.1f s; counting the levels" % t_tab)
-    levels, _ = net._sample_levels(inputs, hops, samples, 0, 1.0, sc.nbrhoods, E_lookup)
-    entries = [int(l[1].shape[0]) for l in levels]                                     # level 0 .. hops; the last one is not evaluated
-    live = [int((l[2] >= 0).sum().item()) for l in levels]
+    levels = multihop.sample_levels(net, inputs, hops, samples, 0, 1.0, sc.nbrhoods, E_lookup)
+    entries = [int(l.node.shape[0]) for l in levels]                                   # level 0 .. hops; the last one is not evaluated
+    live = [int((l.entry_of >= 0).sum().item()) for l in levels]
     del levels
     leaves = int(sum(entries[:hops]))
     _say("entries per level %s; timing" % entries)
