@@ -605,6 +605,52 @@ int scn_tree_slabs_list(scn_conv_t conv, int32_t n_leaves, int32_t n_slabs, int3
                         const float* path_sign, int32_t n_roots, const float* root_x, int32_t n_rows, int32_t ns, float* x,
                         const scn_work_list* wl, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The k-th order Markov baseline (markov_model.py, MM:9-112) on a direct-addressed integer count table.  The graph is the padded
+ * neighbour table nbr[n_nodes][d] (a node's neighbours ascending and left-aligned, -1 behind them) with deg[n_nodes] real
+ * neighbours per node; slot(a, b) is the position of b in nbr[a][0 .. deg[a]).  A walk of `order` nodes (v0 .. v_{k-1}) is the state
+ *     s = ((v0 * d + slot(v0, v1)) * d + slot(v1, v2)) ... * d + slot(v_{k-2}, v_{k-1})           (order 1: s = v0)
+ * and counts[rows][d] (int32, rows = n_nodes * d^(order-1)) holds in counts[s][j] how often the walk was followed by the neighbour
+ * in slot j of its last node.  MM's weights are counts[s][j] / sum_j counts[s][j]; a state nobody visited is an all-zero row.
+ * Orders 1 .. SCN_MARKOV_MAX_ORDER are served while rows * d < 2^31 - 1; SCN_ERR_UNSUPPORTED otherwise, before any launch.
+ * Walks and prefixes are ragged: ptr[n + 1] and nodes[ptr[n]], both int32 (so fewer than 2^31 - 1 nodes in all).  n == 0 returns SCN_OK.
+ * The err word (the caller initialises it to INT32_MAX) is lowered (atomicMin) to the flat position t in `nodes` of the first
+ * consecutive pair (nodes[t], nodes[t + 1]) of one walk that the call reads and that is no edge of the graph or has an id outside
+ * [0, n_nodes) -- for an order-1 prefix, whose window has no pair, to the position of its last node if that id is out of range.
+ * Nothing is read through such an id.  The prefix calls read the last `order` nodes of a prefix and nothing before them.
+ * Integer atomics only, one launch per call on `stream`, no allocation, no synchronisation: the same inputs give the same bytes.
+ *
+ * scn_markov_table_rows (host): rows of the table, or the negative status above (SCN_ERR_BAD_SHAPE for n_nodes or d <= 0).
+ * scn_markov_count: for every walk and every i < len - order: counts[state(walk[i : i + order])][slot(walk[i + order - 1],
+ *   walk[i + order])] += 1 (MM:47-51).  It accumulates: the caller zeroes the table.  A walk with len <= order counts nothing, and
+ *   so does a window that contains an offending pair.  One wave per walk.
+ * scn_markov_rollout: MM:58-93 for all hops in one launch, one wave per prefix i.  At hop h the state is that of the last `order`
+ *   nodes (the prefix's, then the predictions'), v the last of them, the row counts[s][0 .. deg[v]); the maxima are the slots equal
+ *   to the row's maximum (an all-zero row ties all deg[v] slots, as MM:62-72 does on equal probabilities); with m maxima the
+ *   prediction is the ((u24 * m) >> 24)-th of them in slot order, u24 the 24-bit integer behind scn_sample_uniform(seed, i, 0, h).
+ *   pred[i][h] = that neighbour's id, n_tied[i][h] = m (MM's was_random: m > 1).  A prefix shorter than `order` predicts nothing
+ *   (MM:85 tests the original length): pred = -1, n_tied = 0 at every hop; likewise a prefix with an offending pair, and every hop
+ *   from a node of degree 0 on.  hops >= 1.
+ * scn_markov_two_target: MM:95-112.  t = the slot of target[i] at the prefix's last node v, o = (u24 * (deg[v] - 1)) >> 24 from the
+ *   uniform of (seed, i, 1, 0); the other neighbour is slot o + (o >= t).  score[i] = 1, 0.5 or 0 by comparing the two counts,
+ *   other[i] = that neighbour's id.  A target that is no neighbour of v lowers err_target[0] (INT32_MAX at the start) to i.  That
+ *   row, a short or offending prefix and a last node with a single neighbour (np.random.choice([]) raises in MM:104) get score 0
+ *   and other -1.
+ * scn_markov_probs: probs[i][j] (fp64, [n][d]) = (double)counts[s][j] / (double)(sum of the row) -- the bits Python's division
+ *   gives -- and 0 where the row is empty, j >= deg[v] or the prefix is short or offending. */
+#define SCN_MARKOV_MAX_ORDER 4
+int scn_markov_table_rows(int32_t n_nodes, int32_t d, int32_t order);
+int scn_markov_count(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t order, int32_t n_nodes, int32_t d,
+                     const int32_t* nbr, const int32_t* deg, int32_t* counts, int32_t* err, void* stream);
+int scn_markov_rollout(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t order, int32_t hops, uint64_t seed,
+                       int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, const int32_t* counts, int32_t* pred,
+                       int32_t* n_tied, int32_t* err, void* stream);
+int scn_markov_two_target(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t order, uint64_t seed,
+                          const int32_t* target, int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg,
+                          const int32_t* counts, float* score, int32_t* other, int32_t* err, int32_t* err_target, void* stream);
+int scn_markov_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t order, int32_t n_nodes, int32_t d,
+                     const int32_t* nbr, const int32_t* deg, const int32_t* counts, double* probs, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

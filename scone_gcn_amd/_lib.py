@@ -22,6 +22,7 @@ SCN_ERR_UNSUPPORTED = -4
 SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
 SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sample_expand
 SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
+SCN_MARKOV_MAX_ORDER = 4          # highest order of the scn_markov_* count tables
 
 
 class WorkListDesc(ctypes.Structure):          # scn_work_list (device pointers)
@@ -159,6 +160,14 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scn_tree_slabs_list": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_i32,
                                            c_void_p, ctypes.POINTER(WorkListDesc), c_void_p]),
+    "scn_markov_table_rows": (ctypes.c_int, [c_i32, c_i32, c_i32]),
+    "scn_markov_count": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_rollout": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, ctypes.c_uint64, c_i32, c_i32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_two_target": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, ctypes.c_uint64, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_probs": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

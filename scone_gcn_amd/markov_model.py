@@ -1,0 +1,266 @@
+"""The k-th order Markov next-node baseline (the reference's trajectory_analysis/markov_model.py = MM) on the device.
+
+Same call surface as the reference's Markov_Model -- train(G, paths), predict(prefix), test(prefixes, target_nodes, hops),
+test_2_target(prefixes, target_nodes) -- on a direct-addressed integer count table instead of nested dictionaries: a walk of
+`order` nodes is the state ((v0 D + slot(v0, v1)) D + ...) of the padded neighbour table (include/scone_hip.h, scn_markov_*),
+training is one launch over all walks and a whole multi-hop test is one launch over all prefixes (csrc/scn_markov.hip).
+The reference's weights are counts[s][j] / counts[s].sum(): next_node_probs / weights_of return exactly those float64 values.
+
+Where the reference calls np.random.choice -- among tied maxima (MM:71-72) and for the other neighbour of the 2-target test
+(MM:104) -- the draw here is the Philox uniform of (seed, row of the prefix in the call, ...), so a result depends on the seed
+and the row's position and on nothing else (not the global NumPy stream, not the rest of the batch).  Equal counts are equal
+probabilities (one divisor per row), so the tied sets are the reference's.  All math runs in libscone_hip.so; nothing falls
+back to the CPU.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import SCN_MARKOV_MAX_ORDER, check
+from .ops import INT32_MAX
+
+
+def neighbour_table(G):
+    """(nbr (V, D) int32, deg (V,) int32) of G: every node's neighbours ascending and left-aligned, -1 behind them.  G is the
+    project's UndirGraph, a (V, D) table padded with -1 (sc.nbrhoods), or a networkx-style graph on the nodes 0 .. V-1."""
+    if hasattr(G, "complex") and hasattr(G.complex, "nbrhoods"):
+        G = G.complex.nbrhoods
+    if torch.is_tensor(G):
+        G = G.cpu().numpy()
+    if isinstance(G, np.ndarray):
+        nb = np.asarray(G, np.int64)
+        if nb.ndim != 2 or nb.shape[1] < 1:
+            raise ValueError("the neighbour table must be (V, D), padded with -1")
+        V = nb.shape[0]
+        if np.any(nb >= V):
+            raise ValueError("the neighbour table names a node outside its %d rows" % V)
+        key = np.where(nb >= 0, nb, V)                          # real neighbours ascending, the padding behind them
+        nb = np.sort(key, axis=1)
+        nb = np.where(nb < V, nb, -1)
+    else:
+        nodes = sorted(int(v) for v in G.nodes)
+        V = len(nodes)
+        if V == 0 or nodes[0] != 0 or nodes[-1] != V - 1:
+            raise ValueError("the graph's nodes must be the integers 0 .. V-1")
+        rows = [sorted(int(u) for u in G[v]) for v in range(V)]
+        D = max(1, max(len(r) for r in rows))
+        nb = np.full((V, D), -1, np.int64)
+        for v, r in enumerate(rows):
+            nb[v, :len(r)] = r
+    deg = (nb >= 0).sum(axis=1)
+    return np.ascontiguousarray(nb, np.int32), np.ascontiguousarray(deg, np.int32)
+
+
+def ragged(paths):
+    """(ptr (n + 1,) int32, nodes int32) of a list of node lists, or of a (ptr, nodes) pair of arrays as it is."""
+    if isinstance(paths, tuple) and len(paths) == 2 and all(isinstance(a, np.ndarray) or torch.is_tensor(a) for a in paths):
+        ptr, nodes = (np.asarray(a.cpu() if torch.is_tensor(a) else a).astype(np.int64).ravel() for a in paths)
+        if len(ptr) < 1 or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(nodes):
+            raise ValueError("ptr must rise from 0 to len(nodes)")
+    else:
+        lens = [len(p) for p in paths]
+        ptr = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).astype(np.int64)
+        nodes = np.fromiter((int(v) for p in paths for v in p), np.int64, int(ptr[-1]))
+    if len(nodes) >= INT32_MAX:
+        raise ValueError("the paths hold %d nodes; fewer than 2^31 - 1 are served" % len(nodes))
+    if len(nodes) and (nodes.min() < -INT32_MAX or nodes.max() > INT32_MAX):
+        raise ValueError("a node id does not fit 32 bits")
+    return np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(nodes, np.int32)
+
+
+def table_rows(n_nodes, d, order):
+    """Rows of the count table (scn_markov_table_rows); ValueError for an order or a size the library does not serve."""
+    if int(order) != order or not 1 <= int(order) <= SCN_MARKOV_MAX_ORDER:
+        raise ValueError("order must be an integer in 1 .. %d, got %r" % (SCN_MARKOV_MAX_ORDER, order))
+    rows = _lib.load().scn_markov_table_rows(int(n_nodes), int(d), int(order))
+    if rows == _lib.SCN_ERR_UNSUPPORTED:
+        raise ValueError("the order-%d table of %d nodes x %d slots passes 2^31 - 1 entries" % (order, n_nodes, d))
+    if rows < 0:
+        raise ValueError("no count table for %d nodes x %d slots" % (n_nodes, d))
+    return rows
+
+
+class Markov_Model:
+    def __init__(self, order, seed=0, device=None):
+        """
+        :param order: number of prior states to consider when making a prediction (1 .. SCN_MARKOV_MAX_ORDER)
+        :param seed: key of every random choice (ties, the 2-target test's other neighbour)
+        """
+        if int(order) != order or not 1 <= int(order) <= SCN_MARKOV_MAX_ORDER:
+            raise ValueError("order must be an integer in 1 .. %d, got %r" % (SCN_MARKOV_MAX_ORDER, order))
+        self.order, self.seed, self.device = int(order), int(seed), device
+        self.counts = None                                      # (rows, D) int32 on the device after train()
+        self.n_rand_choices = 0                                 # tied predictions of the last test() (MM:81, 87)
+        self.h_nbr = self.h_deg = None
+
+    # ---- plumbing ----
+    def _upload(self, a):
+        return torch.from_numpy(a).to(self.device)
+
+    def _graph_args(self):
+        return self.n_nodes, self.width, ops._dev(self.nbr, torch.int32), ops._dev(self.deg, torch.int32)
+
+    def _err_word(self):
+        return torch.full((1,), INT32_MAX, dtype=torch.int32, device=self.device)
+
+    def _raise_bad_pair(self, err, ptr, nodes):
+        t = int(err.item())
+        if t == INT32_MAX:
+            return
+        p = int(np.searchsorted(ptr, t, side="right")) - 1
+        q = t - int(ptr[p])
+        if t + 1 < int(ptr[p + 1]):
+            raise ValueError("path %d, position %d: (%d, %d) is not an edge" % (p, q, nodes[t], nodes[t + 1]))
+        raise ValueError("path %d, position %d: node %d is outside the graph" % (p, q, nodes[t]))
+
+    def _prefix_args(self, prefixes):
+        if self.counts is None:
+            raise RuntimeError("train() first")
+        ptr, nodes = ragged(prefixes)
+        return ptr, nodes, self._upload(ptr), self._upload(nodes)
+
+    # ---- the reference's surface ----
+    def train(self, G, paths):
+        """
+        :param G: UndirGraph, networkx graph on 0 .. V-1, or (V, D) neighbour table
+        :param paths: paths over G: a list of node lists or a (ptr, nodes) pair
+        Builds the count table from scratch (MM:43-51); one upload, one launch.  ValueError for a pair of consecutive nodes that
+        is not an edge (the reference: KeyError).
+        """
+        nbr, deg = neighbour_table(G)
+        rows = table_rows(nbr.shape[0], nbr.shape[1], self.order)
+        ptr, nodes = ragged(paths)
+        if self.device is None:
+            self.device = ops.default_device()
+        lib = _lib.load()
+        self.h_nbr, self.h_deg = nbr, deg
+        self.n_nodes, self.width = int(nbr.shape[0]), int(nbr.shape[1])
+        self.nbr, self.deg = self._upload(nbr), self._upload(deg)
+        d_ptr, d_nodes = self._upload(ptr), self._upload(nodes)
+        counts = torch.zeros((rows, self.width), dtype=torch.int32, device=self.device)
+        err = self._err_word()
+        with torch.cuda.device(self.device):
+            check(lib.scn_markov_count(len(ptr) - 1, ops._dev(d_ptr, torch.int32), ops._dev(d_nodes, torch.int32), self.order,
+                                       *self._graph_args(), ops._dev(counts, torch.int32), ops._dev(err, torch.int32),
+                                       ops._stream()), "scn_markov_count")
+        self.counts = None
+        self._raise_bad_pair(err, ptr, nodes)
+        self.counts = counts
+
+    def predict_paths(self, prefixes, hops):
+        """(pred (n, hops) node ids, n_tied (n, hops)) of the greedy rollout of every prefix (MM:58-93): -1 / 0 from the hop on
+        at which nothing is predicted (a prefix shorter than `order`, a node without neighbours).  Row i draws from (seed, i)."""
+        ptr, nodes, d_ptr, d_nodes = self._prefix_args(prefixes)
+        n, hops = len(ptr) - 1, int(hops)
+        if hops < 1:
+            raise ValueError("hops must be at least 1")
+        pred = torch.empty((n, hops), dtype=torch.int32, device=self.device)
+        tied = torch.empty((n, hops), dtype=torch.int32, device=self.device)
+        err = self._err_word()
+        with torch.cuda.device(self.device):
+            check(_lib.load().scn_markov_rollout(n, ops._dev(d_ptr, torch.int32), ops._dev(d_nodes, torch.int32), self.order, hops,
+                                                 ctypes.c_uint64(self.seed & (2 ** 64 - 1)), *self._graph_args(),
+                                                 ops._dev(self.counts, torch.int32), ops._dev(pred, torch.int32),
+                                                 ops._dev(tied, torch.int32), ops._dev(err, torch.int32), ops._stream()),
+                  "scn_markov_rollout")
+        self._raise_bad_pair(err, ptr, nodes)
+        return pred.cpu().numpy(), tied.cpu().numpy()
+
+    def predict(self, prefix):
+        """
+        Predicts which node will be visited next, given that prefix was just visited: (node, was_random), from the last `order`
+        nodes of prefix (MM:58-74).  KeyError for a prefix shorter than `order`, as the reference's dictionary raises.
+        """
+        if len(prefix) < self.order:
+            raise KeyError(tuple(prefix))
+        pred, tied = self.predict_paths([list(prefix)], 1)
+        return (int(pred[0, 0]) if pred[0, 0] >= 0 else None), bool(tied[0, 0] > 1)
+
+    def test(self, prefixes, target_nodes, hops):
+        """
+        Returns the model's accuracy over the given prefixes and targets: the node of the last hop against the target (MM:76-93).
+        A prefix shorter than `order` is never extended, so its own last node is compared (MM:85, 92).
+        """
+        ptr, _ = ragged(prefixes)
+        pred, tied = self.predict_paths(prefixes, hops)
+        self.n_rand_choices = int((tied > 1).sum())
+        last = pred[:, -1].astype(np.int64)
+        lens = np.diff(ptr)
+        short = np.flatnonzero(lens < self.order)
+        if len(short):
+            if np.any(lens[short] == 0):
+                raise IndexError("an empty prefix has no last node")
+            _, nodes = ragged(prefixes)
+            last[short] = nodes[ptr[short + 1] - 1]
+        target = np.asarray([int(t) for t in target_nodes], np.int64)
+        if len(target) != len(last):
+            raise ValueError("prefixes and target_nodes disagree on the number of paths")
+        return np.average(target == last)
+
+    def test_2_target(self, prefixes, target_nodes):
+        """
+        Returns 2-target accuracy of model (MM:95-112): the target against one other neighbour of the last node, drawn from
+        (seed, row).  ValueError for a last node with a single neighbour (np.random.choice([]) raises in the reference too),
+        for a target that is not a neighbour and for a prefix shorter than `order`.
+        """
+        score, _ = self.two_target_scores(prefixes, target_nodes)
+        return float(score.sum()) / len(score)
+
+    # ---- beyond the reference ----
+    def two_target_scores(self, prefixes, target_nodes):
+        """(score (n,) of 1 / 0.5 / 0, other (n,) node ids) behind test_2_target."""
+        ptr, nodes, d_ptr, d_nodes = self._prefix_args(prefixes)
+        n = len(ptr) - 1
+        target = np.ascontiguousarray([int(t) for t in target_nodes], np.int32)
+        if len(target) != n:
+            raise ValueError("prefixes and target_nodes disagree on the number of paths")
+        lens = np.diff(ptr)
+        if np.any(lens < self.order):
+            raise ValueError("path %d is shorter than the order %d" % (int(np.flatnonzero(lens < self.order)[0]), self.order))
+        last = nodes[ptr[1:] - 1] if n else nodes[:0]
+        inside = (last >= 0) & (last < self.n_nodes)
+        single = np.flatnonzero(inside & (self.h_deg[np.where(inside, last, 0)] < 2))
+        if len(single):
+            raise ValueError("path %d ends at node %d, which has no second neighbour to compare the target with"
+                             % (int(single[0]), int(last[single[0]])))
+        score = torch.empty((n,), dtype=torch.float32, device=self.device)
+        other = torch.empty((n,), dtype=torch.int32, device=self.device)
+        d_target = self._upload(target)
+        err, err_t = self._err_word(), self._err_word()
+        with torch.cuda.device(self.device):
+            check(_lib.load().scn_markov_two_target(n, ops._dev(d_ptr, torch.int32), ops._dev(d_nodes, torch.int32), self.order,
+                                                    ctypes.c_uint64(self.seed & (2 ** 64 - 1)), ops._dev(d_target, torch.int32),
+                                                    *self._graph_args(), ops._dev(self.counts, torch.int32),
+                                                    ops._dev(score, torch.float32), ops._dev(other, torch.int32),
+                                                    ops._dev(err, torch.int32), ops._dev(err_t, torch.int32), ops._stream()),
+                  "scn_markov_two_target")
+        self._raise_bad_pair(err, ptr, nodes)
+        i = int(err_t.item())
+        if i != INT32_MAX:
+            raise ValueError("path %d: target %d is not a neighbour of its last node %d" % (i, target[i], last[i]))
+        return score.cpu().numpy().astype(np.float64), other.cpu().numpy()
+
+    def next_node_probs(self, prefixes):
+        """(n, D) float64: the reference's weights of every prefix's state by slot of its last node (0 in the padding, for a
+        state nobody visited and for a prefix shorter than `order`)."""
+        ptr, nodes, d_ptr, d_nodes = self._prefix_args(prefixes)
+        n = len(ptr) - 1
+        probs = torch.empty((n, self.width), dtype=torch.float64, device=self.device)
+        err = self._err_word()
+        with torch.cuda.device(self.device):
+            check(_lib.load().scn_markov_probs(n, ops._dev(d_ptr, torch.int32), ops._dev(d_nodes, torch.int32), self.order,
+                                               *self._graph_args(), ops._dev(self.counts, torch.int32),
+                                               ops._dev(probs, torch.float64), ops._dev(err, torch.int32), ops._stream()),
+                  "scn_markov_probs")
+        self._raise_bad_pair(err, ptr, nodes)
+        return probs.cpu().numpy()
+
+    def weights_of(self, prefix):
+        """The reference's weights[tuple(prefix)]: {neighbour: probability} of the state of the last `order` nodes of prefix."""
+        if len(prefix) < self.order:
+            raise KeyError(tuple(prefix))
+        p = self.next_node_probs([list(prefix)])[0]
+        v = int(prefix[-1])
+        return {int(self.h_nbr[v, j]): float(p[j]) for j in range(int(self.h_deg[v]))}

@@ -34,7 +34,8 @@ def hyperparams(args=None):
           'multi_hop': 0,                # 1: the 2-hop probability-tree accuracies (the reference's commented-out call, TE:508-510)
           'multi_hop_skip': 'dense',     # not in the reference: dense | field (field-of-view work lists for the multi-hop forwards)
           'beam': 0,                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
-          'multi_hop_samples': 0}        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
+          'multi_hop_samples': 0,        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
+          'markov_order': 1}             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
@@ -220,14 +221,79 @@ def data_setup(hops=(1,), load=True, folder_suffix='schaub', hp=None):
         target_nodes_all, prefixes
 
 
+def markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask, order=1, seed=0):
+    """The Markov baseline's five experiments (TE:327-432) with the reference's masks and print labels, on the device
+    (markov_model.Markov_Model of the given order).  The mixed experiment's forward / backward mask is shuffled by the trainer's
+    global stream (scone_trajectory_model._RNG), where the reference uses NumPy's.  Returns {label: [accuracies in print order]}."""
+    from . import scone_trajectory_model as stm
+    from .markov_model import Markov_Model
+    markov = Markov_Model(order, seed=seed)
+    prefixes = [[int(v) for v in p] for p in prefixes]
+    t1, t2 = (np.asarray(t).astype(np.int64) for t in target_nodes_all[:2])
+    train_mask, test_mask = np.asarray(train_mask), np.asarray(test_mask)
+    n = len(prefixes)
+    paths = [p + [int(a), int(b)] for p, a, b in zip(prefixes, t1, t2)]            # TE:331
+    pick = lambda seq, mask: [seq[i] for i in np.flatnonzero(np.asarray(mask))]
+    results = {}
+
+    def report(label, rows):
+        print(label)
+        results[label] = [float(r) for r in rows]
+        for r in rows:
+            print(r)
+
+    def accs(pre, a, b, mask, two_target=False):
+        pre, a, b = pick(pre, mask), np.asarray(pick(a, mask)), np.asarray(pick(b, mask))
+        return [markov.test(pre, a, 1), markov.test(pre, b, 2)] + ([markov.test_2_target(pre, a)] if two_target else [])
+
+    # forward paths (TE:341-350)
+    markov.train(G_undir, pick(paths, train_mask == 1))
+    report("train accs", accs(prefixes, t1, t2, train_mask == 1, True))
+    report("test accs", accs(prefixes, t1, t2, test_mask == 1, True))
+    # reversed test paths (TE:354-364)
+    rev_paths = [p[::-1] for p in paths]
+    rev_prefixes = [p[:-2] for p in rev_paths]
+    rev_t1, rev_t2 = np.asarray([p[-2] for p in rev_paths]), np.asarray([p[-1] for p in rev_paths])
+    report("Reversed test accs", accs(rev_prefixes, rev_t1, rev_t2, test_mask == 1))
+    # half forward, half backward (TE:366-392)
+    fwd_mask = np.array([True] * int(n / 2) + [False] * int(n / 2))
+    stm._RNG.shuffle(fwd_mask)
+    fwd, bkwd = np.flatnonzero(fwd_mask), np.flatnonzero(~fwd_mask)
+    mixed_paths = [paths[i] for i in fwd] + [rev_paths[i] for i in bkwd]
+    mixed_prefixes = [prefixes[i] for i in fwd] + [rev_prefixes[i] for i in bkwd]
+    mixed_t1, mixed_t2 = np.concatenate((t1[fwd], rev_t1[bkwd])), np.concatenate((t2[fwd], rev_t2[bkwd]))
+    m = len(mixed_paths)                                                           # n - 1 for an odd n, where the reference's masks misfit
+    markov.train(G_undir, pick(mixed_paths, train_mask[:m] == 1))
+    report("Mixed train accs", accs(mixed_prefixes, mixed_t1, mixed_t2, train_mask[:m] == 1))
+    report("Mixed test accs", accs(mixed_prefixes, mixed_t1, mixed_t2, test_mask[:m] == 1))
+    # train on middle, test on middle (TE:394-412)
+    third = np.arange(n) % 3
+    mid_train, mid_test = (third == 0) & (train_mask == 1), (third == 0) & (test_mask == 1)
+    markov.train(G_undir, pick(paths, mid_train))
+    report("Middle region train accs", accs(prefixes, t1, t2, mid_train))
+    report("Middle region test accs", accs(prefixes, t1, t2, mid_test))
+    # train on upper, test on lower (TE:415-432)
+    markov.train(G_undir, pick(paths, third == 1))
+    report("Upper region train accs", accs(prefixes, t1, t2, third == 1))
+    report("Lower region accs", accs(prefixes, t1, t2, third == 2))
+    return results
+
+
 def train_model(hp=None):
-    """Trains a model to predict the next node in each input path (TE:313-510, Markov block excluded)."""
+    """Trains a model to predict the next node in each input path (TE:313-510).  With -markov 1 the k-th order Markov baseline
+    (-markov_order K, default 1) runs its five experiments first (TE:327-432) and its accuracies go to
+    experiment_results["markov"].  The reference then stops (`raise Exception`, TE:433); this driver does not: it goes on to
+    train the model."""
     from .scone_trajectory_model import Scone_GCN
     hp = hyperparams() if hp is None else hp
     inputs_all, y_all, train_mask, test_mask, shifts, G_undir, E_lookup, nbrhoods, n_nbrs, target_nodes_all, prefixes = \
         data_setup(hops=(1, 2), load=hp['load_data'], folder_suffix=hp['data_folder_suffix'], hp=hp)
     (inputs_1hop, inputs_2hop), (y_1hop, y_2hop) = inputs_all, y_all
     in_axes = tuple(([None] * len(shifts)) + [None, None, 0, 0])          # TE:325
+    markov_results = None
+    if hp.get('markov', 0) == 1:                                           # TE:327-432
+        markov_results = markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask,
+                                            order=int(hp.get('markov_order', 1)))
     scone = Scone_GCN(hp['epochs'], hp['learning_rate'], hp['batch_size'], hp['weight_decay'],
                       skip_mode=hp.get('skip_mode', 'dense'), multi_hop_skip=hp.get('multi_hop_skip', 'dense'))
     if hp['model'] not in MODEL_FUNCS:
@@ -284,6 +350,8 @@ def train_model(hp=None):
             tp = scone.multi_hop_target_probs_sampled(inputs_1hop, target_nodes_all[1], 2, int(hp['multi_hop_samples']))
             results["multi_hop_sampled"] = [float(np.average(tp[np.asarray(m) == 1])) for m in (train_mask, test_mask)]
             print('Multi hop sampled target probs (%d samples):' % int(hp['multi_hop_samples']), results["multi_hop_sampled"])
+    if markov_results is not None:
+        results["markov"] = markov_results
     scone.experiment_results = results
     return scone, (train_loss, train_acc, test_loss, test_acc)
 
