@@ -315,6 +315,30 @@ int scn_conv_backward_fused_first_from_y(scn_conv_t conv_t, int32_t n_slabs, int
                                          float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
                                          const scn_work_list* wl /* NULL: dense */, void* stream);
 
+/* The LAST layer's output is read by the readout alone, and only on the edges incident to a neighbour of each trajectory's last
+ * node (scn_readout_forward / scn_readout_backward): a few dozen rows per trajectory.  The *_keep forwards compute every tile as the
+ * plain calls do and STORE only the (plan block, slab) items of a keep mask; which items depends on the last nodes, never on a value.
+ * scn_keep_mask: leaf i < n belongs to slab i / ns and stands on node[i] (the readout's last_nodes); with the `top` table of
+ *   scn_field_lists (node v -> T(v), the plan blocks holding a row the readout of v reads)
+ *     mask[n_blocks][words], words = ceil(n_slabs / 32), n_slabs = ceil(n / ns):
+ *     bit s & 31 of mask[b][s >> 5] is set iff some leaf i of slab s has b in T(node[i]).
+ *   The call zeroes the mask and sets the bits on `stream` (atomic OR; the result does not depend on the order): no allocation, no
+ *   synchronisation, no host read.  A node outside [0, n_nodes) is a caller's error that is only guarded against (nothing is read
+ *   through it); so is a block outside [0, n_blocks).
+ * scn_conv_forward_keep / scn_conv_forward_from_y_keep = scn_conv_forward / scn_conv_forward_from_y with such a mask (device,
+ *   geometry as above for the call's n_slabs): the rows of every kept (block, slab) of `out` hold the bits the plain call writes,
+ *   every other row of `out` is LEFT UNTOUCHED -- it holds whatever the buffer held.  keep = NULL: every row is stored (the plain
+ *   call).  With a mask: one group, c_in = c_out = 32 or 16 (from y: 32) on the LDS-blocked plan, and at most 64 slabs per
+ *   workgroup of the launch grid (any n_slabs <= 64); SCN_ERR_UNSUPPORTED otherwise, before any launch. */
+int scn_keep_mask(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
+                  int32_t n_blocks, uint32_t* mask, void* stream);
+int scn_conv_forward_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
+                          const float* const* W, int32_t c_out, int32_t act, float* out, const uint32_t* keep /* NULL: every row */,
+                          void* stream);
+int scn_conv_forward_from_y_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                                 const float* const* W, int32_t channels, int32_t act, float* out,
+                                 const uint32_t* keep /* NULL: every row */, void* stream);
+
 /* Backward of the layer that FOLLOWS the first one, fused with the first layer's weight gradient (what jax.grad of TE:144-149
  * yields for weights[0:6], STM:307, in one pass):
  *   this layer :  dW[slot] += aux^T G_slot                       (as scn_conv_backward; aux = the first layer's output)

@@ -112,6 +112,11 @@ SIGNATURES = {
                                                             ctypes.POINTER(c_void_p), c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
                                                             ctypes.POINTER(c_void_p), c_void_p, c_size_t, ctypes.POINTER(WorkListDesc),
                                                             c_void_p]),
+    "scn_keep_mask": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p]),
+    "scn_conv_forward_keep": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p), c_i32,
+                                             c_i32, c_void_p, c_void_p, c_void_p]),
+    "scn_conv_forward_from_y_keep": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                                    c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                         ctypes.POINTER(c_void_p)]),
     "scn_terms_forward": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_i32, c_i32,

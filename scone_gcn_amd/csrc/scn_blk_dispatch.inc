@@ -80,6 +80,12 @@ static dim3 launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, int max_pe
 
 constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
 constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
+constexpr KeepMask NO_KEEP{nullptr, 0};
+
+// The keep mask of a launch (scn_conv_forward_keep / _from_y_keep): words per block from the slab count.  A workgroup holds the bits
+// of its slab range in one 64-bit window (keep_window): false where the grid hands one more than that.
+static bool keep_fits(unsigned gy, int n_slabs) { return (n_slabs + (int)gy - 1) / (int)gy <= KEEP_WINDOW; }
+static KeepMask keep_mask_of(const uint32_t* keep, int n_slabs) { return KeepMask{keep, (n_slabs + 31) / 32}; }
 
 // What a launch of a blocked kernel starts from: the plan's device view with the block assignment of the chosen grid, the grid
 // (a work list carries its own slab lists: no slab split then), the operator's shape.
@@ -110,10 +116,12 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
 
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wlp,
-                    hipStream_t st, const float* partial) {            // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
+                    hipStream_t st, const float* partial,              // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
+                    const uint32_t* keep) {                            // keep (32 -> 32 and 16 -> 16, dense, no partial): stores by the mask
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const int ci = c_in[0];
     if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
+    if (keep && (partial || wl.block || !out || (ci != 32 && ci != 16))) return SCN_ERR_UNSUPPORTED;   // (the first layer is never the last)
     if (!out) {                                                           // first layer, shifted input only (scn_conv_forward_first with out = NULL)
         if (ci != 1 || !y_out || wl.block) return SCN_ERR_UNSUPPORTED;
         const size_t lds = smem_bytes(16);
@@ -123,18 +131,27 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
     if (ci == 32) {                                                       // 16 waves, f16 hi + lo split
         const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES);
         const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
+        if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
         return with_act(act, [&](auto A) -> int {
             constexpr int ACT = decltype(A)::value;
+            if (keep)
+                return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1], W[2],
+                                      out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(keep, n_slabs));
             return launch_checked(partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0],
-                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW);
+                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP);
         });
     }
     if (ci == 16) {                                                       // 16 waves, f16 hi + lo split, two slabs per visit
         const size_t lds = smem_bytes_c32(16 + 64);
         const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
+        if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
         return with_act(act, [&](auto A) -> int {
-            return launch_checked(fwd_c16_plain<decltype(A)::value>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1],
-                                  W[2], out, L.nr, L.nc, n_slabs, wl);
+            constexpr int ACT = decltype(A)::value;
+            if (keep)
+                return launch_checked(fwd_c16_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1], W[2],
+                                      out, L.nr, L.nc, n_slabs, wl, keep_mask_of(keep, n_slabs));
+            return launch_checked(fwd_c16_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1],
+                                  W[2], out, L.nr, L.nc, n_slabs, wl, NO_KEEP);
         });
     }
     const size_t lds = smem_bytes(16, 2 * BK_R * BK_NS * 12);
@@ -151,13 +168,18 @@ bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
 }
 
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st) {
+                           float* out, hipStream_t st, const uint32_t* keep) {      // keep: stores by the mask (see blocked_forward)
     const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
     const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
+    if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
     return with_act(act, [&](auto A) -> int {
-        return launch_checked(fwd_c32_from_y<decltype(A)::value>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
-                              out, L.nr, L.nc, n_slabs, NO_LIST, fw);
+        constexpr int ACT = decltype(A)::value;
+        if (keep)
+            return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2], out, L.nr,
+                                  L.nc, n_slabs, NO_LIST, fw, keep_mask_of(keep, n_slabs));
+        return launch_checked(fwd_c32_from_y<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
+                              out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP);
     });
 }
 
@@ -340,9 +362,9 @@ int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const flo
         constexpr int ACT = decltype(A)::value;
         if (ch == 16)
             return launch_checked(fwd_c16_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc,
-                                  n_slabs, NO_LIST);
+                                  n_slabs, NO_LIST, NO_KEEP);
         return launch_checked(fwd_c32_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs,
-                              NO_LIST, NO_FIRSTW);
+                              NO_LIST, NO_FIRSTW, NO_KEEP);
     });
 }
 

@@ -219,17 +219,40 @@ template <int I> __device__ __forceinline__ void fwd_prio() { __builtin_amdgcn_s
 // consecutive lanes write one whole 512-byte piece.  The records of slab v + 1 are requested at the start of interval v and
 // expanded between the wave's two phases; the slab barrier waits for the LDS writes (lgkmcnt) instead of the LDS-DMA (vmcnt).
 constexpr int W16_FIRSTW_BYTES = 3 * 32 * 4;              // FROMY: the first layer's weights [g][32], behind the plain form's extra bytes
-template <int ACT, bool EXT0 = false, bool ACCUM = false, bool FROMY = false>
+// KEEP (plain and from-y forms, dense launches): the layer is the LAST one and only the readout reads its output -- `km` holds a bit
+// per (plan block, slab) (scn_keep_mask) and a finished tile is stored only where its bit is set.  Staging, gather, contraction and
+// early-out are the other forms': what changes is whether pend[] is written out.  The decision depends on the trajectories' last
+// nodes, never on a value.
+// keep_window: the bits of block b for the KEEP_WINDOW slabs from `first` on (bit j = slab first + j), fetched ONCE in the block
+// prologue, beside the block's metadata, made wave-uniform and claimed there: nothing of it is in flight when the slab loop starts (a
+// scalar load in flight there turns the gather's counted lgkmcnt waits into lgkmcnt(0), a vector load is followed by vmcnt(0), a
+// wait for the LDS-DMA just issued: profiles/HISTORY.md section 3.2); the slab loop shifts two SGPRs.  The host hands a workgroup
+// at most KEEP_WINDOW slabs.
+constexpr int KEEP_WINDOW = 64;
+__device__ __forceinline__ uint64_t keep_window(const KeepMask km, int b, int first) {
+    const uint32_t* mw = km.bits + (size_t)b * km.words;
+    const int w0 = first >> 5, sh = first & 31;
+    const int last = km.words - 1, w1 = w0 + 1 < last ? w0 + 1 : last, w2 = w0 + 2 < last ? w0 + 2 : last;   // three loads, no branch
+    const uint32_t a = mw[w0], c1 = mw[w1], d2 = mw[w2];
+    const uint32_t c = w0 + 1 <= last ? c1 : 0u, d = w0 + 2 <= last ? d2 : 0u;                                // (words past the row: no slab)
+    uint64_t win = (((uint64_t)c << 32) | a) >> sh;
+    if (sh) win |= (uint64_t)d << (64 - sh);
+    uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)win), hi = __builtin_amdgcn_readfirstlane((uint32_t)(win >> 32));   // wave-uniform
+    asm volatile("" : "+s"(lo), "+s"(hi));                    // the loads are waited for HERE
+    return ((uint64_t)hi << 32) | lo;
+}
+template <int ACT, bool EXT0 = false, bool ACCUM = false, bool FROMY = false, bool KEEP = false>
 __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, const float* __restrict__ X,
                                                                      const float* __restrict__ X0,
                                                                      const float* __restrict__ W0,
                                                                      const float* __restrict__ W1,
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
-                                                                     int n_slabs, WorkList wl, FirstW fw) {
+                                                                     int n_slabs, WorkList wl, FirstW fw, KeepMask km) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave
     static_assert(!FROMY || (!EXT0 && !ACCUM), "the from-y form exists for the plain kernel");
+    static_assert(!KEEP || (!EXT0 && !ACCUM), "the keep mask exists for the plain and the from-y kernel");
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     char* wfrag = smem + smem_bytes_c32();
@@ -310,6 +333,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             if (tid < BK_R) sm.self[tid] = P.self_slot[(size_t)b * BK_R + tid];
             if (tid < W16_WAVES) tws[tid] = P.tile_w4[b * W16_WAVES + tid];
         }
+        const uint64_t keep = KEEP ? keep_window(km, b, k0) : ~0ull;   // bit `it` = slab k0 + it of this block is stored (dense launches only)
         __syncthreads();
         const int tw = tws[wave];                    // width of this wave's own quad
         const int twu = EXT0 ? 0 : P.tile_wu4[b * W16_WAVES + wave];
@@ -498,7 +522,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             }
             // D: column = lane&15 = point, row = 4*kq + r = channel within the 16-channel tile
             pend_ptr = out + tile0 + lane_out;
-            pend_valid = rt < m.rows;
+            pend_valid = rt < m.rows && (!KEEP || ((keep >> it) & 1) != 0);   // decided by the visit that made the tile, never again at store time
             STAMP_ADD(3);
         };
         // One barrier interval per slab (+ one for the late waves' last contraction).  Early waves: gather(v), contract(v); late
@@ -552,6 +576,8 @@ template <int ACT> constexpr auto fwd_c32_plain = fwd_c32_w16_kernel<ACT>;      
 template <int ACT> constexpr auto fwd_c32_power = fwd_c32_w16_kernel<ACT, true>;                  // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
 template <int ACT> constexpr auto fwd_c32_accum = fwd_c32_w16_kernel<ACT, false, true>;           // X0 = partial pre-activation, added before act
 template <int ACT> constexpr auto fwd_c32_from_y = fwd_c32_w16_kernel<ACT, false, false, true>;   // X = the first layer's records y, fw = its weight rows
+template <int ACT> constexpr auto fwd_c32_plain_keep = fwd_c32_w16_kernel<ACT, false, false, false, true>;   // plain, stores by km
+template <int ACT> constexpr auto fwd_c32_from_y_keep = fwd_c32_w16_kernel<ACT, false, false, true, true>;   // from y, stores by km
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = C_out = 16, sixteen waves, f16 hi + lo split -- the C=32 machinery on TWO slabs at a time:
@@ -577,16 +603,18 @@ __device__ __forceinline__ void split2_4(const f32x4 x, float s, f16x4& hi, f16x
 
 // EXT0 (the power form, see fwd_c32_w16_kernel): act(X0 W0 + X W1 + (S X) W2), segment 0 = the point's own channels of X0 in
 // slab A / slab B straight from HBM, the operator has one value array.
-template <int ACT, bool EXT0 = false>
+// KEEP (plain form, dense launches): see fwd_c32_w16_kernel; each slab of a pair has its own bit.
+template <int ACT, bool EXT0 = false, bool KEEP = false>
 __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, const float* __restrict__ X,
                                                                      const float* __restrict__ X0,
                                                                      const float* __restrict__ W0,
                                                                      const float* __restrict__ W1,
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
-                                                                     int n_slabs, WorkList wl) {
+                                                                     int n_slabs, WorkList wl, KeepMask km) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave and slab pair
+    static_assert(!KEEP || !EXT0, "the keep mask exists for the plain kernel");
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     uint8_t* tws = (uint8_t*)(smem + smem_bytes_c32());
@@ -644,6 +672,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
             if (tid < BK_R) sm.self[tid] = P.self_slot[(size_t)b * BK_R + tid];
             if (tid < W16_WAVES) tws[tid] = P.tile_w4[b * W16_WAVES + tid];
         }
+        const uint64_t keep = KEEP ? keep_window(km, b, k0) : ~0ull;   // bit `it` = slab k0 + it of this block is stored (dense launches only)
         __syncthreads();
         const int tw = tws[wave];
         const int twu = EXT0 ? 0 : P.tile_wu4[b * W16_WAVES + wave];
@@ -753,8 +782,9 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
             }
             // D: column = lane&15 = point, row = 4*g + r = output channel
             const bool valid = rt < m.rows;
-            pend_ptr[0] = valid ? out + (((size_t)slab_a * n_rows + m.row0 + rt) * BK_NS + n) * 16 + 4 * g : nullptr;
-            pend_ptr[1] = valid && has_b ? out + (((size_t)slab_b * n_rows + m.row0 + rt) * BK_NS + n) * 16 + 4 * g : nullptr;
+            const bool keep_a = !KEEP || ((keep >> (2 * ip)) & 1) != 0, keep_b = !KEEP || ((keep >> (2 * ip + 1)) & 1) != 0;
+            pend_ptr[0] = valid && keep_a ? out + (((size_t)slab_a * n_rows + m.row0 + rt) * BK_NS + n) * 16 + 4 * g : nullptr;
+            pend_ptr[1] = valid && has_b && keep_b ? out + (((size_t)slab_b * n_rows + m.row0 + rt) * BK_NS + n) * 16 + 4 * g : nullptr;
         }
     }
 #pragma unroll
@@ -765,6 +795,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
 // The forms of fwd_c16_w16_kernel by name (one function-pointer type; the dispatch never spells the boolean pack):
 template <int ACT> constexpr auto fwd_c16_plain = fwd_c16_w16_kernel<ACT>;            // X = the layer's input, X0 unused (null)
 template <int ACT> constexpr auto fwd_c16_power = fwd_c16_w16_kernel<ACT, true>;      // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
+template <int ACT> constexpr auto fwd_c16_plain_keep = fwd_c16_w16_kernel<ACT, false, true>;   // plain, stores by km
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = 1 -> C_out = C (first layer, TE:143-147 with flow (E,1)): three gathered scalars per point,

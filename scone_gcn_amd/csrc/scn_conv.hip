@@ -20,7 +20,7 @@ void free_block_plan(scn_conv_s* c);
 bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in, int c_out);
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wl,
-                    hipStream_t st, const float* partial = nullptr);
+                    hipStream_t st, const float* partial = nullptr, const uint32_t* keep = nullptr);
 bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux);
 size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux);
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
@@ -41,7 +41,7 @@ int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const fl
                            hipStream_t st, const float* const* W_first = nullptr);
 bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st);
+                           float* out, hipStream_t st, const uint32_t* keep = nullptr);
 int build_terms_plan(scn_conv_s* c, const uint8_t* term, const int32_t* lvl_row0, const uint8_t* merged, const int32_t* bins,
                      int group_rows);
 int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
@@ -541,6 +541,20 @@ int scn_conv_forward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const float
     return SCN_OK;
 }
 
+int scn_conv_forward_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
+                          const float* const* W, int32_t c_out, int32_t act, float* out, const uint32_t* keep, void* stream) {
+    if (!keep) return scn_conv_forward_list(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, stream);
+    if (!c || !src || !c_in || !W || !out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (!src[0] || c_in[0] <= 0) return SCN_ERR_BAD_ARG;
+    for (int s = 0; s < c->n_slots; ++s)
+        if (!W[s]) return SCN_ERR_BAD_ARG;
+    if (c->n_groups != 1 || c_in[0] != c_out || (c_out != 32 && c_out != 16) || !blocked_forward_supported(c, ns, c_in, c_out))
+        return SCN_ERR_UNSUPPORTED;
+    return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, nullptr, (hipStream_t)stream, nullptr, keep);
+}
+
 static int generic_bwd_blocks(const scn_conv_s* c, int n_slabs) {
     int64_t items = (int64_t)c->n_rows * n_slabs;
     return (int)std::min<int64_t>(items, 2048);
@@ -613,6 +627,16 @@ int scn_conv_forward_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const flo
     if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
     if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
     return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream);
+}
+
+int scn_conv_forward_from_y_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                                 const float* const* W, int32_t channels, int32_t act, float* out, const uint32_t* keep,
+                                 void* stream) {
+    if (!c || !y || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !W || !W[0] || !W[1] || !W[2] || !out)
+        return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream, keep);
 }
 
 int scn_conv_backward_fused_first_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,

@@ -218,6 +218,13 @@ struct WorkList {
     const int32_t* slab;    // active slabs of each listed block, ascending
 };
 
+// optional keep mask of a last layer's forward (scn_keep_mask): bit s & 31 of bits[b * words + (s >> 5)] = (block b, slab s) is
+// stored; bits == nullptr: everything is
+struct KeepMask {
+    const uint32_t* bits;
+    int32_t words;          // words per block = ceil(n_slabs / 32)
+};
+
 // extra plan arrays of a "terms" operator (fused Bunch layer, scn_terms.inc); the common part lives in BlockPlan
 struct TermsPlan {
     bool built = false;

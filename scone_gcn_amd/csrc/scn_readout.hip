@@ -322,6 +322,24 @@ __global__ __launch_bounds__(1024) void readout_dw_kernel(int nd, int c, const f
     }
 }
 
+// Keep mask of a last layer's forward (scn_keep_mask): thread = leaf i of slab i / ns, standing on node[i]; bit (b, slab) is set for
+// every block b of T(node[i]) (the `top` table of scn_field_lists).  A node outside [0, n_nodes) or a block outside [0, n_blocks)
+// is a caller's error that is only guarded against: nothing is read or written through it.
+__global__ __launch_bounds__(256) void keep_mask_kernel(int n, int ns, const int32_t* __restrict__ node, int n_nodes,
+                                                        const int32_t* __restrict__ top_ptr, const int32_t* __restrict__ top_blk,
+                                                        int n_blocks, int words, uint32_t* __restrict__ mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int v = node[i];
+    if (v < 0 || v >= n_nodes) return;
+    const int s = i / ns;
+    const uint32_t bit = 1u << (s & 31);
+    for (int t = top_ptr[v]; t < top_ptr[v + 1]; ++t) {
+        const int b = top_blk[t];
+        if (b >= 0 && b < n_blocks) atomicOr(&mask[(size_t)b * words + (s >> 5)], bit);
+    }
+}
+
 __global__ __launch_bounds__(64) void node_readout_fwd_kernel(int ns, int n_nodes, const float* __restrict__ X,
                                                               const int32_t* __restrict__ nbr, int max_deg,
                                                               const int32_t* __restrict__ last_nodes,
@@ -672,6 +690,19 @@ int scn_readout_clear_dz(int32_t n_slabs, int32_t ns, int32_t n_edges, int32_t c
         hipLaunchKernelGGL(readout_bwd_kernel, dim3(n_slabs * ns), dim3(64), 0, (hipStream_t)stream, ns, n_edges, c, nullptr,
                            nullptr, nbr, max_deg, last_nodes, inc_ptr, inc_edge, nullptr, edge_nodes, nullptr, nullptr, 0, dz,
                            nullptr, 1);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_keep_mask(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
+                  int32_t n_blocks, uint32_t* mask, void* stream) {
+    if (!node || !top_ptr || !top_blk || !mask) return SCN_ERR_BAD_ARG;
+    if (n <= 0 || ns <= 0 || n_nodes <= 0 || n_blocks <= 0) return SCN_ERR_BAD_SHAPE;
+    const int n_slabs = (n + ns - 1) / ns, words = (n_slabs + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    SCN_HIP_TRY(hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)n_blocks * words, st));
+    hipLaunchKernelGGL(keep_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, ns, node, n_nodes, top_ptr, top_blk, n_blocks,
+                       words, mask);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

@@ -82,6 +82,11 @@ FUSE_FIRST = True      # False: separate scn_conv_backward + scn_conv_dw_first i
 # stack at hidden 32 never stores it -- layer 1 writes y only, layer 2's forward expands y into its LDS image and the fused-first backward
 # rebuilds its aux values in registers (SconePlan.conv_stack / _backward).  False: H1 is materialised (the path every other shape takes).
 RECOMPUTE_FIRST = True
+# Nothing reads the last layer's output H_L except the readout, and that only on the edges around each trajectory's last node (about
+# 0.1 % of the rows at |E| = 1M): the last layer's forward stores only the (plan block, slab) items holding such a row, by a bit mask
+# built on the device from the last nodes (SconePlan.conv_stack, scn_keep_mask, scn_conv_forward_keep).  Every tile is still staged,
+# gathered and contracted: this is not the zero-skipping mode.  False: the whole tensor is stored.
+KEEP_LAST = True
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
 # step, one launch against the layer-by-layer kernels, ms (tools/small_step.py, profiles/r04_small_step_ab.txt):
@@ -232,6 +237,19 @@ def field_tables(row0, pattern_csr, nbr, inc_ptr, inc_edge):
     return tuple(out)
 
 
+def keep_mask_host(nodes, ns, top_ptr, top_blk, n_blocks):
+    """NumPy restatement of scn_keep_mask (include/scone_hip.h): uint32 [n_blocks][ceil(n_slabs / 32)], bit s & 31 of word
+    [b][s >> 5] set iff a leaf i of slab s = i // ns has block b in T(nodes[i]).  A node outside the table contributes nothing."""
+    nodes = np.asarray(nodes, np.int64)
+    n_slabs = -(-len(nodes) // ns)
+    mask = np.zeros((n_blocks, (n_slabs + 31) // 32), np.uint32)
+    for i, v in enumerate(nodes):
+        if 0 <= v < len(top_ptr) - 1:
+            s = i // ns
+            mask[np.asarray(top_blk[top_ptr[v]:top_ptr[v + 1]], np.int64), s >> 5] |= np.uint32(1 << (s & 31))
+    return mask
+
+
 class FieldTables(NamedTuple):
     """Device copies of field_tables for one plan."""
     n_blocks: int
@@ -301,11 +319,27 @@ class ConvOp:
         check(_lib.load().scn_conv_plan_info(self.handle, ctypes.byref(nb), ctypes.byref(ms)), "scn_conv_plan_info")
         return nb.value, ms.value
 
-    def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None):
+    def keep_mask(self, nodes, ns, n_nodes, tabs):
+        """The keep mask of a last layer's forward (scn_keep_mask): int32 words [n_blocks][ceil(n_slabs / 32)], bit (b, s) set iff a
+        leaf of slab s stands on a node whose readout reads a row of plan block b.  nodes: int32 device tensor, one per trajectory;
+        tabs: the plan's FieldTables.  A fresh buffer per call, filled on the current stream (nothing is kept on the operator)."""
+        n = nodes.numel()
+        words = (-(-n // ns) + 31) // 32
+        mask = torch.empty((tabs.n_blocks, words), device=nodes.device, dtype=torch.int32)
+        with _timed("keep_mask", _nbytes(mask, nodes)):
+            check(_lib.load().scn_keep_mask(n, ns, _dev(nodes, torch.int32), n_nodes, _dev(tabs.top_ptr, torch.int32),
+                                            _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32), _stream()),
+                  "scn_keep_mask")
+        return mask
+
+    def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None):
         """wl: WorkList (zero-skipping): only the listed items of `out` are written; `out` must be given, all-zero.
-        partial: tensor of the output's shape added to the pre-activation (scn_conv_forward_accumulate; out defaults to it, in place)."""
+        partial: tensor of the output's shape added to the pre-activation (scn_conv_forward_accumulate; out defaults to it, in place).
+        keep: keep_mask() of the launch (last layer, dense): only the kept (block, slab) items of `out` are written, the rest of it
+        holds whatever the buffer held; None when the shape is not served (scn_conv_forward_keep)."""
         lib = _lib.load()
         assert wl is None or out is not None
+        assert keep is None or (wl is None and partial is None)
         if partial is not None:
             assert wl is None and tuple(partial.shape) == (srcs[0].shape[0], self.n_rows, srcs[0].shape[2], c_out)
             out = partial if out is None else out
@@ -324,6 +358,13 @@ class ConvOp:
                 check(lib.scn_conv_forward_accumulate(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act],
                                                       _dev(partial), _dev(out), _stream()), "scn_conv_forward_accumulate")
             return out
+        if keep is not None:
+            # (the key of the plain forward; the kept stores are left out of the byte model: under 0.2 % of a tensor on the benchmark's
+            # batches, and their count is on the device)
+            with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), _nbytes(*srcs) + self.csr_bytes):
+                st = lib.scn_conv_forward_keep(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
+                                               _dev(keep, torch.int32), _stream())
+            return out if _served(st, "scn_conv_forward_keep") else None
         with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if wl is not None else _nbytes(out, *srcs) + self.csr_bytes):
             check(lib.scn_conv_forward_list(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
                                             wl.ref() if wl is not None else None, _stream()), "scn_conv_forward")
@@ -393,18 +434,25 @@ class ConvOp:
             st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
         return y if _served(st, "scn_conv_forward_first") else None
 
-    def forward_from_y(self, y, Ws_first, Ws, act):
+    def forward_from_y(self, y, Ws_first, Ws, act, keep=None, out=None):
         """The layer AFTER a 1-channel first layer from that layer's shifted input y and weights Ws_first: act(sum_s (S_s H1) Ws[s]) with
-        H1 rebuilt inside the kernel (scn_conv_forward_from_y); None when the shape is not served."""
+        H1 rebuilt inside the kernel (scn_conv_forward_from_y); None when the shape is not served.  keep: as in forward
+        (scn_conv_forward_from_y_keep)."""
         lib = _lib.load()
         S, rows, ns, _ = y.shape
         c = Ws[0].shape[1]
         if self.n_groups != 1 or self.n_slots != 3 or rows != self.n_rows or any(tuple(w.shape) != (c, c) for w in Ws) or \
                 any(tuple(w.shape) != (1, c) for w in Ws_first):
             return None
-        out = torch.empty((S, self.n_rows, ns, c), device=y.device, dtype=torch.float32)
+        if out is None:
+            out = torch.empty((S, self.n_rows, ns, c), device=y.device, dtype=torch.float32)
         # (the key of the plain C -> C forward: the same kernel family, and what callers that look for the fused layer kernels expect;
         # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
+        if keep is not None:                          # (the kept stores are left out of the byte model, see forward)
+            with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y) + self.csr_bytes):
+                st = lib.scn_conv_forward_from_y_keep(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out),
+                                                      _dev(keep, torch.int32), _stream())
+            return out if _served(st, "scn_conv_forward_from_y_keep") else None
         with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y, out) + self.csr_bytes):
             st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
         return out if _served(st, "scn_conv_forward_from_y") else None
@@ -861,7 +909,9 @@ def _shapes(weights):
 
 class SconeState(NamedTuple):
     """SconePlan / PowerPlan.forward -> backward / release."""
-    hs: list            # [x, H_1 .. H_L]; H_1 is None where it is rebuilt from y0; wide: every entry the list of its 32-channel blocks
+    hs: list            # [x, H_1 .. H_L]; H_1 is None where it is rebuilt from y0; wide: every entry the list of its 32-channel blocks.
+                        # H_L has its full shape, but where the forward ran with a keep mask (ops.KEEP_LAST) only the (plan block, slab)
+                        # items the readout of this forward's last nodes reads were written: every other row is uninitialised memory
     bh: object          # the readout's gathered rows (wide: one per block of H_L)
     y0: object          # the first layer's shifted input, or None
     activity: object    # work lists of the zero-skipping mode, or None
@@ -943,20 +993,37 @@ class SconePlan(Plan):
         self.nnz_lower, self.nnz_upper = int(lo.nnz), int(up.nnz)
 
     # -- raw forward/backward over slabs (no autograd): used by the autograd Function and by the trainer
-    def conv_stack(self, x, weights, activity=None):
+    def conv_stack(self, x, weights, activity=None, last_dev=None, out_last=None):
+        """last_dev: the trajectories' last nodes (what the readout of this forward will take).  With them the LAST layer stores only
+        what that readout reads (_keep_last); without them, or where that path is not served, every layer stores its whole output.
+        out_last (dense stacks of two or more layers): the buffer H_L is written into instead of a fresh one -- a test pre-fills it
+        to see which rows a forward wrote."""
         n_layers = (len(weights) - 1) / 3
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:141-142
         hs, y0 = [x], None
         S, E, ns, _ = x.shape
+        L = int(n_layers)
+        keep = self._keep_last(x, weights, activity, last_dev)
+
+        def layer(i, src):                              # layer i >= 1 of a dense stack; the last one by the keep mask where there is one
+            w = weights[3 * i:3 * i + 3]
+            buf = out_last if i == L - 1 else None
+            out = self.conv.forward([src], w, w[0].shape[1], self.act, out=buf, keep=keep) if keep is not None and i == L - 1 else None
+            return out if out is not None else self.conv.forward([src], w, w[0].shape[1], self.act, out=buf)
+
         if self._recompute_first(x, weights, activity):
             # hidden 32 throughout, 1-channel input, dense: H1 is never stored (hs[1] is None).  Layer 1 writes the shifted input y
             # only, layer 2 expands it in LDS; the backward sees hs[1] is None and rebuilds its aux values from y (see _backward)
             y0 = self.conv.shifted_input(x)
-            h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act) if y0 is not None else None
+            h2 = None
+            if y0 is not None and keep is not None and L == 2:
+                h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=keep, out=out_last)
+            if y0 is not None and h2 is None:
+                h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, out=out_last if L == 2 else None)
             if h2 is not None:
                 hs += [None, h2]
-                for i in range(2, int(n_layers)):
-                    hs.append(self.conv.forward([hs[-1]], weights[3 * i:3 * i + 3], 32, self.act))
+                for i in range(2, L):
+                    hs.append(layer(i, hs[-1]))
                 return hs, y0
             y0 = None
         for i in range(int(n_layers)):
@@ -972,9 +1039,33 @@ class SconePlan(Plan):
             if first is not None:                       # 1-channel input: keep the shifted input for the weight gradient
                 hs.append(first[0])
                 y0 = first[1]
+            elif activity is None and i > 0:
+                hs.append(layer(i, hs[-1]))
             else:
                 hs.append(self.conv.forward([hs[-1]], w, c_out, self.act, out=out, wl=wl))
         return hs, y0
+
+    # up to this size of H_L the last layer stores everything: the two extra launches of the mask cost more than the stores they save
+    # on the graph-replayed steps of small complexes (the bound of SMALL_DZ_BYTES; tests set 0 to take the path on small complexes)
+    KEEP_LAST_MIN_BYTES = 8 << 20
+
+    def _keep_last(self, x, weights, activity, last_dev):
+        """The keep mask the last layer of this stack runs with, or None: plain scone plan on its blocked operator, dense launches, a
+        last layer of 32 -> 32 or 16 -> 16 channels (so at least two layers), an H_L above KEEP_LAST_MIN_BYTES, and the plan's
+        node -> blocks table (field_tables_dev: none for a probed closure; it is built on the host at first use, so not under a
+        graph capture).  KEEP_LAST is the tests' and A/B's switch."""
+        if not KEEP_LAST or last_dev is None or activity is not None or not self.fused_conv or len(weights) < 7:
+            return None
+        S, E, ns, _ = x.shape
+        sh = tuple(weights[-2].shape)
+        if ns != NS or sh not in ((32, 32), (16, 16)) or last_dev.numel() != S * ns or last_dev.dtype != torch.int32:
+            return None
+        if S * E * ns * sh[1] * 4 <= self.KEEP_LAST_MIN_BYTES or not self._blocked():
+            return None
+        if self._field is None and torch.cuda.is_current_stream_capturing():
+            return None
+        tabs = self.field_tables_dev()
+        return self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs) if tabs is not None else None
 
     def _recompute_first(self, x, weights, activity):
         """Whether this stack runs without a stored H1: plain scone plan, 1-channel input, every hidden width 32 (no promotion), at
@@ -1184,7 +1275,8 @@ class SconePlan(Plan):
         # composed Ebli plan (PowerPlan) keeps its per-shift structure and runs its dense-term kernels as 32 x 32 MFMA blocks
         return promoted_width([sh[1] for sh in shapes[:-1]], wide=shapes[0][0] == 1)
 
-    def forward(self, x, last_dev, weights, activity=None):
+    def forward(self, x, last_dev, weights, activity=None, out_last=None):
+        """out_last: see conv_stack (plain dense stacks; ignored by the wide stack and the work-list modes)."""
         P = self.promotion(weights)
         wp = promote_weights(weights, 3, 1, P) if P else None
         w = wp if P else weights
@@ -1200,7 +1292,7 @@ class SconePlan(Plan):
             check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), _ptrs(parts),
                                                          _dev(parts[0]), _dev(logp), _stream()), "scn_logits_sum_log_softmax")
             return logp, SconeState(hs, bhs, y0, None, wp, wide=True)
-        hs, y0 = self.conv_stack(x, w, activity)
+        hs, y0 = self.conv_stack(x, w, activity, last_dev, out_last)
         logp, bh, _ = self.readout(hs[-1], w[-1], last_dev)
         return logp, SconeState(hs, bh, y0, activity, wp, wide=False)
 
@@ -1370,7 +1462,7 @@ class PowerPlan(SconePlan):
     def field_tables_dev(self):
         return None
 
-    def conv_stack(self, x, weights, activity=None):
+    def conv_stack(self, x, weights, activity=None, last_dev=None, out_last=None):   # (neither is used: every layer stores its whole output)
         n_layers = (len(weights) - 1) / 3
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:159-160
         hs, y0 = [x], None

@@ -2,7 +2,7 @@
 """Same-process, same-box A/B of library builds: ONE complex, ONE set of tensors, a plan per library build (tools/ab_build.sh),
 and the timed kernels ALTERNATING between the builds round by round -- box-to-box and run-to-run drift cancel.
 
-    python tools/ab_run.py --libs base=scone_gcn_amd/libscone_hip.so,x=tools/ab/lib_x.so --which fwd,bwd,bwdf,spmm \
+    python tools/ab_run.py --libs base=scone_gcn_amd/libscone_hip.so,x=tools/ab/lib_x.so --which fwd,fwdy,bwd,bwdf,spmm \
                            --data dense,sparse --rounds 3 --reps 3
 
 Prints per (data, kernel, build) the mean launch time over all rounds, per-round values, and output checksums (builds of one
@@ -76,6 +76,8 @@ def call(plan, k, x, aux, yrec):
         return plan.conv.forward_first(x1, W1, C, "tanh", out=out1, y=y1)
     if k == "fwd":
         return plan.conv.forward([x], W, C, "tanh")
+    if k == "fwdy":                                  # the layer after the first one from the first layer's records (hidden 32)
+        return plan.conv.forward_from_y(yin, W1, W, "tanh")
     if k == "bwd":
         dWs = [torch.zeros_like(w) for w in W]
         return plan.conv.backward([x], W, aux, "tanh", True, dWs), dWs
@@ -114,6 +116,8 @@ for data in a.data.split(","):
         x1 = x[..., :1].contiguous()
         out1 = torch.empty(S, E, 4, C, device=dev)
         y1 = torch.empty(S, E, 4, 4, device=dev)
+    if "fwdy" in which:
+        yin = next(iter(builds.values()))[1].conv.shifted_input(x[..., :1].contiguous())
     times = {(k, n): [] for k in which for n in builds}
     for k in which:
         for n, (lib, plan) in builds.items():
