@@ -494,6 +494,8 @@ __global__ void fold1_backward_kernel(const float* __restrict__ w1, const float*
     dw1[a] += (w > 0.f ? sp : 0.f) + (w < 0.f ? sm : 0.f);
 }
 
+// grid cap of the generic and the MFMA backward (whose block covers two of these tiles: blocks without a tile write a zero partial):
+// tests/test_gpu_dense_terms.py runs past it (CAP_TILES) and on the idle blocks
 static int dense_blocks(int64_t n_points) { return (int)std::min<int64_t>(2048, (n_points + DN_TILE - 1) / DN_TILE); }
 
 }  // namespace scn
@@ -517,6 +519,7 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
                 if (!G[k] || !W[k]) return SCN_ERR_BAD_ARG;
                 a1.G[k] = G[k]; a1.W[k] = W[k];
             }
+            // grid cap, IN1_U items per thread and trip: tests/test_gpu_dense_terms.py runs past both (CAP_STREAM, IN1_U)
             const int blocks = (int)std::min<int64_t>(8192, (n_points * (c_out / 4) + 255) / 256);
             return with_act(act, [&](auto A) -> int {
                 constexpr int ACT = decltype(A)::value;
@@ -538,6 +541,7 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
     bool all32 = c_out == 32;
     for (int k = 0; k < n_terms; ++k) all32 = all32 && c_in[k] == 32;
     if (all32) {
+        // grid cap: tests/test_gpu_dense_terms.py runs past it (CAP_TILES)
         const int blocks = (int)std::min<int64_t>(2048, ((n_points + 31) / 32 + DM_WAVES - 1) / DM_WAVES);
         return with_act(act, [&](auto A) -> int {
             return launch_checked(dense_fwd_mfma_kernel<decltype(A)::value>, dim3(blocks), dim3(DM_THREADS), 0, (hipStream_t)stream, a);
@@ -547,6 +551,7 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
     for (int k = 1; k < n_terms; ++k) same = same && c_in[k] == c_in[0];
     if (same) {                                                     // one output channel, equal term widths 16 / 32
         const int cqn = c_in[0] / 4;
+        // grid cap: tests/test_gpu_dense_terms.py runs past it (CAP_STREAM)
         const int blocks = (int)std::min<int64_t>(8192, (n_points * cqn + 255) / 256);
         if (cqn == 8) hipLaunchKernelGGL(dense_fwd_out1_kernel<8>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
         else hipLaunchKernelGGL(dense_fwd_out1_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
@@ -555,6 +560,7 @@ int scn_dense_terms_forward(int64_t n_points, int32_t n_terms, const float* cons
     }
     if (lds > 64 * 1024) return SCN_ERR_UNSUPPORTED;
     const int64_t total = n_points * ((c_out + 3) / 4);
+    // grid cap: tests/test_gpu_dense_terms.py runs past it (CAP_STREAM)
     const int blocks = (int)std::min<int64_t>(8192, (total + DN_THREADS - 1) / DN_THREADS);
     hipLaunchKernelGGL(dense_fwd_kernel, dim3(blocks), dim3(DN_THREADS), lds, (hipStream_t)stream, a);
     SCN_LAUNCH_CHECK();
@@ -600,6 +606,7 @@ int scn_dense_terms_backward(int64_t n_points, int32_t n_terms, const float* con
         g.n_points = n_points; g.n_terms = n_terms; g.c_aux = c_aux; g.act = act; g.aux = aux; g.dx = dx;
         g.partial = (float*)workspace;
         for (int k = 0; k < n_terms; ++k) { g.G[k] = G[k]; g.W[k] = W[k]; }
+        // grid cap, G1_U items per thread and trip: tests/test_gpu_dense_terms.py runs past both (CAP_G1, G1_U)
         const int nbs = (int)std::min<int64_t>(1024, (n_points * (c_aux / 4) + 255) / 256);
         const int st_k = with_act(act, [&](auto A) -> int {
             constexpr int ACT = decltype(A)::value;
@@ -642,6 +649,7 @@ int scn_sum_act(int64_t n, int32_t n_terms, const float* const* terms, int32_t a
     }
     if ((uintptr_t)out & 15) return SCN_ERR_BAD_ARG;
     const int64_t n4 = n / 4;
+    // grid cap: tests/test_gpu_dense_terms.py runs past it (CAP_STREAM)
     const dim3 grid((int)std::min<int64_t>(8192, (n4 + 255) / 256));
     if (act != SCN_ACT_NONE && act != SCN_ACT_TANH && act != SCN_ACT_RELU && act != SCN_ACT_LEAKY_RELU) return SCN_ERR_BAD_ARG;
     return with_act(act, [&](auto A) -> int {
@@ -652,6 +660,7 @@ int scn_sum_act(int64_t n, int32_t n_terms, const float* const* terms, int32_t a
 int scn_split_sign(int64_t n, const float* g, float* g_pos, float* g_neg, void* stream) {
     if (!g || !g_pos || !g_neg) return SCN_ERR_BAD_ARG;
     if (n <= 0) return SCN_ERR_BAD_SHAPE;
+    // grid cap: tests/test_gpu_dense_terms.py runs past it (CAP_SPLIT)
     hipLaunchKernelGGL(split_sign_kernel, dim3((int)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, g,
                        g_pos, g_neg);
     SCN_LAUNCH_CHECK();
