@@ -675,6 +675,61 @@ int scn_markov_two_target(int32_t n, const int32_t* prefix_ptr, const int32_t* p
 int scn_markov_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t order, int32_t n_nodes, int32_t d,
                      const int32_t* nbr, const int32_t* deg, const int32_t* counts, double* probs, int32_t* err, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The harmonic projection baseline (projection_model.py, PM:58-126), everything in fp64.  The pieces of a conjugate-gradient solve of
+ * A X = B for k <= SCN_PROJECT_MAX_K columns at once -- X, R, P, AP are [n][k] row-major -- whose step lengths are taken on the device,
+ * one per column, from per-workgroup partial sums that every consumer adds up in the same fixed order (no floating-point atomics: the
+ * same inputs give the same bits); the Gram product A^T B; and the prediction of a batch in one launch.  A wave covers 64 / k rows of
+ * an [n][k] array with one lane per (row, column); k need not be a power of two.  k outside 1 .. SCN_PROJECT_MAX_K is
+ * SCN_ERR_UNSUPPORTED before any launch; n == 0 returns SCN_OK without a launch.  Nothing is allocated, nothing synchronises.
+ *
+ * scn_project_parts (host): the workgroups W <= SCN_PROJECT_MAX_PARTS that scn_csr_apply_f64 and the two updates run for (n, k): their
+ *   partial-sum buffers are [W][k].  scn_gram_parts(n): the same for scn_gram_f64, whose buffer is [W][ka * kb].
+ * scn_csr_apply_f64: y = A x for the CSR operator (rowptr[n_rows + 1], col -- int32, inside [0, n_rows) -- and val), and
+ *   parts[w][c] = the sum over the rows of workgroup w of x[r][c] y[r][c] (in CG: p.Ap).
+ * scn_cg_update_xr: alpha[c] = rr[c] / sum_w pap_parts[w][c]; x += alpha p, r -= alpha ap; rr_parts[w][c] = partial sums of r.r.  A
+ *   column is frozen (alpha = 0, its x and r keep their bits) once it was found converged or when its denominator is not positive.
+ *   first != 0: alpha = 0 for every column (pap_parts, p and ap are not read): the call that takes r0.r0.
+ * scn_cg_update_p: rr_new[c] = sum_w rr_parts[w][c]; a column with rr_new <= tol^2 rr0 is frozen from here on (this covers rr0 = 0, so
+ *   a column that starts converged never divides 0 by 0); beta[c] = rr_new / rr, 0 when frozen; p = r + beta p.  first != 0: rr0 =
+ *   rr_new and p = r.  It leaves rr_new for the next step and two words: flags[2 K + SCN_CG_FLAG_ALL_FROZEN] = 1 when every column is
+ *   frozen, and flags[2 K + SCN_CG_FLAG_ITERATIONS], which the caller sets to -1, = the `it` of the call that first found them so
+ *   (K = SCN_PROJECT_MAX_K).  state holds SCN_CG_STATE_DOUBLES doubles (rr by parity of it [2][K], rr0 [K]), flags SCN_CG_FLAG_WORDS
+ *   int32 (zero at the start but for the -1).  The sequence: xr(it = 0, first), p(it = 0, first), then for it = 1, 2, ...: apply(p ->
+ *   ap), xr(it), p(it); the host reads the all-frozen word whenever it likes.
+ * scn_gram_f64: out[ka][kb] = a^T b for a [n][ka], b [n][kb] (two launches: partial sums per workgroup, then their sum in order).
+ * scn_project_predict: one wave per trajectory i.  c = V^T f over the entries flow_idx / flow_val [flow_ptr[i], flow_ptr[i + 1]) (device
+ *   edge ids; any number of entries, none included), V [n_edges][k] in device edge order, k = 0 .. SCN_PROJECT_MAX_K (0: a complex
+ *   without holes).  For every edge e at the node last[i] (inc_ptr / inc_edge / inc_sign: the node-major incidence table, inc_sign =
+ *   B1[node, e]) with other endpoint j (edge_nodes[n_edges][2]): logits[i][slot(j)] = B1[j, e] (V[e, :] . c), slot(j) the position of j
+ *   in nbr[last[i]][0 .. deg); every other slot of the d keeps logit 0 and enters the soft-max (PM:86-96).  probs[i][d] = the soft-max
+ *   over all d slots, argmax[i] = its first maximum (PM:108).  err (INT32_MAX at the start) is lowered to a row whose last node or
+ *   edge id lies outside the complex or whose tables disagree; such an entry adds nothing.
+ * scn_project_two_target: PM:110-126 on probs [n][d]: t = target[i] (a slot), the other slot is o + (o >= t) with o = (u24 *
+ *   (n_nbrs[i] - 1)) >> 24 from the uniform of (seed, i, 1, 0); score[i] = 1, 0.5 or 0, other[i] = that slot.  n_nbrs[i] < 2 (PM:119
+ *   raises there) or a target outside [0, d) lowers err to i: score 0, other -1. */
+#define SCN_PROJECT_MAX_K 32
+#define SCN_PROJECT_MAX_PARTS 1024
+#define SCN_CG_STATE_DOUBLES (3 * SCN_PROJECT_MAX_K)
+#define SCN_CG_FLAG_WORDS (2 * SCN_PROJECT_MAX_K + 2)
+#define SCN_CG_FLAG_ALL_FROZEN 0
+#define SCN_CG_FLAG_ITERATIONS 1
+int scn_project_parts(int64_t n_rows, int32_t k);
+int scn_gram_parts(int64_t n);
+int scn_csr_apply_f64(int32_t n_rows, int32_t k, const int32_t* rowptr, const int32_t* col, const double* val, const double* x, double* y,
+                      double* parts, void* stream);
+int scn_cg_update_xr(int64_t n, int32_t k, int32_t it, int32_t first, const double* pap_parts, const double* p, const double* ap, double* x,
+                     double* r, double* state, int32_t* flags, double* rr_parts, void* stream);
+int scn_cg_update_p(int64_t n, int32_t k, int32_t it, int32_t first, double tol, const double* rr_parts, const double* r, double* p,
+                    double* state, int32_t* flags, void* stream);
+int scn_gram_f64(int64_t n, int32_t ka, int32_t kb, const double* a, const double* b, double* parts, double* out, void* stream);
+int scn_project_predict(int32_t n, int32_t k, int32_t n_edges, const double* v, const int32_t* flow_ptr, const int32_t* flow_idx,
+                        const double* flow_val, const int32_t* last, int32_t n_nodes, const int32_t* inc_ptr, const int32_t* inc_edge,
+                        const float* inc_sign, const int32_t* edge_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, double* logits,
+                        double* probs, int32_t* argmax, int32_t* err, void* stream);
+int scn_project_two_target(int32_t n, int32_t d, uint64_t seed, const double* probs, const int32_t* target, const int32_t* n_nbrs,
+                           float* score, int32_t* other, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

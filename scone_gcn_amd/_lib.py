@@ -23,6 +23,10 @@ SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
 SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sample_expand
 SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
 SCN_MARKOV_MAX_ORDER = 4          # highest order of the scn_markov_* count tables
+SCN_PROJECT_MAX_K = 32            # widest [n, k] array of the fp64 projection kernels (scn_csr_apply_f64, scn_cg_*, scn_gram_f64)
+SCN_CG_STATE_DOUBLES = 3 * SCN_PROJECT_MAX_K
+SCN_CG_FLAG_WORDS = 2 * SCN_PROJECT_MAX_K + 2
+SCN_CG_FLAG_ALL_FROZEN, SCN_CG_FLAG_ITERATIONS = 2 * SCN_PROJECT_MAX_K, 2 * SCN_PROJECT_MAX_K + 1   # positions in the flags array
 
 
 class WorkListDesc(ctypes.Structure):          # scn_work_list (device pointers)
@@ -173,6 +177,19 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_markov_probs": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "scn_project_parts": (ctypes.c_int, [c_i64, c_i32]),
+    "scn_gram_parts": (ctypes.c_int, [c_i64]),
+    "scn_csr_apply_f64": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_cg_update_xr": (ctypes.c_int, [c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "scn_cg_update_p": (ctypes.c_int, [c_i64, c_i32, c_i32, c_i32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "scn_gram_f64": (ctypes.c_int, [c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_project_predict": (ctypes.c_int, [c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "scn_project_two_target": (ctypes.c_int, [c_i32, c_i32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

@@ -35,7 +35,8 @@ def hyperparams(args=None):
           'multi_hop_skip': 'dense',     # not in the reference: dense | field (field-of-view work lists for the multi-hop forwards)
           'beam': 0,                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
           'multi_hop_samples': 0,        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
-          'markov_order': 1}             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
+          'markov_order': 1,             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
+          'projection': 0}               # 1: the harmonic projection baseline's experiments first (the reference's projection_model.py)
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
@@ -279,11 +280,42 @@ def markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mas
     return results
 
 
+def projection_experiments(sc, folder, seed=0):
+    """The harmonic projection baseline's experiments (the reference's projection_model.py, PM:215-227) with its print labels, on
+    the device (projection_model.Projection_Model): standard test set, reversed test set when the folder has the rev_* files,
+    2-target, transfer (rows i % 3 == 2).  The data set is read again, as PM reads it itself: the baseline works on the unflipped
+    flows whatever -flip_edges says (the result does not depend on the flips).  The basis is computed once.  Returns
+    {"standard": (loss, acc), "reverse": (loss, acc), "two_target": acc, "two_target_slots": drawn slots, "transfer": (loss, acc),
+    "dim", "iterations", "residual"}."""
+    from .dataset_io import load_dataset, load_reverse
+    from .projection_model import Projection_Model
+    X, _, y, _, test_mask, _, last_nodes, _ = load_dataset(folder)
+    last_nodes, test_mask = np.asarray(last_nodes), np.asarray(test_mask)
+    pm = Projection_Model(seed=seed).embed(sc)
+    results = {"dim": pm.dim, "iterations": pm.iterations, "residual": pm.residual}
+    results["standard"] = pm.test(X, last_nodes, y, test_mask)
+    print('Standard experiment loss / acc:', results["standard"])
+    if all(os.path.exists(os.path.join(folder, f)) for f in ('rev_targets.npy', 'rev_last_nodes.npy')) and \
+            any(os.path.exists(os.path.join(folder, 'rev_flows_in' + ext)) for ext in ('.npy', '.npz')):
+        rev_flows, rev_targets, rev_last_nodes = load_reverse(folder)
+        results["reverse"] = pm.test(rev_flows, rev_last_nodes, rev_targets, test_mask)
+        print('Reverse experiment loss / acc:', results["reverse"])
+    rows = np.flatnonzero(test_mask == 1)
+    results["two_target"], results["two_target_slots"] = pm.test_2_target(pm._select(X, rows), last_nodes[rows], np.asarray(y)[rows],
+                                                                          sc.n_nbrs(last_nodes[rows]), seed=seed)
+    print('2-target acc:', results["two_target"])
+    regional_mask = np.array([1 if i % 3 == 2 else 0 for i in range(len(last_nodes))])
+    results["transfer"] = pm.test(X, last_nodes, y, regional_mask)
+    print('Transfer experiment loss / acc:', results["transfer"])
+    return results
+
+
 def train_model(hp=None):
     """Trains a model to predict the next node in each input path (TE:313-510).  With -markov 1 the k-th order Markov baseline
     (-markov_order K, default 1) runs its five experiments first (TE:327-432) and its accuracies go to
     experiment_results["markov"].  The reference then stops (`raise Exception`, TE:433); this driver does not: it goes on to
-    train the model."""
+    train the model.  With -projection 1 the harmonic projection baseline runs next (projection_experiments) and its results go to
+    experiment_results["projection"]; training follows as well."""
     from .scone_trajectory_model import Scone_GCN
     hp = hyperparams() if hp is None else hp
     inputs_all, y_all, train_mask, test_mask, shifts, G_undir, E_lookup, nbrhoods, n_nbrs, target_nodes_all, prefixes = \
@@ -294,6 +326,9 @@ def train_model(hp=None):
     if hp.get('markov', 0) == 1:                                           # TE:327-432
         markov_results = markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask,
                                             order=int(hp.get('markov_order', 1)))
+    projection_results = None
+    if hp.get('projection', 0) == 1:                                       # the reference's projection_model.py, PM:215-227
+        projection_results = projection_experiments(G_undir.complex, 'trajectory_data_1hop_' + hp['data_folder_suffix'])
     scone = Scone_GCN(hp['epochs'], hp['learning_rate'], hp['batch_size'], hp['weight_decay'],
                       skip_mode=hp.get('skip_mode', 'dense'), multi_hop_skip=hp.get('multi_hop_skip', 'dense'))
     if hp['model'] not in MODEL_FUNCS:
@@ -352,6 +387,8 @@ def train_model(hp=None):
             print('Multi hop sampled target probs (%d samples):' % int(hp['multi_hop_samples']), results["multi_hop_sampled"])
     if markov_results is not None:
         results["markov"] = markov_results
+    if projection_results is not None:
+        results["projection"] = projection_results
     scone.experiment_results = results
     return scone, (train_loss, train_acc, test_loss, test_acc)
 
