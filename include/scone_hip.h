@@ -339,6 +339,27 @@ int scn_conv_forward_from_y_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, c
                                  const float* const* W, int32_t channels, int32_t act, float* out,
                                  const uint32_t* keep /* NULL: every row */, void* stream);
 
+/* The mirror on the backward side: the readout's gradient dz of the LAST layer is non-zero only on the rows the readout reads
+ * (scn_readout_backward writes exactly those), so the top layer's backward stages dz only where it was written.  Every
+ * (block, slab) item is still visited and dx is still written in full: this is not the zero-skipping mode; which items are staged
+ * depends on the last nodes, never on a value.
+ * scn_mask_hop: one hop out from a mask of scn_keep_mask's geometry, with the `adj` table of scn_field_lists (block b -> A(b), the
+ *   plan blocks block b's rows stage): out[b][w] = OR over b' in A(b) of in[b'][w], for w < words.  in != out.  Every word of `out`
+ *   is written by one plain store on `stream`: no atomics, no allocation, no synchronisation, no host read.  A block outside
+ *   [0, n_blocks) is only guarded against.  With in = scn_keep_mask's mask, bit (b, s) of out is set wherever some source block of
+ *   b holds a row the readout of slab s touches: the SOURCE mask of the backward.
+ * scn_conv_backward_dzmask = scn_conv_backward with such a source mask.  CONTRACT: every (block, slab) item of dz[0] whose bit in
+ *   the mask that was hopped is clear holds only +-0.  Under it dx, dW and the use of the workspace are bit for bit those of
+ *   scn_conv_backward (dx = NULL included).  NOT READ: aux of the items whose bit in dzmask is clear, and dz of the items that no
+ *   item with a set bit stages (item (b', s) is staged by the items (b, s) with b' in A(b)).  dzmask = NULL: the
+ *   plain call.  With a mask: one group, c_dz = c_aux = 32 on the LDS-blocked plan, dx 16-byte aligned, and at most 64 slabs per
+ *   workgroup of the launch grid (any n_slabs <= 64); SCN_ERR_UNSUPPORTED otherwise, before any launch. */
+int scn_mask_hop(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, const int32_t* adj_blk, const uint32_t* in, uint32_t* out,
+                 void* stream);
+int scn_conv_backward_dzmask(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                             const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
+                             void* workspace, size_t workspace_bytes, const uint32_t* dzmask /* NULL: plain call */, void* stream);
+
 /* Backward of the layer that FOLLOWS the first one, fused with the first layer's weight gradient (what jax.grad of TE:144-149
  * yields for weights[0:6], STM:307, in one pass):
  *   this layer :  dW[slot] += aux^T G_slot                       (as scn_conv_backward; aux = the first layer's output)

@@ -121,6 +121,10 @@ SIGNATURES = {
                                              c_i32, c_void_p, c_void_p, c_void_p]),
     "scn_conv_forward_from_y_keep": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                                     c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    "scn_mask_hop": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_conv_backward_dzmask": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
+                                                c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t,
+                                                c_void_p, c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                         ctypes.POINTER(c_void_p)]),
     "scn_terms_forward": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_i32, c_i32,

@@ -112,7 +112,16 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // FROMY (FIRST, plain C = 32): aux = H1 is not read at all -- `fw` carries the first layer's three weight rows and the tile's sixteen
 // aux values per lane are rebuilt from the y records the lane group already holds for dW_first (the same row_newbcast hand-over,
 // first_layer_value: the bits fwd_c1_kernel would have stored), after the zero-tile early-out.
-template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false>
+// DZMASK (plain C = 32, dense launches): the layer is the LAST one and DZ is the readout's gradient, which lives on the rows the
+// readout reads -- DZ0 carries a bit per (plan block, slab) (a KeepMask's words: scn_keep_mask, one hop out: scn_mask_hop; the kernel's
+// parameter list stays the other forms') that is set wherever one of the block's SOURCE blocks holds such a row.  A visit whose bit
+// is clear would stage and gather zeros only to find the zero-tile early-out: it stages nothing, waits for nothing, requests no aux,
+// gathers nothing and writes the early-out's zero tile.  Every (block, slab) item is still visited and dx is still written in full:
+// this is not the zero-skipping mode.  The decision depends on the trajectories' last nodes, never on a value.  The block's bits
+// come as keep_window's 64-bit window (scn_blk_fwd.inc); with a NaN / Inf weight the plain path has no early-out (0 * Inf), so the
+// window is all ones there and the kernel is the plain one.  A visit with its bit clear reads NEITHER staging buffer: they hold
+// other slabs' data.
+template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false, bool DZMASK = false>
 __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, const float* __restrict__ DZ,
                                                                      const float* __restrict__ DZ0,
                                                                      const float* __restrict__ W0,
@@ -125,6 +134,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                                                                      FirstW fw = FirstW{{nullptr, nullptr, nullptr}}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!FROMY || (FIRST && !PAIR), "the aux-free form exists for the fused-first C = 32 kernel");
+    static_assert(!DZMASK || (!EXT0 && !PAIR && !FIRST && !ACCUM && !FROMY), "the source mask exists for the plain C = 32 kernel");
     static_assert(!FIRST || !EXT0, "the fused first-layer gradient exists for the plain forms (C = 32, and C = 16 on slab pairs)");
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / BK_THREADS;
     constexpr int CH = PAIR ? 16 : 32;                       // channels of a stored point
@@ -197,6 +207,8 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     SCN_UNIT_BEGIN()
         wait_all_and_barrier();
         const BlockMeta m = load_block_c32<BK_THREADS>(P, b, sm);
+        // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
+        const uint64_t dzm = DZMASK ? (keep_window(KeepMask{(const uint32_t*)DZ0, (n_slabs + 31) >> 5}, b, k0) | (w_bad ? ~0ull : 0ull)) : ~0ull;
         __syncthreads();
         const int tw = P.tile_w[b * BK_WAVES + wave];
         const int twu = EXT0 ? 0 : P.tile_wu[b * BK_WAVES + wave];
@@ -222,13 +234,15 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         auto slab_of = [&](int vis, int q) {                     // q-th slab of a visit (the lone last slab stands in for its pair)
             // plain form: wave-uniform -- saying so BEFORE the address arithmetic keeps the 64-bit multiplies on the scalar unit and the
             // LDS-DMA takes (SGPR base + 32-bit lane offset) instead of a 64-bit VGPR address
+            // (DZMASK: dense launches only -- no vector load of a list entry, whose vmcnt(0) would drain the zero tiles at every visit)
+            if (DZMASK) return k0 + vis;
             if (!PAIR) return __builtin_amdgcn_readfirstlane(SLAB_AT(vis));
             return SLAB_AT(2 * vis + q < n_it ? 2 * vis + q : 2 * vis);
         };
         auto src_base = [&](int vis) {
             return (const char*)DZ + (size_t)slab_of(vis, second ? 1 : 0) * slab_bytes;
         };
-        {
+        if (!DZMASK || (dzm & 1)) {
             const char* Xs = src_base(0);
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma_k(i, Xs, 0);
@@ -236,10 +250,51 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         const int rows_left = m.rows - wave * 8;
         f32x4 G[3][4];
         for (int it = 0; it < n_vis; ++it) {
+            if (DZMASK) {
+                // A RUN of visits whose bit is clear -- no source of the (block, slab) holds a row the readout wrote: each is the
+                // zero-tile early-out below without the staging, the wait, the aux requests and the gather that lead to it.  Its own
+                // loop, on scalars and what it makes itself (lane index, zeros, row count): a value carried through the live visits
+                // is spilled there, and a reload is a vmcnt(0) wait -- stores count on vmcnt, so it would drain the zero tiles in
+                // flight, as the wait at the top of a staged visit does.  The barrier stays on every visit (workgroup-uniform bits:
+                // it is needed only where a buffer is published or about to be overwritten; kept until measured otherwise).
+                // The wave's 8-row tile is 4 KB in a row: four 16-byte stores per lane, row 2 j + (lane >> 5).
+                const int rows_left_s = __builtin_amdgcn_readfirstlane(rows_left);
+                while (!((dzm >> it) & 1)) {
+                    STAMP_START();
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                    if (it + 1 < n_vis && ((dzm >> ((it + 1) & 63)) & 1)) {      // the next visit is a staged one
+                        const char* Xn0 = src_base(it + 1);
+#pragma unroll
+                        for (int i = 0; i < NDMA; ++i) dma_k(i, Xn0, (it + 1) & 1);
+                    }
+                    if (dx) {
+                        float* dp0 = dx + (((size_t)slab_of(it, 0) * n_rows + m.row0 + wave * 8) * BK_NS) * CH;
+                        int ln;
+                        float z;
+                        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_mov_b32 %1, 0" : "=&v"(ln), "=v"(z));
+#ifdef SCN_AB_DZMASK_DWORD_STORES                                       // diagnostic builds: the early-out's sixteen dword stores per lane
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (2 * (r >> 2) + (ln >> 5) < rows_left_s) SCN_ST_STREAM(dp0 + (ln & 31) + 128 * (ln >> 5) + ((r & 3) + 8 * (r >> 2)) * 32, z);
+#else
+                        const f32x4 z4 = {z, z, z, z};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (2 * j + (ln >> 5) < rows_left_s) SCN_ST_STREAM((f32x4*)(dp0 + (j * 64 + ln) * 4), z4);
+#endif
+                    }
+                    STAMP_ADD(4);
+                    if (++it == n_vis) break;
+                }
+                if (it == n_vis) break;
+            }
             const int slab = slab_of(it, PAIR ? p >> 4 : 0);          // PAIR: lanes p >= 16 hold slab B's channels
             const bool lane_live = !PAIR || p < 16 || 2 * it + 1 < n_it;
             const uint32_t bufbit = (uint32_t)((it & 1) << 16);
             const uint32_t cbs[4] = {cqs[0] | bufbit, cqs[1] | bufbit, cqs[2] | bufbit, cqs[3] | bufbit};
+            // DZMASK (workgroup-uniform, scalar): the next visit's slab is to be staged (it + 1 < n_vis <= 64 where it is used)
+            const bool dz_next = !DZMASK || ((dzm >> ((it + 1) & 63)) & 1);
             STAMP_START();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             STAMP_ADD(0);
@@ -328,7 +383,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 // neighbourhood -- nearly every tile of a real batch leaves here.  Its share of the staging is still issued.
                 if (!w_bad && mgb == 0) {
                     const int vdma0 = it + 1;
-                    if (vdma0 < n_vis) {
+                    if (vdma0 < n_vis && dz_next) {
                         const char* Xn0 = src_base(vdma0);
 #pragma unroll
                         for (int i = 0; i < NDMA; ++i) dma_k(i, Xn0, vdma0 & 1);
@@ -403,7 +458,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             }
             // ---------------- CONTRACT
             const int vdma = it + 1;                                     // the visit whose slab this contraction stages
-            const bool more = vdma < n_vis;
+            const bool more = vdma < n_vis && dz_next;                  // (DZMASK: a slab without a source in the mask is not staged)
             const char* Xn = src_base(more ? vdma : it);
             const int nbuf = vdma & 1;
             auto side = [&](int k) {                                     // (all eight right after the barrier instead: +2 %)
@@ -547,6 +602,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
 // fw carry in each:
 template <int ACT> constexpr auto bwd_c32_plain = bwd_c32_bf16_kernel<ACT>;                                  // DZ = dz, DZ0 null
 template <int ACT> constexpr auto bwd_c32_pair = bwd_c32_bf16_kernel<ACT, false, true>;                      // the same at C = 16, on slab pairs
+template <int ACT> constexpr auto bwd_c32_plain_dzmask = bwd_c32_bf16_kernel<ACT, false, false, false, false, false, true>;   // DZ = dz staged by DZ0 = source mask words
 template <int ACT> constexpr auto bwd_c32_power = bwd_c32_bf16_kernel<ACT, true>;                            // DZ = g1 = S^T dz, DZ0 = dz
 template <int ACT> constexpr auto bwd_c32_power_pair = bwd_c32_bf16_kernel<ACT, true, true>;                 // the same at C = 16
 template <int ACT> constexpr auto bwd_c32_accum = bwd_c32_bf16_kernel<ACT, false, false, false, true>;       // DZ0 = dx_partial, added to dx

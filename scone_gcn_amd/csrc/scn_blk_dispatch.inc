@@ -82,7 +82,8 @@ constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
 constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
 constexpr KeepMask NO_KEEP{nullptr, 0};
 
-// The keep mask of a launch (scn_conv_forward_keep / _from_y_keep): words per block from the slab count.  A workgroup holds the bits
+// The keep mask of a launch (scn_conv_forward_keep / _from_y_keep; the source mask of scn_conv_backward_dzmask has its geometry and
+// its window limit): words per block from the slab count.  A workgroup holds the bits
 // of its slab range in one 64-bit window (keep_window): false where the grid hands one more than that.
 static bool keep_fits(unsigned gy, int n_slabs) { return (n_slabs + (int)gy - 1) / (int)gy <= KEEP_WINDOW; }
 static KeepMask keep_mask_of(const uint32_t* keep, int n_slabs) { return KeepMask{keep, (n_slabs + 31) / 32}; }
@@ -209,15 +210,20 @@ size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, cons
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
                      float* const* dW, void* ws, size_t ws_bytes, const WorkList* wlp, hipStream_t st,
-                     const float* dx_partial) {           // dx_partial (32 -> 32 only): dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
+                     const float* dx_partial,             // dx_partial (32 -> 32 only): dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
+                     const uint32_t* dzmask) {            // dzmask (32 -> 32, dense, no partial): dz is staged by the mask, see there
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const int cd = c_dz[0];
     float* partial = (float*)ws;
     const size_t lds = bwd_lds();
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
     if (dx_partial && (c_aux != 32 || !dx)) return SCN_ERR_UNSUPPORTED;
+    if (dzmask && (dx_partial || wl.block || c_aux != 32 || cd != 32 || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
     const int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
+        if (dzmask)                                              // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
+            return launch_checked(bwd_c32_plain_dzmask<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], (const float*)dzmask, W[0], W[1],
+                                  W[2], aux, dx, partial, L.nr, L.nc, n_slabs, wl, nullptr, NO_FIRSTW);
         const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
                               n_slabs, wl, nullptr, NO_FIRSTW);

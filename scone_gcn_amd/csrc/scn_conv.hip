@@ -26,7 +26,7 @@ size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, cons
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
                      float* const* dW, void* ws, size_t ws_bytes, const WorkList* wl, hipStream_t st,
-                     const float* dx_partial = nullptr);
+                     const float* dx_partial = nullptr, const uint32_t* dzmask = nullptr);
 bool blocked_spmm_supported(const scn_conv_s* c, int k);
 bool blocked_power_supported(const scn_conv_s* c, int ns, int ch);
 size_t blocked_power_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
@@ -703,6 +703,24 @@ int scn_conv_backward_accumulate(scn_conv_t c, int32_t n_slabs, int32_t ns, cons
     if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
     return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
                             (hipStream_t)stream, dx_partial);
+}
+
+int scn_conv_backward_dzmask(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                             const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
+                             void* workspace, size_t workspace_bytes, const uint32_t* dzmask, void* stream) {
+    if (!dzmask)
+        return scn_conv_backward_list(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr, stream);
+    if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
+    for (int s = 0; s < c->n_slots; ++s)
+        if (!W[s] || !dW[s]) return SCN_ERR_BAD_ARG;
+    if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(dx) & 15) return SCN_ERR_UNSUPPORTED;           // (the zero tiles go out in 16-byte stores)
+    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
+    return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
+                            (hipStream_t)stream, nullptr, dzmask);
 }
 
 int scn_conv_backward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,

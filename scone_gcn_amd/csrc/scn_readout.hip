@@ -340,6 +340,26 @@ __global__ __launch_bounds__(256) void keep_mask_kernel(int n, int ns, const int
     }
 }
 
+// One hop out from a keep mask (scn_mask_hop), for the top layer's backward (scn_conv_backward_dzmask).  readout_bwd_kernel writes dz
+// on exactly the rows readout_fwd_kernel reads of H -- the edges inc_edge[inc_ptr[v] .. inc_ptr[v + 1]) of every neighbour v >= 0 of
+// the last node, less the edges it skips as handled from the other endpoint, which are among them -- so the keep mask M0 of the
+// forward is also where the readout's gradient can be non-zero.  Block b of the backward stages the blocks of A(b) (the `adj` table
+// of scn_field_lists): out[b][w] = OR of in[b'][w] over b' in A(b).  Pull form, thread = (b, w): one plain store per word, no atomics,
+// the result does not depend on any order.  A block outside [0, n_blocks) is only guarded against, as in field_hop_kernel.
+__global__ __launch_bounds__(256) void mask_hop_kernel(int n_blocks, int words, const int32_t* __restrict__ adj_ptr,
+                                                       const int32_t* __restrict__ adj_blk, const uint32_t* __restrict__ in,
+                                                       uint32_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)n_blocks * words) return;
+    const int b = (int)(t / words), w = (int)(t - (int64_t)b * words);
+    uint32_t acc = 0;
+    for (int k = adj_ptr[b]; k < adj_ptr[b + 1]; ++k) {
+        const int b2 = adj_blk[k];
+        if (b2 >= 0 && b2 < n_blocks) acc |= in[(size_t)b2 * words + w];
+    }
+    out[t] = acc;
+}
+
 __global__ __launch_bounds__(64) void node_readout_fwd_kernel(int ns, int n_nodes, const float* __restrict__ X,
                                                               const int32_t* __restrict__ nbr, int max_deg,
                                                               const int32_t* __restrict__ last_nodes,
@@ -703,6 +723,17 @@ int scn_keep_mask(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, c
     SCN_HIP_TRY(hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)n_blocks * words, st));
     hipLaunchKernelGGL(keep_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, ns, node, n_nodes, top_ptr, top_blk, n_blocks,
                        words, mask);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_mask_hop(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, const int32_t* adj_blk, const uint32_t* in, uint32_t* out,
+                 void* stream) {
+    if (!adj_ptr || !adj_blk || !in || !out || in == out) return SCN_ERR_BAD_ARG;
+    if (n_blocks <= 0 || words <= 0) return SCN_ERR_BAD_SHAPE;
+    const int64_t n = (int64_t)n_blocks * words;
+    hipLaunchKernelGGL(mask_hop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_blocks, words, adj_ptr,
+                       adj_blk, in, out);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

@@ -87,6 +87,12 @@ RECOMPUTE_FIRST = True
 # built on the device from the last nodes (SconePlan.conv_stack, scn_keep_mask, scn_conv_forward_keep).  Every tile is still staged,
 # gathered and contracted: this is not the zero-skipping mode.  False: the whole tensor is stored.
 KEEP_LAST = True
+# The mirror on the backward side: the readout's gradient dZ_L is non-zero only on those same rows, yet the top layer's backward staged
+# and gathered all of it -- zeros -- to find its zero-tile early-out.  With the keep mask hopped once over the block adjacency
+# (scn_mask_hop) the top layer's backward stages dZ_L only where a source block holds a row the readout wrote; elsewhere it writes its
+# zero tile without staging, gathering or reading aux (SconePlan._top_dz_mask, scn_conv_backward_dzmask).  Every (block, slab) item is
+# still visited and dX is written in full: this is not the zero-skipping mode.  False: the plain backward.
+TOP_DZ_MASK = True
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
 # step, one launch against the layer-by-layer kernels, ms (tools/small_step.py, profiles/r04_small_step_ab.txt):
@@ -250,6 +256,19 @@ def keep_mask_host(nodes, ns, top_ptr, top_blk, n_blocks):
     return mask
 
 
+def mask_hop_host(mask, adj_ptr, adj_blk):
+    """NumPy restatement of scn_mask_hop (include/scone_hip.h): out[b] = OR of mask[b'] over b' in A(b) = adj_blk[adj_ptr[b] :
+    adj_ptr[b + 1]], word by word.  A block outside the mask's rows contributes nothing."""
+    mask = np.asarray(mask, np.uint32)
+    out = np.zeros_like(mask)
+    for b in range(mask.shape[0]):
+        src = np.asarray(adj_blk[adj_ptr[b]:adj_ptr[b + 1]], np.int64)
+        src = src[(src >= 0) & (src < mask.shape[0])]
+        if len(src):
+            out[b] = np.bitwise_or.reduce(mask[src], axis=0)
+    return out
+
+
 class FieldTables(NamedTuple):
     """Device copies of field_tables for one plan."""
     n_blocks: int
@@ -319,18 +338,28 @@ class ConvOp:
         check(_lib.load().scn_conv_plan_info(self.handle, ctypes.byref(nb), ctypes.byref(ms)), "scn_conv_plan_info")
         return nb.value, ms.value
 
-    def keep_mask(self, nodes, ns, n_nodes, tabs):
+    def keep_mask(self, nodes, ns, n_nodes, tabs, key="keep_mask"):
         """The keep mask of a last layer's forward (scn_keep_mask): int32 words [n_blocks][ceil(n_slabs / 32)], bit (b, s) set iff a
         leaf of slab s stands on a node whose readout reads a row of plan block b.  nodes: int32 device tensor, one per trajectory;
-        tabs: the plan's FieldTables.  A fresh buffer per call, filled on the current stream (nothing is kept on the operator)."""
+        tabs: the plan's FieldTables.  A fresh buffer per call, filled on the current stream (nothing is kept on the operator).
+        key: the timer's name of the launch (the top layer's backward builds the same mask under its own)."""
         n = nodes.numel()
         words = (-(-n // ns) + 31) // 32
         mask = torch.empty((tabs.n_blocks, words), device=nodes.device, dtype=torch.int32)
-        with _timed("keep_mask", _nbytes(mask, nodes)):
+        with _timed(key, _nbytes(mask, nodes)):
             check(_lib.load().scn_keep_mask(n, ns, _dev(nodes, torch.int32), n_nodes, _dev(tabs.top_ptr, torch.int32),
                                             _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32), _stream()),
                   "scn_keep_mask")
         return mask
+
+    def mask_hop(self, mask, tabs):
+        """One hop out from a keep_mask() over the plan's block adjacency (scn_mask_hop): bit (b, s) set iff a block that b's rows
+        stage has its bit set in `mask` -- the source mask of the top layer's backward.  A fresh buffer per call, as keep_mask."""
+        out = torch.empty_like(mask)
+        with _timed("dz_mask_hop", _nbytes(mask, out)):
+            check(_lib.load().scn_mask_hop(tabs.n_blocks, mask.shape[1], _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32),
+                                           _dev(mask, torch.int32), _dev(out, torch.int32), _stream()), "scn_mask_hop")
+        return out
 
     def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None):
         """wl: WorkList (zero-skipping): only the listed items of `out` are written; `out` must be given, all-zero.
@@ -370,12 +399,16 @@ class ConvOp:
                                             wl.ref() if wl is not None else None, _stream()), "scn_conv_forward")
         return out
 
-    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None):
+    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None):
         """dWs: list of tensors ACCUMULATED into.  Returns dx or None.  wl: WorkList (zero-skipping): only the listed
         items of `dx` are written (it must be given, all-zero) and only they contribute to dWs.
-        dx_partial: tensor of dx's shape ADDED to the input gradient (scn_conv_backward_accumulate; dx defaults to it, in place)."""
+        dx_partial: tensor of dx's shape ADDED to the input gradient (scn_conv_backward_accumulate; dx defaults to it, in place).
+        dz_mask: mask_hop() of the keep mask outside whose items dzs[0] is all-zero (top layer, dense): dz is staged only where the
+        mask is set, with the plain call's results; returns False (nothing launched, dWs untouched) when the shape is not served
+        (scn_conv_backward_dzmask)."""
         lib = _lib.load()
         assert wl is None or (dx is not None or not need_dx)
+        assert dz_mask is None or (wl is None and dx_partial is None)
         if dx_partial is not None:
             assert wl is None and need_dx and tuple(dx_partial.shape) == tuple(aux.shape)
             dx = dx_partial if dx is None else dx
@@ -397,6 +430,15 @@ class ConvOp:
                                                        _dev(dx_partial), _dev(dx), _ptrs(dWs), *ws, _stream()),
                       "scn_conv_backward_accumulate")
             return dx
+        if dz_mask is not None:
+            # (the key of the plain backward; the staged items are left out of the byte model, as the kept stores of the forward are)
+            with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
+                        _nbytes(dx if need_dx else None) + self.csr_bytes):
+                st = lib.scn_conv_backward_dzmask(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
+                                                  _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _dev(dz_mask, torch.int32), _stream())
+            if not _served(st, "scn_conv_backward_dzmask"):
+                return False
+            return dx if need_dx else None
         with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
                     None if wl is not None else _nbytes(aux, dx if need_dx else None, *dzs) + self.csr_bytes):
             check(lib.scn_conv_backward_list(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
@@ -1394,6 +1436,27 @@ class SconePlan(Plan):
                                                _dev(dz_top), _stream()), "scn_readout_clear_dz")
         self._dz_zero.setdefault(key, []).append(dz_top)
 
+    def _top_dz_mask(self, dz_top, aux, activity, last_dev):
+        """The source mask the top layer's backward stages the readout gradient by, or None: plain scone plan on its blocked operator
+        with symmetric shifts (conv_T is conv: the plan's block adjacency is the forward operator's), dense launches, 32 -> 32
+        channels, the pooled all-zero buffer (above SMALL_DZ_BYTES; below it dz_top is zeroed by the readout's launch and the plain
+        call is cheaper than two mask launches) and the plan's tables (field_tables_dev; not built under a graph capture).  Built
+        from the last nodes the readout's backward got, for this call alone: nothing is kept on the plan.  TOP_DZ_MASK is the tests'
+        and A/B's switch."""
+        if not TOP_DZ_MASK or last_dev is None or activity is not None or not self.fused_conv or self.conv_T is not self.conv:
+            return None
+        S, E, ns, C = dz_top.shape
+        if ns != NS or C != 32 or aux.shape[3] != 32 or last_dev.numel() != S * ns or last_dev.dtype != torch.int32:
+            return None
+        if dz_top.numel() * 4 <= self.SMALL_DZ_BYTES or not self._blocked():
+            return None
+        if self._field is None and torch.cuda.is_current_stream_capturing():
+            return None
+        tabs = self.field_tables_dev()
+        if tabs is None:
+            return None
+        return self.conv.mask_hop(self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs, key="dz_mask"), tabs)
+
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         if saved.wide:
             return self._wide_backward(saved, logp, d_logp, last_dev, weights, grads)
@@ -1423,8 +1486,15 @@ class SconePlan(Plan):
             else:
                 assert not activity or i > 0, "zero-skipping needs the first-layer fast path"
                 dx = self._zeros(hs[i].shape) if activity else None
-                dz = self.conv_T.backward([dz], weights[3 * i:3 * i + 3], hs[i], self.act, i > 0, grads[3 * i:3 * i + 3],
-                                          dx=dx, wl=wl_out)
+                src_mask = self._top_dz_mask(dz_top, hs[i], activity, last_dev) if i == L - 1 and i >= 2 else None
+                dz_in_grad = False                      # the top layer: dz staged only where the readout wrote it (False: not served)
+                if src_mask is not None:
+                    dz_in_grad = self.conv_T.backward([dz], weights[3 * i:3 * i + 3], hs[i], self.act, True, grads[3 * i:3 * i + 3],
+                                                      dz_mask=src_mask)
+                if dz_in_grad is False:
+                    dz_in_grad = self.conv_T.backward([dz], weights[3 * i:3 * i + 3], hs[i], self.act, i > 0, grads[3 * i:3 * i + 3],
+                                                      dx=dx, wl=wl_out)
+                dz = dz_in_grad
             if i == L - 1:                              # the top layer is done with the readout gradient: wipe and keep it
                 self._release_top(dz_top, key, last_dev)
             elif activity:
