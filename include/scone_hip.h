@@ -316,8 +316,10 @@ int scn_conv_backward_fused_first_from_y(scn_conv_t conv_t, int32_t n_slabs, int
                                          const scn_work_list* wl /* NULL: dense */, void* stream);
 
 /* The LAST layer's output is read by the readout alone, and only on the edges incident to a neighbour of each trajectory's last
- * node (scn_readout_forward / scn_readout_backward): a few dozen rows per trajectory.  The *_keep forwards compute every tile as the
- * plain calls do and STORE only the (plan block, slab) items of a keep mask; which items depends on the last nodes, never on a value.
+ * node (scn_readout_forward / scn_readout_backward): a few dozen rows per trajectory.  The *_keep forwards VISIT only the (plan
+ * block, slab) items of a keep mask: at 32 channels an item whose bit is clear is not staged, gathered or contracted (at 16 channels,
+ * slab pairs, it is computed and dropped), and in either case no row outside the kept items is written; a kept item is computed as
+ * the plain calls compute it.  Which items are kept depends on the last nodes, never on a value.
  * scn_keep_mask: leaf i < n belongs to slab i / ns and stands on node[i] (the readout's last_nodes); with the `top` table of
  *   scn_field_lists (node v -> T(v), the plan blocks holding a row the readout of v reads)
  *     mask[n_blocks][words], words = ceil(n_slabs / 32), n_slabs = ceil(n / ns):
@@ -327,8 +329,9 @@ int scn_conv_backward_fused_first_from_y(scn_conv_t conv_t, int32_t n_slabs, int
  *   through it); so is a block outside [0, n_blocks).
  * scn_conv_forward_keep / scn_conv_forward_from_y_keep = scn_conv_forward / scn_conv_forward_from_y with such a mask (device,
  *   geometry as above for the call's n_slabs): the rows of every kept (block, slab) of `out` hold the bits the plain call writes,
- *   every other row of `out` is LEFT UNTOUCHED -- it holds whatever the buffer held.  keep = NULL: every row is stored (the plain
- *   call).  With a mask: one group, c_in = c_out = 32 or 16 (from y: 32) on the LDS-blocked plan, and at most 64 slabs per
+ *   every other row of `out` is LEFT UNTOUCHED -- it holds whatever the buffer held.  NOT READ (32 channels): the input of the
+ *   items that no kept item stages (item (b', s) is staged by the kept items (b, s) with b' in A(b), the `adj` table of
+ *   scn_field_lists).  keep = NULL: every row is stored (the plain call).  With a mask: one group, c_in = c_out = 32 or 16 (from y: 32) on the LDS-blocked plan, and at most 64 slabs per
  *   workgroup of the launch grid (any n_slabs <= 64); SCN_ERR_UNSUPPORTED otherwise, before any launch. */
 int scn_keep_mask(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
                   int32_t n_blocks, uint32_t* mask, void* stream);

@@ -118,7 +118,7 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wlp,
                     hipStream_t st, const float* partial,              // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
-                    const uint32_t* keep) {                            // keep (32 -> 32 and 16 -> 16, dense, no partial): stores by the mask
+                    const uint32_t* keep) {                            // keep (32 -> 32 and 16 -> 16, dense, no partial): only the mask's items are stored (32 -> 32: visited)
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const int ci = c_in[0];
     if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
@@ -169,7 +169,7 @@ bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
 }
 
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st, const uint32_t* keep) {      // keep: stores by the mask (see blocked_forward)
+                           float* out, hipStream_t st, const uint32_t* keep) {      // keep: visits and stores by the mask (see blocked_forward)
     const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
     const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds);

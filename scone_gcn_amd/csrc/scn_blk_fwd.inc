@@ -220,14 +220,17 @@ template <int I> __device__ __forceinline__ void fwd_prio() { __builtin_amdgcn_s
 // expanded between the wave's two phases; the slab barrier waits for the LDS writes (lgkmcnt) instead of the LDS-DMA (vmcnt).
 constexpr int W16_FIRSTW_BYTES = 3 * 32 * 4;              // FROMY: the first layer's weights [g][32], behind the plain form's extra bytes
 // KEEP (plain and from-y forms, dense launches): the layer is the LAST one and only the readout reads its output -- `km` holds a bit
-// per (plan block, slab) (scn_keep_mask) and a finished tile is stored only where its bit is set.  Staging, gather, contraction and
-// early-out are the other forms': what changes is whether pend[] is written out.  The decision depends on the trajectories' last
-// nodes, never on a value.
-// keep_window: the bits of block b for the KEEP_WINDOW slabs from `first` on (bit j = slab first + j), fetched ONCE in the block
-// prologue, beside the block's metadata, made wave-uniform and claimed there: nothing of it is in flight when the slab loop starts (a
+// per (plan block, slab) (scn_keep_mask) and only the items whose bit is set are VISITED: a block's slab loop runs over the set
+// bits of its window (visit i = the slab of the i-th set bit), a block without one is left before its metadata is read.  An item
+// whose bit is clear is not staged, gathered or contracted, and no byte of its rows is written; a visit that runs is staged,
+// gathered, contracted (or early-outed) and stored exactly as in the other forms, so a kept row holds the plain forward's bits.
+// The decision depends on the trajectories' last nodes, never on a value.  (The slab-pair kernel fwd_c16_w16_kernel<KEEP> still
+// visits every pair and only drops the store.)
+// keep_window: the bits of block b for the KEEP_WINDOW slabs from `first` on (bit j = slab first + j), fetched ONCE per block,
+// ahead of the block's metadata, made wave-uniform and claimed there: nothing of it is in flight when the slab loop starts (a
 // scalar load in flight there turns the gather's counted lgkmcnt waits into lgkmcnt(0), a vector load is followed by vmcnt(0), a
-// wait for the LDS-DMA just issued: profiles/HISTORY.md section 3.2); the slab loop shifts two SGPRs.  The host hands a workgroup
-// at most KEEP_WINDOW slabs.
+// wait for the LDS-DMA just issued: profiles/HISTORY.md section 3.2); the slab loop walks it in SGPRs (scn_keep_bits.h).  The host
+// hands a workgroup at most KEEP_WINDOW slabs.
 constexpr int KEEP_WINDOW = 64;
 __device__ __forceinline__ uint64_t keep_window(const KeepMask km, int b, int first) {
     const uint32_t* mw = km.bits + (size_t)b * km.words;
@@ -316,6 +319,16 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     auto run = [&](auto late_c) {
     constexpr int late = decltype(late_c)::value;
     SCN_UNIT_BEGIN()
+        // KEEP: the block's window FIRST, cut to this workgroup's slab range (the bits above n_it are other workgroups' slabs); a
+        // block without a kept slab is left here, before its metadata is touched, before the barrier and before any LDS write.
+        // The window is the same scalar in all sixteen waves, so they leave together; a tile pending from an earlier block stays
+        // pending.  (dense launches only: k0 = slab0)
+        uint64_t keep = ~0ull;
+        if (KEEP) {
+            keep = keep_cut(keep_window(km, b, k0), n_it);
+            if (keep == 0) continue;
+        }
+        const int n_vis = KEEP ? keep_count(keep) : n_it;             // visits of this block: visit i = the slab of the i-th set bit
         wait_all_and_barrier();
         BlockMeta m;
         {
@@ -333,7 +346,6 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             if (tid < BK_R) sm.self[tid] = P.self_slot[(size_t)b * BK_R + tid];
             if (tid < W16_WAVES) tws[tid] = P.tile_w4[b * W16_WAVES + tid];
         }
-        const uint64_t keep = KEEP ? keep_window(km, b, k0) : ~0ull;   // bit `it` = slab k0 + it of this block is stored (dense launches only)
         __syncthreads();
         const int tw = tws[wave];                    // width of this wave's own quad
         const int twu = EXT0 ? 0 : P.tile_wu4[b * W16_WAVES + wave];
@@ -355,6 +367,14 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         // slab indices are wave-uniform; saying so BEFORE the address arithmetic keeps the 64-bit multiplies on the scalar unit (the
         // listed form loads them with a vector load: left to itself the compiler does slab * slab_bytes in quarter-rate v_mul_*_u32)
         auto slab_at = [&](int it) { return SLAB_AT_U(it); };
+        // KEEP: the visits are the set bits of `keep`, consumed in ascending order.  Each consumer holds a CURSOR, a copy of the
+        // window whose lowest set bit is the visit it handles next (keep_first), and drops that bit when done (keep_next): two
+        // SGPRs and a few scalar instructions per visit, no table and no memory operation inside the slab loop (see keep_window).
+        // slab_of(w, it): the slab of visit `it`, `w` being a cursor that stands at it.  The visit INDEX still counts 0, 1, 2, ...:
+        // buffer parity, the stagger and the vdma guards run on it as in the other forms.
+        auto slab_of = [&](uint64_t w, int it) { return KEEP ? k0 + keep_first(w) : slab_at(it); };
+        uint64_t cw = keep;                                           // the contraction's cursor
+        uint64_t yw = keep_next(keep);                                // FROMY: the record loads' cursor, one visit ahead
         auto slab_base = [&](int slab) { return (const char*)X + (size_t)slab * slab_bytes; };   // SGPR base + 32-bit lane offset in the LDS-DMA
         // FROMY staging: this thread's four records of a slab (slots ys_slot + 32 i, trajectory ys_n), then their channel quad ys_cq
         // of H1 into the image: piece chunk ys_n * 8 + ys_cq of slot s lives at s * 512 + swz32(s, chunk) * 16 (what the LDS-DMA builds)
@@ -388,10 +408,10 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             }
         };
         if (FROMY) {
-            y_load(slab_at(0));
+            y_load(slab_of(keep, 0));
             y_expand(0);
         } else {
-            const char* Xs = slab_base(slab_at(0));
+            const char* Xs = slab_base(slab_of(keep, 0));
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma(i, Xs, 0);
         }
@@ -400,8 +420,8 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         // behind waves 0-7 (every SIMD hosts two of each): while one half gathers slab v the other contracts slab v - 1, between
         // the same two slab barriers.  A late wave carries its gathered z across the barrier; its share of the next LDS-DMA is one
         // visit further ahead (slab v + 2), the early waves' as before (slab v + 1).
-        if (!FROMY && late && n_it > 1) {              // the late waves' share of slab 1 has no contraction to ride in
-            const char* Xs = slab_base(slab_at(1));
+        if (!FROMY && late && n_vis > 1) {             // the late waves' share of visit 1 has no contraction to ride in
+            const char* Xs = slab_base(slab_of(keep_next(keep), 1));
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma(i, Xs, 1);
         }
@@ -439,11 +459,13 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         // ---------------- CONTRACT of slab `it` from z: out^T tile (16 channels x 16 points) x 2 channel tiles; the LDS-DMA of the
         // slab this wave stages next and the previous tile's two 16-byte stores ride inside the chains
         auto contract_phase = [&](int it) {
-            const int slab = slab_at(it);
+            const int slab = slab_of(cw, it);
             const size_t tile0 = tile_of(slab);
             const int vdma = it + 1 + late;
-            const bool more = vdma < n_it;
-            const char* Xn = slab_base(more ? slab_at(vdma) : slab);
+            const bool more = vdma < n_vis;
+            const uint64_t cw1 = keep_next(cw), cwd = late ? keep_next(cw1) : cw1;   // KEEP: the cursor at visit it + 1 and at visit vdma
+            const char* Xn = slab_base(more ? slab_of(cwd, vdma) : slab);
+            if (KEEP) cw = cw1;
             const int nbuf = vdma & 1;
 #if defined(SCN_FWD_FLOOR) && SCN_FWD_FLOOR == 1
             if (more) {
@@ -522,12 +544,12 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             }
             // D: column = lane&15 = point, row = 4*kq + r = channel within the 16-channel tile
             pend_ptr = out + tile0 + lane_out;
-            pend_valid = rt < m.rows && (!KEEP || ((keep >> it) & 1) != 0);   // decided by the visit that made the tile, never again at store time
+            pend_valid = rt < m.rows;                                // decided by the visit that made the tile, never again at store time (KEEP: every visit that runs is kept)
             STAMP_ADD(3);
         };
         // One barrier interval per slab (+ one for the late waves' last contraction).  Early waves: gather(v), contract(v); late
         // waves: contract(v - 1), gather(v).
-        for (int v = 0; v <= n_it; ++v) {
+        for (int v = 0; v <= n_vis; ++v) {
             STAMP_START();
 #ifndef SCN_FWD_FREERUN               // (diagnostic build, results WRONG by design: no slab barrier at all -- the no-synchronisation floor)
             // FROMY: the image of slab v was WRITTEN by this workgroup's waves (and every LDS read of the buffer it replaces has
@@ -539,10 +561,13 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             asm volatile("" ::: "memory");
 #endif
             STAMP_ADD(1);
-            const bool stage = FROMY && v + 1 < n_it;          // both halves stage slab v + 1 during interval v
-            if (stage) y_load(slab_at(v + 1));
+            const bool stage = FROMY && v + 1 < n_vis;         // both halves stage visit v + 1 during interval v
+            if (stage) {
+                y_load(slab_of(yw, v + 1));
+                if (KEEP) yw = keep_next(yw);
+            }
             if (!late) {
-                if (v < n_it) {
+                if (v < n_vis) {
                     SCN_FWD_PRIO_GATHER();
                     gather_phase(v);
                     if (stage) y_expand((v + 1) & 1);
@@ -552,7 +577,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
                 if (v > 0) contract_phase(v - 1);
                 if (stage) y_expand((v + 1) & 1);
                 SCN_FWD_PRIO_GATHER();
-                if (v < n_it) gather_phase(v);
+                if (v < n_vis) gather_phase(v);
             }
         }
     }
@@ -576,8 +601,8 @@ template <int ACT> constexpr auto fwd_c32_plain = fwd_c32_w16_kernel<ACT>;      
 template <int ACT> constexpr auto fwd_c32_power = fwd_c32_w16_kernel<ACT, true>;                  // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
 template <int ACT> constexpr auto fwd_c32_accum = fwd_c32_w16_kernel<ACT, false, true>;           // X0 = partial pre-activation, added before act
 template <int ACT> constexpr auto fwd_c32_from_y = fwd_c32_w16_kernel<ACT, false, false, true>;   // X = the first layer's records y, fw = its weight rows
-template <int ACT> constexpr auto fwd_c32_plain_keep = fwd_c32_w16_kernel<ACT, false, false, false, true>;   // plain, stores by km
-template <int ACT> constexpr auto fwd_c32_from_y_keep = fwd_c32_w16_kernel<ACT, false, false, true, true>;   // from y, stores by km
+template <int ACT> constexpr auto fwd_c32_plain_keep = fwd_c32_w16_kernel<ACT, false, false, false, true>;   // plain, visits by km
+template <int ACT> constexpr auto fwd_c32_from_y_keep = fwd_c32_w16_kernel<ACT, false, false, true, true>;   // from y, visits by km
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = C_out = 16, sixteen waves, f16 hi + lo split -- the C=32 machinery on TWO slabs at a time:

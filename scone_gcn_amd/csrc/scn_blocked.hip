@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "scn_internal.h"
+#include "scn_keep_bits.h"
 
 namespace scn {
 

@@ -42,15 +42,19 @@ class KernelTimer:
         return {k: (len(v), sum(a.elapsed_time(b) for a, b, _ in v) / max(len(v), 1)) for k, v in self.records.items()}
 
     def table(self):
-        """key -> {"launches", "avg_ms", "alg_bytes" (mean per launch, None where no model is stated), "GB/s"}."""
+        """key -> {"launches", "avg_ms", "alg_bytes" (mean per launch, None where no model is stated), "GB/s"}.  alg_bytes and GB/s are
+        taken over the launches that state a model: a key may mix them with launches that state none (the kept last-layer forward
+        shares the key of the layer below it)."""
         torch.cuda.synchronize()
         out = {}
         for k, v in self.records.items():
-            ms = sum(a.elapsed_time(b) for a, b, _ in v) / max(len(v), 1)
+            t = [a.elapsed_time(b) for a, b, _ in v]
+            ms = sum(t) / max(len(v), 1)
             nb = [n for _, _, n in v if n is not None]
             alg = sum(nb) / len(nb) if nb else None
+            ms_nb = sum(x for x, (_, _, n) in zip(t, v) if n is not None) / max(len(nb), 1)
             out[k] = {"launches": len(v), "avg_ms": ms, "alg_bytes": alg,
-                      "GB/s": (alg / (ms * 1e-3) / 1e9) if (alg and ms > 0) else None}
+                      "GB/s": (alg / (ms_nb * 1e-3) / 1e9) if (alg and ms_nb > 0) else None}
         return out
 
 
@@ -84,8 +88,10 @@ FUSE_FIRST = True      # False: separate scn_conv_backward + scn_conv_dw_first i
 RECOMPUTE_FIRST = True
 # Nothing reads the last layer's output H_L except the readout, and that only on the edges around each trajectory's last node (about
 # 0.1 % of the rows at |E| = 1M): the last layer's forward stores only the (plan block, slab) items holding such a row, by a bit mask
-# built on the device from the last nodes (SconePlan.conv_stack, scn_keep_mask, scn_conv_forward_keep).  Every tile is still staged,
-# gathered and contracted: this is not the zero-skipping mode.  False: the whole tensor is stored.
+# built on the device from the last nodes (SconePlan.conv_stack, scn_keep_mask, scn_conv_forward_keep).  At hidden 32 the forward
+# visits only those items -- the others are not staged, gathered or contracted; at hidden 16 (slab pairs) every tile is still computed
+# and the others dropped.  Which items run depends on the last nodes, never on a value: this is not the zero-skipping mode.  False: the
+# whole tensor is stored.
 KEEP_LAST = True
 # The mirror on the backward side: the readout's gradient dZ_L is non-zero only on those same rows, yet the top layer's backward staged
 # and gathered all of it -- zeros -- to find its zero-tile early-out.  With the keep mask hopped once over the block adjacency
@@ -388,9 +394,10 @@ class ConvOp:
                                                       _dev(partial), _dev(out), _stream()), "scn_conv_forward_accumulate")
             return out
         if keep is not None:
-            # (the key of the plain forward; the kept stores are left out of the byte model: under 0.2 % of a tensor on the benchmark's
-            # batches, and their count is on the device)
-            with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), _nbytes(*srcs) + self.csr_bytes):
+            # (the key of the plain forward.  32 channels: no byte model -- the launch moves the staged rows and the stored rows of the
+            # KEPT items only, and their count is on the device; pricing it at the input tensor would print a rate above the HBM
+            # peak.  16 channels: every tile is still staged, the input tensor is the model)
+            with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if c_in[0] == 32 else _nbytes(*srcs) + self.csr_bytes):
                 st = lib.scn_conv_forward_keep(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
                                                _dev(keep, torch.int32), _stream())
             return out if _served(st, "scn_conv_forward_keep") else None
@@ -490,8 +497,8 @@ class ConvOp:
             out = torch.empty((S, self.n_rows, ns, c), device=y.device, dtype=torch.float32)
         # (the key of the plain C -> C forward: the same kernel family, and what callers that look for the fused layer kernels expect;
         # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
-        if keep is not None:                          # (the kept stores are left out of the byte model, see forward)
-            with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y) + self.csr_bytes):
+        if keep is not None:                          # (no byte model, see forward)
+            with _timed("conv_fwd c%d->%d" % (c, c), None):
                 st = lib.scn_conv_forward_from_y_keep(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out),
                                                       _dev(keep, torch.int32), _stream())
             return out if _served(st, "scn_conv_forward_from_y_keep") else None

@@ -10,9 +10,11 @@ git -C "$ROOT" archive "$REV" scone_gcn_amd/csrc include | tar -x -C "$TMP"
 C="$TMP/scone_gcn_amd/csrc"
 mkdir -p "$ROOT/tools/ab" "$TMP/obj"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -I$TMP/include -I$C -Wall -Wno-unused-result $EXTRA"
-for f in scn_conv scn_blocked scn_readout scn_dense scn_small; do
-  /opt/rocm/bin/hipcc $FLAGS -c "$C/$f.hip" -o "$TMP/obj/$f.o" &
+pids=()
+for src in "$C"/*.hip; do                       # every translation unit the revision had: the library exports all of its entry points
+  /opt/rocm/bin/hipcc $FLAGS -c "$src" -o "$TMP/obj/$(basename "$src" .hip).o" &
+  pids+=($!)
 done
-wait
+for p in "${pids[@]}"; do wait "$p"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/ab/lib_$NAME.so" "$TMP"/obj/*.o
 echo "built tools/ab/lib_$NAME.so from $REV"
