@@ -754,6 +754,45 @@ int scn_project_predict(int32_t n, int32_t k, int32_t n_edges, const double* v, 
 int scn_project_two_target(int32_t n, int32_t d, uint64_t seed, const double* probs, const int32_t* target, const int32_t* n_nbrs,
                            float* score, int32_t* other, int32_t* err, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Synthetic trajectories (synthetic_data_gen.generate_random_walks, SDG:178-243): batched single-source shortest paths on one sparse
+ * graph, and the assembly of a walk from three of them.  Every array is device memory.  The graph is the undirected adjacency as CSR,
+ * adj_ptr[n_nodes + 1] / adj with the columns of a row ascending and every edge present in both rows; adj_w (fp64, one weight per
+ * entry, the same in both rows, >= 0) or NULL for unit weights (the reference's hop metric).  The library cannot look into device
+ * arrays: the caller owns these properties (scone_gcn_amd/synthetic_data_gen.py checks them on the host before the upload); a column
+ * outside [0, n_nodes) is skipped, never followed.
+ *
+ * scn_sssp_paths: job j has source[j] and n_targets (1 .. SCN_SSSP_MAX_TARGETS) targets target[j][t], -1 = no target (an id outside
+ *   [0, n_nodes) counts as none; a source outside reaches nothing).  A tentative distance is the bit pattern of an fp64, ordered as an
+ *   unsigned 64-bit integer and lowered by a 64-bit atomic minimum; the frontier is relaxed generation by generation (unit weights:
+ *   level-synchronous breadth-first search; weights: label-correcting) to THE fixed point dist[v] = min_u fl(dist[u] + w(u, v)).
+ *   pred[v] = the smallest-index neighbour u with fl(dist[u] + w(u, v)) == dist[v] exactly, so trees and paths do not depend on the
+ *   order of execution.
+ *     path [n_jobs][n_targets][path_cap]: the nodes from the source to the target, both included; entries past the length are not written.
+ *     path_len [n_jobs][n_targets]: > 0 the length; 0 no target; -1 unreachable; -2 longer than path_cap (nothing is written);
+ *       -3 on every target of a job whose frontier was not empty after n_nodes generations (not reachable with weights >= 0).
+ *     dist_out [n_jobs][n_targets], optional: the distance of a reached target (path_len > 0 or -2), +inf otherwise.
+ *     dist_all, pred_all [n_jobs][n_nodes], optional (64-bit indexing): the whole tree; +inf / -1 where unreachable, pred[source] = -1.
+ *       Without them a job ends as soon as its targets are final.
+ *     n_gen [n_jobs], optional: generations the job ran.
+ *   One 256-thread workgroup owns one job at a time in one of the n_slots slots of the workspace (scn_sssp_slot_bytes(n_nodes) bytes
+ *   each, 8-byte aligned); min(n_jobs, n_slots) workgroups run, workgroup g takes the jobs g, g + grid, ...; none waits on another.
+ *   SCN_ERR_BAD_ARG for a null array, n_targets or path_cap or n_slots out of range, SCN_ERR_WORKSPACE for fewer than n_slots slots.
+ * scn_walk_assemble: attempt a takes job 2 a = (v_1 -> v_begin, v_1 -> v_2) and job 2 a + 1 = (v_2 -> v_end, none) of a
+ *   scn_sssp_paths call with n_targets = 2: walk[a] = reverse(path(v_1 -> v_begin))[:-1] + path(v_1 -> v_2)[:-1] + path(v_2 -> v_end)
+ *   (SDG:236-238), walk [n][walk_cap], walk_len[a] = its length, or 0 where a segment's path_len is not positive, where the walk is
+ *   longer than walk_cap (nothing is written) or where it visits a node twice (SDG:239; an LDS hash set of the walk's ids).
+ *   walk_cap <= SCN_WALK_MAX, SCN_ERR_UNSUPPORTED beyond. */
+#define SCN_SSSP_MAX_TARGETS 2
+#define SCN_WALK_MAX 16384
+size_t scn_sssp_slot_bytes(int32_t n_nodes);
+int scn_sssp_paths(int32_t n_nodes, const int32_t* adj_ptr, const int32_t* adj, const double* adj_w, int32_t n_jobs, const int32_t* source,
+                   const int32_t* target, int32_t n_targets, int32_t path_cap, int32_t* path, int32_t* path_len, double* dist_out,
+                   double* dist_all, int32_t* pred_all, int32_t* n_gen, void* workspace, size_t workspace_bytes, int32_t n_slots,
+                   void* stream);
+int scn_walk_assemble(int32_t n, const int32_t* path, const int32_t* path_len, int32_t path_cap, int32_t* walk, int32_t* walk_len,
+                      int32_t walk_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

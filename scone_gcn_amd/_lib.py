@@ -24,6 +24,8 @@ SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sa
 SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
 SCN_MARKOV_MAX_ORDER = 4          # highest order of the scn_markov_* count tables
 SCN_PROJECT_MAX_K = 32            # widest [n, k] array of the fp64 projection kernels (scn_csr_apply_f64, scn_cg_*, scn_gram_f64)
+SCN_SSSP_MAX_TARGETS = 2          # targets per job of scn_sssp_paths
+SCN_WALK_MAX = 16384              # longest walk scn_walk_assemble tests for repeats (its LDS hash set)
 SCN_CG_STATE_DOUBLES = 3 * SCN_PROJECT_MAX_K
 SCN_CG_FLAG_WORDS = 2 * SCN_PROJECT_MAX_K + 2
 SCN_CG_FLAG_ALL_FROZEN, SCN_CG_FLAG_ITERATIONS = 2 * SCN_PROJECT_MAX_K, 2 * SCN_PROJECT_MAX_K + 1   # positions in the flags array
@@ -194,6 +196,10 @@ SIGNATURES = {
                                            c_void_p]),
     "scn_project_two_target": (ctypes.c_int, [c_i32, c_i32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),
+    "scn_sssp_slot_bytes": (c_size_t, [c_i32]),
+    "scn_sssp_paths": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_i32, c_void_p]),
+    "scn_walk_assemble": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

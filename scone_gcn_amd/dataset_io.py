@@ -55,12 +55,18 @@ def _onehot(choice, D):
     return y
 
 
-def generate_dataset(n, m, folder, holes=True, seed=1030):
-    """SDG:375-428 with the sparse generator: writes the 1-hop and 2-hop folders."""
+def generate_dataset(n, m, folder, holes=True, seed=1030, walks="host", metric="hops"):
+    """SDG:375-428 with the sparse generator: writes the 1-hop and 2-hop folders.  walks="device": the walks come from
+    generate_random_walks_batched on the GPU (fresh waypoints per walk at any size) instead of the host loop."""
+    if walks not in ("host", "device"):
+        raise ValueError("walks must be 'host' or 'device', got %r" % (walks,))
     cx = sdg.random_SC_graph(n, holes=holes)
     B1, B2 = sdg.incidence_matrices(cx)
     rs = np.random.RandomState(seed)
-    paths = sdg.generate_random_walks(cx, m=m, seed=int(rs.randint(1 << 30)))
+    if walks == "device":
+        paths = sdg.generate_random_walks_batched(cx, m=m, seed=int(rs.randint(1 << 30)), metric=metric, backend="device")
+    else:
+        paths = sdg.generate_random_walks(cx, m=m, seed=int(rs.randint(1 << 30)), metric=metric)
     rev_paths = [p[::-1] for p in paths]
     train_mask = np.asarray([1] * int(len(paths) * 0.8) + [0] * int(len(paths) * 0.2))   # SDG:392-394
     rs.shuffle(train_mask)

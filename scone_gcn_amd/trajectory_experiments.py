@@ -36,14 +36,18 @@ def hyperparams(args=None):
           'beam': 0,                     # B > 0 with -multi_hop 1: also the 2-hop top-B accuracies of a beam search of width B
           'multi_hop_samples': 0,        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
           'markov_order': 1,             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
-          'projection': 0}               # 1: the harmonic projection baseline's experiments first (the reference's projection_model.py)
+          'projection': 0,               # 1: the harmonic projection baseline's experiments first (the reference's projection_model.py)
+          'n_points': 400, 'n_walks': 1000,   # not in the reference (hard-coded, TE:224): the size of the -load_data 0 data set
+          'walks': 'host',               # host | device: device = generate_random_walks_batched (fresh waypoints per walk on the GPU)
+          'walk_metric': 'hops'}         # hops | euclid: the shortest-path metric of the generated walks
     for i in range(len(args) - 1):
         if args[i] and args[i][0] == '-':
             name = args[i][1:]
             if name == 'hidden_layers':
                 nums = list(map(int, args[i + 1].split("_")))
                 hp['hidden_layers'] = [(nums[j], nums[j + 1]) for j in range(0, len(nums), 2)]
-            elif name in ['model_name', 'data_folder_suffix', 'multi_graph', 'model', 'skip_mode', 'multi_hop_skip']:
+            elif name in ['model_name', 'data_folder_suffix', 'multi_graph', 'model', 'skip_mode', 'multi_hop_skip', 'walks',
+                          'walk_metric']:
                 hp[name] = str(args[i + 1])
             else:
                 try:
@@ -187,7 +191,8 @@ def data_setup(hops=(1,), load=True, folder_suffix='schaub', hp=None):
         from . import scone_trajectory_model as stm                        # the flips are drawn from it, so the weights drawn
         stm.reseed(1)                                                      # afterwards (STM:237) continue that stream
     if not load:
-        generate_dataset(400, 1000, folder=folder_suffix, holes=bool(hp['holes']))
+        generate_dataset(int(hp.get('n_points', 400)), int(hp.get('n_walks', 1000)), folder=folder_suffix, holes=bool(hp['holes']),
+                         walks=hp.get('walks', 'host'), metric=hp.get('walk_metric', 'hops'))
         raise Exception('Data generation done')                            # TE:225
     inputs_all, y_all, target_nodes_all = [], [], []
     sc = None
