@@ -363,6 +363,40 @@ int scn_conv_backward_dzmask(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, con
                              const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
                              void* workspace, size_t workspace_bytes, const uint32_t* dzmask /* NULL: plain call */, void* stream);
 
+/* The readout's cone.  The argument above does not stop at the top layer: H_l is read by nothing outside M_{L-l} = hop^{L-l}(M0)
+ * (M0 = scn_keep_mask's mask, hop = scn_mask_hop), and dZ_l is zero outside it whatever the data are.  The calls below run a layer
+ * on such a set only; which items run depends on the last nodes, never on a value.  Masks have scn_keep_mask's geometry for the
+ * call's n_slabs; all need the LDS-blocked plan and ns = 4, and (except scn_clear_mask) at most 64 slabs per workgroup of the launch
+ * grid (any n_slabs <= 64): SCN_ERR_UNSUPPORTED otherwise, before any launch.
+ * scn_conv_backward_visit = scn_conv_backward that VISITS only the items of the mask `visit` (V), on scn_conv_backward's launch
+ *   grid and in its slab order.  CONTRACT: every (block, slab) item of dz[0] that some item of V stages (item (b', s) is staged by
+ *   (b, s) with b' in A(b), the `adj` table of scn_field_lists) either was written by the producer of dz or holds only +0, and every
+ *   item outside V stages only +0 -- with dz zero outside a mask M, V = scn_mask_hop(M) is such a set.  Under it and finite weights dW
+ *   and the use of the workspace are bit for bit scn_conv_backward's on the same dz, and so is dx on V; every other row of dx is LEFT
+ *   UNTOUCHED (dx = NULL: none is written).  NOT READ: aux of the items outside V, and dz of the items no item of V stages.
+ *   NON-FINITE WEIGHTS: scn_conv_backward_dzmask widens its mask to all ones under a NaN / Inf weight so that dx matches the plain
+ *   call; this call cannot (it would write rows its caller keeps zero) and visits V regardless.  What holds then: with V non-empty,
+ *   every entry of dW the plain call makes non-finite is non-finite here too (a visited tile contracts zero rows with the Inf).
+ *   One group, c_dz = c_aux = 32, dense launches; SCN_ERR_UNSUPPORTED for every other width, SCN_ERR_BAD_ARG for visit = NULL.
+ * scn_conv_backward_fused_first_from_y_visit = scn_conv_backward_fused_first_from_y likewise (no dx exists): dW and dW_first bit for
+ *   bit under the same contract and finite weights, the same statement under non-finite ones.  NOT READ: y of the items outside V,
+ *   dz of the items no item of V stages.  channels = 32, dense launches.
+ * scn_conv_shifted_input_keep = scn_conv_forward_first with out = NULL on the items of `keep`: the records y of every kept item are
+ *   that call's bits, every other row of y_out is LEFT UNTOUCHED.  x is the input and is read wherever a kept item stages it.
+ * scn_clear_mask: +0 over the rows of every item (b, s) whose bit is set in `mask` of a [n_slabs][n_rows][ns][channels] tensor (16-byte
+ *   aligned), nothing else is written: plain vector stores, no atomics.  The mask-driven twin of scn_clear_list -- it returns a
+ *   pooled all-zero gradient buffer to that state after scn_conv_backward_visit wrote it on `mask`. */
+int scn_conv_backward_visit(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                            const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
+                            void* workspace, size_t workspace_bytes, const uint32_t* visit, void* stream);
+int scn_conv_backward_fused_first_from_y_visit(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
+                                               const float* const* W_first, int32_t channels, int32_t act, const float* y,
+                                               float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
+                                               const uint32_t* visit, void* stream);
+int scn_conv_shifted_input_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
+                                void* stream);
+int scn_clear_mask(scn_conv_t conv, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream);
+
 /* Backward of the layer that FOLLOWS the first one, fused with the first layer's weight gradient (what jax.grad of TE:144-149
  * yields for weights[0:6], STM:307, in one pass):
  *   this layer :  dW[slot] += aux^T G_slot                       (as scn_conv_backward; aux = the first layer's output)

@@ -127,6 +127,15 @@ SIGNATURES = {
     "scn_conv_backward_dzmask": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
                                                 c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t,
                                                 c_void_p, c_void_p]),
+    "scn_conv_backward_visit": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
+                                               c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t,
+                                               c_void_p, c_void_p]),
+    "scn_conv_backward_fused_first_from_y_visit": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
+                                                                  ctypes.POINTER(c_void_p), c_i32, c_i32, c_void_p,
+                                                                  ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_size_t,
+                                                                  c_void_p, c_void_p]),
+    "scn_conv_shifted_input_keep": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_clear_mask": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                         ctypes.POINTER(c_void_p)]),
     "scn_terms_forward": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_i32, c_i32,

@@ -121,7 +121,17 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // come as keep_window's 64-bit window (scn_blk_fwd.inc); with a NaN / Inf weight the plain path has no early-out (0 * Inf), so the
 // window is all ones there and the kernel is the plain one.  A visit with its bit clear reads NEITHER staging buffer: they hold
 // other slabs' data.
-template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false, bool DZMASK = false>
+// VISIT (plain C = 32 and FIRST + FROMY, dense launches): the mirror of fwd_c32_w16_kernel<KEEP> -- only the (block, slab) items of a
+// visit mask V are VISITED.  The block's 64-bit window is fetched first (keep_window, cut to this workgroup's slab range), a block
+// with an empty window is left before its metadata is read, and the slab loop runs over the window's set bits with its cursor in
+// SGPRs (scn_keep_bits.h): no memory operation for the walk inside the slab loop.  A visit that runs is staged, gathered, contracted
+// (or early-outed) and stored exactly as in the plain forms, in ascending slab order on the plain call's grid, so wherever every
+// item outside V would have taken the zero-tile early-out the weight-gradient partials see the same tiles in the same order.  dx
+// (plain form) is written on the visited items only; aux / y outside V and dz of items no visited item stages are not read.  The
+// mask's words ride where the form has a free pointer: DZ0 in the plain form, aux in the FIRST + FROMY form.  A NaN / Inf weight
+// does NOT widen the window (DZMASK does): V is visited regardless, see scn_conv_backward_visit in include/scone_hip.h.
+template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false, bool DZMASK = false,
+          bool VISIT = false>
 __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, const float* __restrict__ DZ,
                                                                      const float* __restrict__ DZ0,
                                                                      const float* __restrict__ W0,
@@ -136,6 +146,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     static_assert(!FROMY || (FIRST && !PAIR), "the aux-free form exists for the fused-first C = 32 kernel");
     static_assert(!DZMASK || (!EXT0 && !PAIR && !FIRST && !ACCUM && !FROMY), "the source mask exists for the plain C = 32 kernel");
     static_assert(!FIRST || !EXT0, "the fused first-layer gradient exists for the plain forms (C = 32, and C = 16 on slab pairs)");
+    static_assert(!VISIT || (!EXT0 && !PAIR && !ACCUM && !DZMASK && FIRST == FROMY), "the visit mask exists for the plain and the fused-first from-y C = 32 kernel");
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / BK_THREADS;
     constexpr int CH = PAIR ? 16 : 32;                       // channels of a stored point
     const SmemC32 sm = carve_c32(smem);
@@ -205,6 +216,13 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     const bool second = PAIR && (((lane >> 2) ^ wave) & 1);       // this lane's LDS-DMA chunks come from slab B (see dma_k)
     if (listed || slab0 < slab1)
     SCN_UNIT_BEGIN()
+        // VISIT: the block's window FIRST, cut to this workgroup's slab range; a block without a visit is left here, before the
+        // barrier and its metadata (the same scalar in all eight waves: they leave together).  (dense launches only: k0 = slab0)
+        uint64_t vw = 0;                                          // the cursor: its lowest set bit is the visit handled next
+        if (VISIT) {
+            vw = keep_cut(keep_window(KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}, b, k0), n_it);
+            if (vw == 0) continue;
+        }
         wait_all_and_barrier();
         const BlockMeta m = load_block_c32<BK_THREADS>(P, b, sm);
         // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
@@ -230,7 +248,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 else lds_dma16(Xs, off, dst);
             }
         };
-        const int n_vis = PAIR ? (n_it + 1) >> 1 : n_it;          // visits: slabs, or slab pairs
+        const int n_vis = VISIT ? keep_count(vw) : (PAIR ? (n_it + 1) >> 1 : n_it);   // visits: slabs, slab pairs, or the window's set bits
         auto slab_of = [&](int vis, int q) {                     // q-th slab of a visit (the lone last slab stands in for its pair)
             // plain form: wave-uniform -- saying so BEFORE the address arithmetic keeps the 64-bit multiplies on the scalar unit and the
             // LDS-DMA takes (SGPR base + 32-bit lane offset) instead of a 64-bit VGPR address
@@ -242,8 +260,9 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         auto src_base = [&](int vis) {
             return (const char*)DZ + (size_t)slab_of(vis, second ? 1 : 0) * slab_bytes;
         };
+        auto src_of = [&](int slab) { return (const char*)DZ + (size_t)slab * slab_bytes; };   // VISIT: by slab, not by visit index
         if (!DZMASK || (dzm & 1)) {
-            const char* Xs = src_base(0);
+            const char* Xs = VISIT ? src_of(k0 + keep_first(vw)) : src_base(0);
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) dma_k(i, Xs, 0);
         }
@@ -289,7 +308,15 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 }
                 if (it == n_vis) break;
             }
-            const int slab = slab_of(it, PAIR ? p >> 4 : 0);          // PAIR: lanes p >= 16 hold slab B's channels
+            // VISIT: this visit's slab and the next one's (its own where it is the last) off the cursor; the visit INDEX still counts
+            // 0, 1, 2, ...: buffer parity and the staging guards run on it as in the other forms
+            int v_slab = 0, v_next = 0;
+            if (VISIT) {
+                v_slab = k0 + keep_first(vw);
+                vw = keep_next(vw);
+                v_next = vw ? k0 + keep_first(vw) : v_slab;
+            }
+            const int slab = VISIT ? v_slab : slab_of(it, PAIR ? p >> 4 : 0);   // PAIR: lanes p >= 16 hold slab B's channels
             const bool lane_live = !PAIR || p < 16 || 2 * it + 1 < n_it;
             const uint32_t bufbit = (uint32_t)((it & 1) << 16);
             const uint32_t cbs[4] = {cqs[0] | bufbit, cqs[1] | bufbit, cqs[2] | bufbit, cqs[3] | bufbit};
@@ -384,7 +411,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 if (!w_bad && mgb == 0) {
                     const int vdma0 = it + 1;
                     if (vdma0 < n_vis && dz_next) {
-                        const char* Xn0 = src_base(vdma0);
+                        const char* Xn0 = VISIT ? src_of(v_next) : src_base(vdma0);
 #pragma unroll
                         for (int i = 0; i < NDMA; ++i) dma_k(i, Xn0, vdma0 & 1);
                     }
@@ -459,7 +486,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             // ---------------- CONTRACT
             const int vdma = it + 1;                                     // the visit whose slab this contraction stages
             const bool more = vdma < n_vis && dz_next;                  // (DZMASK: a slab without a source in the mask is not staged)
-            const char* Xn = src_base(more ? vdma : it);
+            const char* Xn = VISIT ? src_of(v_next) : src_base(more ? vdma : it);
             const int nbuf = vdma & 1;
             auto side = [&](int k) {                                     // (all eight right after the barrier instead: +2 %)
                 if (k < NDMA && more) dma_k(k, Xn, nbuf);
@@ -609,3 +636,5 @@ template <int ACT> constexpr auto bwd_c32_accum = bwd_c32_bf16_kernel<ACT, false
 template <int ACT> constexpr auto bwd_c32_first = bwd_c32_bf16_kernel<ACT, false, false, true>;              // DZ0 = y, dx null: -> partial_first
 template <int ACT> constexpr auto bwd_c32_first_pair = bwd_c32_bf16_kernel<ACT, false, true, true>;          // the same at C = 16
 template <int ACT> constexpr auto bwd_c32_first_from_y = bwd_c32_bf16_kernel<ACT, false, false, true, false, true>;   // and aux null: rebuilt from y and fw
+template <int ACT> constexpr auto bwd_c32_plain_visit = bwd_c32_bf16_kernel<ACT, false, false, false, false, false, false, true>;   // DZ = dz, DZ0 = visit mask words
+template <int ACT> constexpr auto bwd_c32_first_from_y_visit = bwd_c32_bf16_kernel<ACT, false, false, true, false, true, false, true>;   // DZ0 = y, aux = visit mask words

@@ -162,6 +162,16 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
                           W[2], out, y_out, L.nr, L.nc, n_slabs, act, wl);
 }
 
+// The y-only launch of the first layer (blocked_forward with out = nullptr) on the items of a keep mask: gather3_c1_keep_kernel on
+// the plain launch's grid.
+int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st) {
+    const size_t lds = smem_bytes(16);
+    const dim3 grid = launch_grid(c, n_slabs, lds);
+    if (!keep_fits(grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
+    return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds, st, c->plan.dev, x, y_out, c->n_rows, c->g[0].n_cols,
+                          n_slabs, keep_mask_of(keep, n_slabs));
+}
+
 // Layer 2 of a stack whose first layer has one input channel, straight from the first layer's shifted-input records
 // (fwd_c32_from_y): H1 is rebuilt in LDS, never stored.  Dense launches, 32 channels.
 bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
@@ -211,19 +221,21 @@ int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
                      float* const* dW, void* ws, size_t ws_bytes, const WorkList* wlp, hipStream_t st,
                      const float* dx_partial,             // dx_partial (32 -> 32 only): dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
-                     const uint32_t* dzmask) {            // dzmask (32 -> 32, dense, no partial): dz is staged by the mask, see there
+                     const uint32_t* dzmask,              // dzmask (32 -> 32, dense, no partial): dz is staged by the mask, see there
+                     const uint32_t* visit) {             // visit (the same shapes, no dzmask): only the mask's items are visited, see there
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const int cd = c_dz[0];
     float* partial = (float*)ws;
     const size_t lds = bwd_lds();
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
     if (dx_partial && (c_aux != 32 || !dx)) return SCN_ERR_UNSUPPORTED;
-    if (dzmask && (dx_partial || wl.block || c_aux != 32 || cd != 32 || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
+    const uint32_t* mask = dzmask ? dzmask : visit;
+    if (mask && ((dzmask && visit) || dx_partial || wl.block || c_aux != 32 || cd != 32 || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
     const int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
-        if (dzmask)                                              // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
-            return launch_checked(bwd_c32_plain_dzmask<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], (const float*)dzmask, W[0], W[1],
-                                  W[2], aux, dx, partial, L.nr, L.nc, n_slabs, wl, nullptr, NO_FIRSTW);
+        if (mask)                                                // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
+            return launch_checked(dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0],
+                                  (const float*)mask, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, wl, nullptr, NO_FIRSTW);
         const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
                               n_slabs, wl, nullptr, NO_FIRSTW);
@@ -260,7 +272,8 @@ __global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* _
 
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st, const float* const* W_first) {   // W_first (32 channels): aux is rebuilt from y, not read
+                           hipStream_t st, const float* const* W_first,   // W_first (32 channels): aux is rebuilt from y, not read
+                           const uint32_t* visit) {                       // visit (with W_first, dense): only the mask's items are visited
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const size_t lds = bwd_lds();
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
@@ -268,9 +281,13 @@ int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const fl
     float* partial = (float*)ws;
     float* partial_first = partial + (size_t)n_wg * 3 * ch * ch;
     if (W_first && ch != 32) return SCN_ERR_UNSUPPORTED;
+    if (visit && (!W_first || wl.block || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
     const FirstW fw = W_first ? FirstW{{W_first[0], W_first[1], W_first[2]}} : NO_FIRSTW;
     int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
+        if (visit)                                               // (the mask's words ride in aux, which this form does not read)
+            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2],
+                                  (const float*)visit, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw);
         const auto k = W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2], W_first ? nullptr : aux, nullptr, partial,
                               L.nr, L.nc, n_slabs, wl, partial_first, fw);
@@ -345,6 +362,12 @@ int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* 
                        ns * ch);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
+}
+
+int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st) {
+    if (!c->plan.built || ns != BK_NS || (ns * ch) % 4 || (reinterpret_cast<uintptr_t>(t) & 15)) return SCN_ERR_UNSUPPORTED;
+    return launch_checked(clear_mask_kernel, dim3(std::min(c->plan.dev.n_blocks, 2048)), dim3(256), 0, st, c->plan.dev,
+                          keep_mask_of(mask, n_slabs), t, c->n_rows, n_slabs, ns * ch);
 }
 
 // ---- "power" layers: one operator S (identity + one value array), three terms  X0, S-input's own row, S * input ----

@@ -5,9 +5,12 @@
 // gather3_c1_kernel computes Y[p] = (x, S_lo x, S_up x)[p] from the 16-byte input pieces (the gather of fwd_c1, 12 bytes per
 // point out); dw_first_stream_kernel then reads dz exactly once, coalesced, with no LDS gather at all -- an HBM stream.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, const float* __restrict__ X,
-                                                                   float* __restrict__ Y, int n_rows, int n_cols,
-                                                                   int n_slabs) {
+// KEEP (gather3_c1_keep_kernel): only the (block, slab) items of a keep mask are visited, as in fwd_c32_w16_kernel<KEEP> -- the block's
+// window first, a block with an empty window skipped before load_block, the slab loop over the window's set bits (scn_keep_bits.h).
+// The records of a kept item are the plain kernel's bits, every other row of Y is left untouched; X is read in full (it is the input).
+template <bool KEEP>
+__device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* __restrict__ X, float* __restrict__ Y, int n_rows,
+                                                int n_cols, int n_slabs, const KeepMask km) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 16;
     const Smem sm = carve(smem, PIECE);
@@ -17,17 +20,20 @@ __global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, co
     SCN_SLAB_RANGE();
     if (slab0 >= slab1) return;
     for (; b < b_end; b += b_stride) {
+        uint64_t keep = ~0ull;                                    // KEEP: the cursor, its lowest set bit is the next visit's slab
+        if (KEEP) {
+            keep = keep_cut(keep_window(km, b, slab0), slab1 - slab0);
+            if (keep == 0) continue;
+        }
         wait_all_and_barrier();
         const BlockMeta m = load_block(P, b, sm);
         __syncthreads();
         const int tw = tid < m.rows * BK_NS ? P.tile_w[b * BK_WAVES + (tid >> 5)] : 0;   // (not in the slab loop: see fwd_c1_kernel)
-        dma_stage<PIECE, 0>((const char*)X + (size_t)slab0 * n_cols * PIECE, sm.buf(0), sm, m.nsrc);
-        for (int slab = slab0; slab < slab1; ++slab) {
-            const float* st = (const float*)sm.buf((slab - slab0) & 1);
+        auto visit = [&](int slab, int it, int next) {            // slab `slab` staged in buffer it & 1; next: the slab to stage meanwhile, or -1
+            const float* st = (const float*)sm.buf(it & 1);
             wait_vm_and_barrier();
-            if (slab + 1 < slab1)
-                dma_stage<PIECE, 0>((const char*)X + (size_t)(slab + 1) * n_cols * PIECE, sm.buf((slab + 1 - slab0) & 1), sm,
-                                    m.nsrc);
+            if (next >= 0)
+                dma_stage<PIECE, 0>((const char*)X + (size_t)next * n_cols * PIECE, sm.buf((it + 1) & 1), sm, m.nsrc);
             if (tid < m.rows * BK_NS) {
                 const int rt = tid >> 2, n = tid & 3;
                 float zs = st[sm.self[rt] * 4 + n], zl = 0.f, zu = 0.f;
@@ -42,8 +48,29 @@ __global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, co
                 }
                 *(f32x4*)(Y + (((size_t)slab * n_rows + m.row0) * BK_NS + tid) * Y_STRIDE) = f32x4{zs, zl, zu, 0.f};
             }
+        };
+        if (KEEP) {
+            dma_stage<PIECE, 0>((const char*)X + (size_t)(slab0 + keep_first(keep)) * n_cols * PIECE, sm.buf(0), sm, m.nsrc);
+            for (int it = 0; keep; ++it) {
+                const int slab = slab0 + keep_first(keep);
+                keep = keep_next(keep);
+                visit(slab, it, keep ? slab0 + keep_first(keep) : -1);
+            }
+        } else {
+            dma_stage<PIECE, 0>((const char*)X + (size_t)slab0 * n_cols * PIECE, sm.buf(0), sm, m.nsrc);
+            for (int slab = slab0; slab < slab1; ++slab) visit(slab, slab - slab0, slab + 1 < slab1 ? slab + 1 : -1);
         }
     }
+}
+__global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, const float* __restrict__ X,
+                                                                   float* __restrict__ Y, int n_rows, int n_cols,
+                                                                   int n_slabs) {
+    gather3_c1_body<false>(P, X, Y, n_rows, n_cols, n_slabs, KeepMask{nullptr, 0});
+}
+__global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_keep_kernel(PlanDev P, const float* __restrict__ X,
+                                                                        float* __restrict__ Y, int n_rows, int n_cols,
+                                                                        int n_slabs, KeepMask km) {
+    gather3_c1_body<true>(P, X, Y, n_rows, n_cols, n_slabs, km);
 }
 
 constexpr int DWS_THREADS = 256, DWS_BLOCKS = 1024;
@@ -142,6 +169,24 @@ __global__ __launch_bounds__(256) void clear_list_kernel(PlanDev P, WorkList wl,
         for (int k = wl.ptr[u]; k < wl.ptr[u + 1]; ++k) {
             f32x4* t = (f32x4*)(T + ((size_t)wl.slab[k] * n_rows + row0) * row_floats);
             for (int i = threadIdx.x; i < count; i += 256) t[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+// The mask-driven twin: +0 over the block's rows of slab s for every set bit (b, s) of a mask of scn_keep_mask's geometry (a bit at or
+// past n_slabs names no slab).  Plain 16-byte vector stores, no atomics; a workgroup walks its blocks' words with scalar loads.
+__global__ __launch_bounds__(256) void clear_mask_kernel(PlanDev P, KeepMask km, float* __restrict__ T, int n_rows, int n_slabs,
+                                                         int row_floats) {
+    for (int b = blockIdx.x; b < P.n_blocks; b += gridDim.x) {
+        const uint32_t* mw = km.bits + (size_t)b * km.words;
+        const int row0 = P.blk_row0[b], count = P.blk_rows[b] * row_floats / 4;
+        for (int w = 0; w < km.words; ++w) {
+            for (uint32_t bits = mw[w]; bits; bits &= bits - 1) {
+                const int s = 32 * w + __builtin_ctz(bits);
+                if (s >= n_slabs) break;
+                f32x4* t = (f32x4*)(T + ((size_t)s * n_rows + row0) * row_floats);
+                for (int i = threadIdx.x; i < count; i += 256) t[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
         }
     }
 }

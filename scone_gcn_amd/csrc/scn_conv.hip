@@ -26,7 +26,7 @@ size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, cons
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
                      const float* const* W, const float* aux, int c_aux, int act, float* dx,
                      float* const* dW, void* ws, size_t ws_bytes, const WorkList* wl, hipStream_t st,
-                     const float* dx_partial = nullptr, const uint32_t* dzmask = nullptr);
+                     const float* dx_partial = nullptr, const uint32_t* dzmask = nullptr, const uint32_t* visit = nullptr);
 bool blocked_spmm_supported(const scn_conv_s* c, int k);
 bool blocked_power_supported(const scn_conv_s* c, int ns, int ch);
 size_t blocked_power_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
@@ -38,7 +38,8 @@ bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch);
 size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st, const float* const* W_first = nullptr);
+                           hipStream_t st, const float* const* W_first = nullptr, const uint32_t* visit = nullptr);
+int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st);
 bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
                            float* out, hipStream_t st, const uint32_t* keep = nullptr);
@@ -54,6 +55,7 @@ size_t blocked_dw_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int 
 int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y, const float* dz, int cd,
                      float* const* dW, void* ws, const WorkList* wl, hipStream_t st);
 int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* wl, hipStream_t st);
+int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st);
 int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
@@ -659,6 +661,50 @@ int scn_clear_list(scn_conv_t c, int32_t ns, int32_t channels, float* tensor, co
     if (!c || !tensor || !wl || !valid_list(wl) || channels <= 0) return SCN_ERR_BAD_ARG;
     WorkList wlist = to_list(wl);
     return blocked_clear_list(c, ns, channels, tensor, &wlist, (hipStream_t)stream);
+}
+
+int scn_clear_mask(scn_conv_t c, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream) {
+    if (!c || !tensor || !mask) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || channels <= 0) return SCN_ERR_BAD_SHAPE;
+    return blocked_clear_mask(c, n_slabs, ns, channels, tensor, mask, (hipStream_t)stream);
+}
+
+int scn_conv_shifted_input_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
+                                void* stream) {
+    if (!c || !x || !y_out || !keep) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0) return SCN_ERR_BAD_SHAPE;
+    const int32_t c_in = 1;
+    if (n_slabs > 65535 || c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, 32)) return SCN_ERR_UNSUPPORTED;
+    return blocked_shifted_input_keep(c, n_slabs, x, y_out, keep, (hipStream_t)stream);
+}
+
+int scn_conv_backward_visit(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                            const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
+                            void* workspace, size_t workspace_bytes, const uint32_t* visit, void* stream) {
+    if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace || !visit) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
+    for (int s = 0; s < c->n_slots; ++s)
+        if (!W[s] || !dW[s]) return SCN_ERR_BAD_ARG;
+    if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
+    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
+    return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
+                            (hipStream_t)stream, nullptr, nullptr, visit);
+}
+
+int scn_conv_backward_fused_first_from_y_visit(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
+                                               const float* const* W_first, int32_t channels, int32_t act, const float* y,
+                                               float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
+                                               const uint32_t* visit, void* stream) {
+    if (!c || !dz || !W || !W[0] || !W[1] || !W[2] || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !y || !dW ||
+        !dW[0] || !dW[1] || !dW[2] || !dW_first || !dW_first[0] || !dW_first[1] || !dW_first[2] || !workspace || !visit)
+        return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > 65535 || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (workspace_bytes < blocked_backward_first_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
+    return blocked_backward_first(c, n_slabs, dz, W, nullptr, channels, act, y, dW, dW_first, workspace, nullptr, (hipStream_t)stream,
+                                  W_first, visit);
 }
 
 int scn_conv_forward_power(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x0, const float* x,

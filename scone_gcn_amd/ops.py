@@ -99,6 +99,14 @@ KEEP_LAST = True
 # zero tile without staging, gathering or reading aux (SconePlan._top_dz_mask, scn_conv_backward_dzmask).  Every (block, slab) item is
 # still visited and dX is written in full: this is not the zero-skipping mode.  False: the plain backward.
 TOP_DZ_MASK = True
+# Neither argument stops at the top layer.  The readout reads H_L on the items M0 (the keep mask); the kept layer-L forward stages H_{L-1}
+# only from M1 = hop(M0); the layer-L backward reads H_{L-1} only there and its dX_L is zero outside M1 whatever the data are -- by
+# induction nothing reads H_l outside M_{L-l} = hop^{L-l}(M0), dZ_l is zero outside it, and y is read only on M_{L-1}.  With the switch
+# on, and where KEEP_LAST and TOP_DZ_MASK are both served on a stack of three or more 32-channel layers (SconePlan._readout_cone),
+# every layer's forward runs kept on its set, every backward VISITS the set one hop out (scn_conv_backward_visit and kin), and the
+# gradients between layers live in pooled all-zero buffers that a masked clear wipes where their producer wrote (scn_clear_mask).
+# Which items run depends on the last nodes, never on a value.  False: every layer below the top runs in full.
+READOUT_CONE = True
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
 # step, one launch against the layer-by-layer kernels, ms (tools/small_step.py, profiles/r04_small_step_ab.txt):
@@ -367,6 +375,12 @@ class ConvOp:
                                            _dev(mask, torch.int32), _dev(out, torch.int32), _stream()), "scn_mask_hop")
         return out
 
+    def clear_mask(self, t, mask):
+        """+0 over the (block, slab) items of a [S, rows, ns, C] tensor whose bit is set in `mask` (scn_clear_mask)."""
+        with _timed("clear_mask", None):
+            check(_lib.load().scn_clear_mask(self.handle, t.shape[0], t.shape[2], t.shape[3], _dev(t), _dev(mask, torch.int32), _stream()),
+                  "scn_clear_mask")
+
     def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None):
         """wl: WorkList (zero-skipping): only the listed items of `out` are written; `out` must be given, all-zero.
         partial: tensor of the output's shape added to the pre-activation (scn_conv_forward_accumulate; out defaults to it, in place).
@@ -406,16 +420,20 @@ class ConvOp:
                                             wl.ref() if wl is not None else None, _stream()), "scn_conv_forward")
         return out
 
-    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None):
+    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None, visit=None):
         """dWs: list of tensors ACCUMULATED into.  Returns dx or None.  wl: WorkList (zero-skipping): only the listed
         items of `dx` are written (it must be given, all-zero) and only they contribute to dWs.
         dx_partial: tensor of dx's shape ADDED to the input gradient (scn_conv_backward_accumulate; dx defaults to it, in place).
         dz_mask: mask_hop() of the keep mask outside whose items dzs[0] is all-zero (top layer, dense): dz is staged only where the
         mask is set, with the plain call's results; returns False (nothing launched, dWs untouched) when the shape is not served
-        (scn_conv_backward_dzmask)."""
+        (scn_conv_backward_dzmask).
+        visit: a mask V one hop out from a mask outside whose items dzs[0] is all-zero: only V's items are visited, with the plain
+        call's dWs and its dx on V; `dx` must be given and every other row of it is left as it is; False when not served
+        (scn_conv_backward_visit)."""
         lib = _lib.load()
         assert wl is None or (dx is not None or not need_dx)
         assert dz_mask is None or (wl is None and dx_partial is None)
+        assert visit is None or (wl is None and dx_partial is None and dz_mask is None and (dx is not None or not need_dx))
         if dx_partial is not None:
             assert wl is None and need_dx and tuple(dx_partial.shape) == tuple(aux.shape)
             dx = dx_partial if dx is None else dx
@@ -446,6 +464,13 @@ class ConvOp:
             if not _served(st, "scn_conv_backward_dzmask"):
                 return False
             return dx if need_dx else None
+        if visit is not None:                         # (the key of the plain backward; no byte model: the visited items' count is on the device)
+            with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"), None):
+                st = lib.scn_conv_backward_visit(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
+                                                 _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _dev(visit, torch.int32), _stream())
+            if not _served(st, "scn_conv_backward_visit"):
+                return False
+            return dx if need_dx else None
         with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
                     None if wl is not None else _nbytes(aux, dx if need_dx else None, *dzs) + self.csr_bytes):
             check(lib.scn_conv_backward_list(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
@@ -470,14 +495,19 @@ class ConvOp:
                                             wl.ref() if wl is not None else None, _stream())
         return (out, y) if _served(st, "scn_conv_forward_first") else None
 
-    def shifted_input(self, x):
+    def shifted_input(self, x, keep=None):
         """y = (x, S_lo x, S_up x, 0) per point of a 1-channel input WITHOUT the first layer's output (scn_conv_forward_first with
-        out = NULL); None when the shape is not served."""
+        out = NULL); None when the shape is not served.  keep: only the kept (block, slab) items of y are written, the rest of it is
+        uninitialised memory (scn_conv_shifted_input_keep)."""
         lib = _lib.load()
         S, rows, ns, c_in = x.shape
         if c_in != 1 or self.n_groups != 1 or self.n_slots != 3:
             return None
         y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
+        if keep is not None:                          # (no byte model, see forward)
+            with _timed("conv_fwd c1->y", None):
+                st = lib.scn_conv_shifted_input_keep(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32), _stream())
+            return y if _served(st, "scn_conv_shifted_input_keep") else None
         dummy = _ptrs([x] * 3)                        # (the weights are not read without an output; the call checks them for NULL)
         with _timed("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes):
             st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
@@ -530,11 +560,12 @@ class ConvOp:
                                               _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _stream()), "scn_conv_backward_power")
         return True, dx
 
-    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None):
+    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None, visit=None):
         """Backward of the layer after the first one, fused with the first layer's weight gradient: dWs (this layer) and
         dWs_first are accumulated, the input gradient is never written (scn_conv_backward_fused_first).  False when the shape
         is not served.  aux = None with Ws_first (the first layer's weights): the first layer's output is rebuilt from y
-        inside the kernel instead of being read (scn_conv_backward_fused_first_from_y, 32 channels)."""
+        inside the kernel instead of being read (scn_conv_backward_fused_first_from_y, 32 channels).  visit (with Ws_first, dense): as
+        in backward (scn_conv_backward_fused_first_from_y_visit)."""
         lib = _lib.load()
         S, rows, ns, c = dz.shape
         if (aux is not None and tuple(aux.shape) != (S, rows, ns, c)) or tuple(y.shape) != (S, rows, ns, Y_STRIDE) or self.n_groups != 1:
@@ -545,6 +576,14 @@ class ConvOp:
         if nbytes == 0:
             return False
         ws = _workspace(nbytes, dz.device)
+        if visit is not None:
+            if aux is not None or wl is not None:
+                return False
+            with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None):
+                st = lib.scn_conv_backward_fused_first_from_y_visit(self.handle, S, ns, _dev(dz), _ptrs(Ws), _ptrs(Ws_first), c, ACT[act],
+                                                                    _dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws,
+                                                                    _dev(visit, torch.int32), _stream())
+            return _served(st, "scn_conv_backward_fused_first_from_y_visit")
         tail = (_dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws, wl.ref() if wl is not None else None, _stream())
         if aux is None:
             with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, y) + self.csr_bytes):
@@ -966,6 +1005,8 @@ class SconeState(NamedTuple):
     activity: object    # work lists of the zero-skipping mode, or None
     promoted: object    # the zero-padded weights the stack ran on, or None
     wide: bool          # hidden widths above 32 ran in 32-channel blocks (_wide_stack / _wide_backward)
+    cone: object = None  # ops.READOUT_CONE: the masks [M0 .. M_{L-1}] the forward ran on (layer l kept on M_{L-l}, y0 on M_{L-1}: every
+                         # other row of hs[2:] and y0 is uninitialised memory), which the backward visits by; None: the stack ran in full
 
 
 class BunchState(NamedTuple):
@@ -1053,6 +1094,19 @@ class SconePlan(Plan):
         S, E, ns, _ = x.shape
         L = int(n_layers)
         keep = self._keep_last(x, weights, activity, last_dev)
+        cone = self._readout_cone(x, weights, activity, keep)
+        if cone is not None:                            # every layer on the readout's cone (READOUT_CONE); not served: the stack below, in full
+            y0, h = self.conv.shifted_input(x, keep=cone[L - 1]), None
+            if y0 is not None:
+                h = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=cone[L - 2])
+            hs += [None, h]
+            for i in range(2, L):
+                if hs[-1] is not None:
+                    hs.append(self.conv.forward([hs[-1]], weights[3 * i:3 * i + 3], 32, self.act, out=out_last if i == L - 1 else None,
+                                                keep=cone[L - 1 - i]))
+            if hs[-1] is not None:
+                return hs, y0, cone
+            hs, y0 = [x], None
 
         def layer(i, src):                              # layer i >= 1 of a dense stack; the last one by the keep mask where there is one
             w = weights[3 * i:3 * i + 3]
@@ -1073,7 +1127,7 @@ class SconePlan(Plan):
                 hs += [None, h2]
                 for i in range(2, L):
                     hs.append(layer(i, hs[-1]))
-                return hs, y0
+                return hs, y0, None
             y0 = None
         for i in range(int(n_layers)):
             w = weights[3 * i:3 * i + 3]
@@ -1092,7 +1146,7 @@ class SconePlan(Plan):
                 hs.append(layer(i, hs[-1]))
             else:
                 hs.append(self.conv.forward([hs[-1]], w, c_out, self.act, out=out, wl=wl))
-        return hs, y0
+        return hs, y0, None
 
     # up to this size of H_L the last layer stores everything: the two extra launches of the mask cost more than the stores they save
     # on the graph-replayed steps of small complexes (the bound of SMALL_DZ_BYTES; tests set 0 to take the path on small complexes)
@@ -1115,6 +1169,29 @@ class SconePlan(Plan):
             return None
         tabs = self.field_tables_dev()
         return self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs) if tabs is not None else None
+
+    # the bound of KEEP_LAST_MIN_BYTES and SMALL_DZ_BYTES under a name of its own: a test that sets those two to 0 to take their paths on a
+    # small complex stays on those paths; the tests of this one set all three
+    READOUT_CONE_MIN_BYTES = 8 << 20
+
+    def _readout_cone(self, x, weights, activity, keep):
+        """The masks [M0 .. M_{L-1}] of the readout's cone (M0 = keep, M_k = one hop out from M_{k-1}), or None: exactly where _keep_last
+        and _top_dz_mask are both served -- their switches on, `keep` built (plain scone plan on its blocked operator, dense launches,
+        the sizes and the tables of _keep_last), symmetric shifts, the gradient buffers above SMALL_DZ_BYTES -- on a stack of three or
+        more layers that runs without a stored H1 (1-channel input, hidden 32 throughout: _recompute_first), and at most 64 slabs,
+        where every masked launch is served whatever its grid.  READOUT_CONE is the tests' and A/B's switch."""
+        L = (len(weights) - 1) // 3
+        if not READOUT_CONE or not TOP_DZ_MASK or keep is None or L < 3 or self.conv_T is not self.conv:
+            return None
+        S, E, ns, _ = x.shape
+        nbytes = S * E * ns * 32 * 4
+        if S > 64 or nbytes <= self.SMALL_DZ_BYTES or nbytes <= self.READOUT_CONE_MIN_BYTES or not self._recompute_first(x, weights, activity):
+            return None
+        tabs = self.field_tables_dev()
+        cone = [keep]
+        for _ in range(L - 1):
+            cone.append(self.conv.mask_hop(cone[-1], tabs))
+        return cone
 
     def _recompute_first(self, x, weights, activity):
         """Whether this stack runs without a stored H1: plain scone plan, 1-channel input, every hidden width 32 (no promotion), at
@@ -1341,9 +1418,9 @@ class SconePlan(Plan):
             check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), _ptrs(parts),
                                                          _dev(parts[0]), _dev(logp), _stream()), "scn_logits_sum_log_softmax")
             return logp, SconeState(hs, bhs, y0, None, wp, wide=True)
-        hs, y0 = self.conv_stack(x, w, activity, last_dev, out_last)
+        hs, y0, cone = self.conv_stack(x, w, activity, last_dev, out_last)
         logp, bh, _ = self.readout(hs[-1], w[-1], last_dev)
-        return logp, SconeState(hs, bh, y0, activity, wp, wide=False)
+        return logp, SconeState(hs, bh, y0, activity, wp, wide=False, cone=cone)
 
     # -- hidden widths above 32 (TE:103-110 accepts any): every activation is P / 32 separate 32-channel tensors and a layer is
     # its (input block i, output block j) pairs on the fused C = 32 kernels -- act(sum_i sum_s (S_s H_i) W_s[i, j]) (TE:143-149):
@@ -1464,9 +1541,37 @@ class SconePlan(Plan):
             return None
         return self.conv.mask_hop(self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs, key="dz_mask"), tabs)
 
+    def _cone_backward(self, saved, logp, d_logp, last_dev, weights, grads):
+        """The backward of a forward that ran on the readout's cone (saved.cone = [M0 .. M_{L-1}]): layer l visits M_{L-l+1}, one hop
+        out from the set its dZ_l was written on.  dX_l goes into a pooled all-zero buffer (the readout gradient's pool: same shape,
+        same all-zero state) on the visited items only; once its consumer has run, the masked clear wipes exactly those items."""
+        hs, y0, cone = saved.hs, saved.y0, saved.cone
+        L = len(hs) - 1
+        dz, key = self._readout_grad(hs[-1], saved.bh, logp, d_logp, last_dev, weights, grads)
+        wrote = None                                    # the mask dz was written on (None: the readout's rows, wiped by _release_top)
+        for i in reversed(range(1, L)):
+            w, g, visit = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3], cone[L - i]
+            if i == 1:                                  # H1 was never stored: aux from y0, dW_first in the same launch, no dx
+                assert self.conv.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit), \
+                    "visiting fused-first backward not served"
+                dx = None
+            else:
+                pool = self._dz_zero.get(key)
+                dx = pool.pop() if pool else torch.zeros_like(dz)
+                assert self.conv.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit) is not False, "visiting backward not served"
+            if wrote is None:
+                self._release_top(dz, key, last_dev)
+            else:
+                self.conv.clear_mask(dz, wrote)
+                self._dz_zero.setdefault(key, []).append(dz)
+            dz, wrote = dx, visit
+        return grads
+
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         if saved.wide:
             return self._wide_backward(saved, logp, d_logp, last_dev, weights, grads)
+        if saved.cone is not None:
+            return self._cone_backward(saved, logp, d_logp, last_dev, weights, grads)
         hs, bh, y0, activity = saved.hs, saved.bh, saved.y0, saved.activity
         dz_top, key = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
         S, E, ns, C = hs[-1].shape
@@ -1553,7 +1658,7 @@ class PowerPlan(SconePlan):
                 if i == 0 and x.shape[3] == 1:
                     y0 = torch.cat([x, g1, g2, torch.zeros_like(x)], dim=3)  # the shifted input per point, for the first layer's weight gradient
             hs.append(out)
-        return hs, y0
+        return hs, y0, None
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         hs, bh, y0 = saved.hs, saved.bh, saved.y0
