@@ -397,6 +397,17 @@ int scn_conv_shifted_input_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, co
                                 void* stream);
 int scn_clear_mask(scn_conv_t conv, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream);
 
+/* Diagnostic, like scn_conv_plan_blocks; no step uses it.  The masked launches above do not walk a workgroup's units one at a time:
+ * ahead of the block loop a workgroup fetches the blocks and the mask windows of its units in batches and keeps, in order, the units
+ * whose window is non-zero.  scn_window_scan_probe runs that same device helper on grid_x workgroups (a multiple of 8, at least 8)
+ * for the slab range [slab0, slab0 + n_it) of a mask of scn_keep_mask's geometry (1 <= n_it <= 64, slab0 < n_slabs) and writes what
+ * each workgroup g would visit: out_count[g] = the length of its sequence, out_block / out_window [g * cap + i] = the plan block and
+ * the window (bit j = slab slab0 + j, cut to n_it bits, never zero) of its i-th entry for i < min(out_count[g], cap).
+ * unit_block (NULL: not wanted) receives the launch's unit -> block table [n_blocks] (the cost-balanced assignment of that grid, or the
+ * identity where the grid has none): workgroup g owns the units first + k * (grid_x / 8) < last of XCD range g % 8. */
+int scn_window_scan_probe(scn_conv_t conv, int32_t n_slabs, const uint32_t* mask, int32_t grid_x, int32_t slab0, int32_t n_it, int32_t cap,
+                          int32_t* out_block, uint64_t* out_window, int32_t* out_count, int32_t* unit_block, void* stream);
+
 /* Backward of the layer that FOLLOWS the first one, fused with the first layer's weight gradient (what jax.grad of TE:144-149
  * yields for weights[0:6], STM:307, in one pass):
  *   this layer :  dW[slot] += aux^T G_slot                       (as scn_conv_backward; aux = the first layer's output)

@@ -122,9 +122,9 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // window is all ones there and the kernel is the plain one.  A visit with its bit clear reads NEITHER staging buffer: they hold
 // other slabs' data.
 // VISIT (plain C = 32 and FIRST + FROMY, dense launches): the mirror of fwd_c32_w16_kernel<KEEP> -- only the (block, slab) items of a
-// visit mask V are VISITED.  The block's 64-bit window is fetched first (keep_window, cut to this workgroup's slab range), a block
-// with an empty window is left before its metadata is read, and the slab loop runs over the window's set bits with its cursor in
-// SGPRs (scn_keep_bits.h): no memory operation for the walk inside the slab loop.  A visit that runs is staged, gathered, contracted
+// visit mask V are VISITED.  The workgroup's blocks with a visit and their 64-bit windows (cut to its slab range) come from one batched
+// scan ahead of the block loop (scn_window_scan.inc), in unit order; a block with an empty window never enters the loop, and the slab
+// loop runs over the window's set bits with its cursor in SGPRs (scn_keep_bits.h): no memory operation for the walk inside the slab loop.  A visit that runs is staged, gathered, contracted
 // (or early-outed) and stored exactly as in the plain forms, in ascending slab order on the plain call's grid, so wherever every
 // item outside V would have taken the zero-tile early-out the weight-gradient partials see the same tiles in the same order.  dx
 // (plain form) is written on the visited items only; aux / y outside V and dz of items no visited item stages are not read.  The
@@ -209,20 +209,18 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     int e_run = 1 << 20;                                      // running exponent of the dW accumulators (see the header): none yet
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     SCN_UNIT_RANGE();
+    SCN_WINDOW_WALK(VISIT, (KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}), smem + smem_bytes_c32(B32_EXTRA_BYTES));
     uint32_t cqs[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) cqs[q] = (uint32_t)((n * 8 + h * 4 + q) ^ (n >> 1)) << 4;
     const size_t slab_bytes = (size_t)n_cols * (PAIR ? 256 : PIECE);
     const bool second = PAIR && (((lane >> 2) ^ wave) & 1);       // this lane's LDS-DMA chunks come from slab B (see dma_k)
-    if (listed || slab0 < slab1)
-    SCN_UNIT_BEGIN()
-        // VISIT: the block's window FIRST, cut to this workgroup's slab range; a block without a visit is left here, before the
-        // barrier and its metadata (the same scalar in all eight waves: they leave together).  (dense launches only: k0 = slab0)
-        uint64_t vw = 0;                                          // the cursor: its lowest set bit is the visit handled next
-        if (VISIT) {
-            vw = keep_cut(keep_window(KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}, b, k0), n_it);
-            if (vw == 0) continue;
-        }
+    if (listed || slab0 < slab1) {
+    // VISIT: the units are the blocks of this workgroup that have a visit, with their windows cut to its slab range, from the batched
+    // scan ahead of the loop (scn_window_scan.inc): a block without a visit never enters the loop -- no barrier, no metadata.  The
+    // table is the same in all eight waves.  (dense launches only: k0 = slab0)
+    SCN_UNIT_BEGIN_MASKED(VISIT)
+        uint64_t vw = VISIT ? win_ : 0;                           // the cursor: its lowest set bit is the visit handled next
         wait_all_and_barrier();
         const BlockMeta m = load_block_c32<BK_THREADS>(P, b, sm);
         // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
@@ -573,6 +571,8 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             }
             STAMP_ADD(4);
         }
+    }
+    SCN_UNIT_END_MASKED(VISIT);
     }
     STAMP_FLUSH();
     wait_all_and_barrier();

@@ -312,6 +312,25 @@ __device__ __forceinline__ void block_range(int n_blocks, int& first, int& last,
         const int k0 = listed ? wl.ptr[u_] : slab0;                                  \
         const int n_it = listed ? wl.ptr[u_ + 1] - k0 : slab1 - slab0;               \
         if (n_it <= 0) continue;
+// The unit loop of a kernel that also has MASKED forms (MASKED: a compile-time constant; dense launches): there the units are the
+// entries of the workgroup's batched window scan (WindowWalk, scn_window_scan.inc; its table lives at LDS, WSCAN_LDS_BYTES of the
+// launch's dynamic LDS) -- the same blocks in the same ascending unit order, minus the ones whose window is empty -- and win_ is the
+// unit's window, cut to this workgroup's slab range and non-zero.  The loop is SCN_UNIT_BEGIN's, token for token: a masked form points
+// its counters at the table (u_ = entry, u_end_ = entries, u_stride_ = 1) and comes back for the next WSCAN_CAP units behind the loop
+// (SCN_UNIT_END_MASKED, after the loop's closing brace), so the walk costs a masked form one scalar across its slab loop (the scans
+// done) and a form without a mask nothing.  SCN_WINDOW_WALK declares the walk, once, behind SCN_UNIT_RANGE().
+#define SCN_WINDOW_WALK(MASKED, KM, LDS) WindowWalk walk_((MASKED), (LDS), P.n_blocks, P.assign, (KM), slab0, slab1 - slab0)
+#define SCN_UNIT_BEGIN_MASKED(MASKED)                                                \
+    scn_next_units_:                                                                 \
+    if (MASKED) walk_.scan_units(u_, u_end_, u_stride_);                             \
+    for (; u_ < u_end_; u_ += u_stride_) {                                           \
+        const int b = (MASKED) ? walk_.block(u_) : (listed ? wl.block[u_] : (P.assign ? P.assign[u_] : u_)); \
+        const uint64_t win_ = (MASKED) ? walk_.window(u_) : ~0ull;                   \
+        const int k0 = listed ? wl.ptr[u_] : slab0;                                  \
+        const int n_it = listed ? wl.ptr[u_ + 1] - k0 : slab1 - slab0;               \
+        if (n_it <= 0) continue;
+#define SCN_UNIT_END_MASKED(MASKED) \
+    if ((MASKED) && walk_.more()) goto scn_next_units_
 #define SLAB_AT(it) (listed ? wl.slab[k0 + (it)] : k0 + (it))
 // the same as a scalar: the readfirstlane sits INSIDE the listed arm, so that the vector load of the list entry and its s_waitcnt
 // vmcnt(0) -- a wait for every LDS-DMA and store the wave has in flight -- stay out of the dense path, whose slab index then never

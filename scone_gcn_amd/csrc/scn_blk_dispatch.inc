@@ -82,6 +82,12 @@ constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
 constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
 constexpr KeepMask NO_KEEP{nullptr, 0};
 
+// The masked 32-channel forms and gather3_c1_keep_kernel are launched with WSCAN_LDS_BYTES more dynamic LDS than the forms without a
+// mask, for the table of their window scan (scn_window_scan.inc); the grid is still picked from the plain form's footprint.
+static_assert(W16_EXTRA_BYTES + W16_FIRSTW_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16) &&
+              B32_EXTRA_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
+              "the scan's table fits behind the kernels' own LDS");
+
 // The keep mask of a launch (scn_conv_forward_keep / _from_y_keep; the source mask of scn_conv_backward_dzmask has its geometry and
 // its window limit): words per block from the slab count.  A workgroup holds the bits
 // of its slab range in one 64-bit window (keep_window): false where the grid hands one more than that.
@@ -136,7 +142,7 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
         return with_act(act, [&](auto A) -> int {
             constexpr int ACT = decltype(A)::value;
             if (keep)
-                return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1], W[2],
+                return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, src[0], nullptr, W[0], W[1], W[2],
                                       out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(keep, n_slabs));
             return launch_checked(partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0],
                                   partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP);
@@ -168,7 +174,7 @@ int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float
     const size_t lds = smem_bytes(16);
     const dim3 grid = launch_grid(c, n_slabs, lds);
     if (!keep_fits(grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
-    return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds, st, c->plan.dev, x, y_out, c->n_rows, c->g[0].n_cols,
+    return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, st, c->plan.dev, x, y_out, c->n_rows, c->g[0].n_cols,
                           n_slabs, keep_mask_of(keep, n_slabs));
 }
 
@@ -187,7 +193,7 @@ int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const flo
     return with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         if (keep)
-            return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2], out, L.nr,
+            return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, y, nullptr, W[0], W[1], W[2], out, L.nr,
                                   L.nc, n_slabs, NO_LIST, fw, keep_mask_of(keep, n_slabs));
         return launch_checked(fwd_c32_from_y<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
                               out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP);
@@ -234,7 +240,8 @@ int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz,
     const int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         if (mask)                                                // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
-            return launch_checked(dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0],
+            return launch_checked(dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS),
+                                  lds + (dzmask ? 0 : WSCAN_LDS_BYTES), st, L.P, dz[0],
                                   (const float*)mask, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, wl, nullptr, NO_FIRSTW);
         const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
@@ -286,7 +293,7 @@ int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const fl
     int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         if (visit)                                               // (the mask's words ride in aux, which this form does not read)
-            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2],
+            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, dz, y, W[0], W[1], W[2],
                                   (const float*)visit, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw);
         const auto k = W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2], W_first ? nullptr : aux, nullptr, partial,
@@ -368,6 +375,16 @@ int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, con
     if (!c->plan.built || ns != BK_NS || (ns * ch) % 4 || (reinterpret_cast<uintptr_t>(t) & 15)) return SCN_ERR_UNSUPPORTED;
     return launch_checked(clear_mask_kernel, dim3(std::min(c->plan.dev.n_blocks, 2048)), dim3(256), 0, st, c->plan.dev,
                           keep_mask_of(mask, n_slabs), t, c->n_rows, n_slabs, ns * ch);
+}
+
+// scn_window_scan_probe: the walk of the masked kernels (WindowWalk) on gx workgroups, written out (window_scan_probe_kernel).
+int blocked_window_scan_probe(scn_conv_s* c, int n_slabs, const uint32_t* mask, int gx, int slab0, int n_it, int cap, int32_t* out_block,
+                              uint64_t* out_window, int32_t* out_count, int32_t* unit_block, hipStream_t st) {
+    if (!c->plan.built) return SCN_ERR_UNSUPPORTED;
+    PlanDev P = c->plan.dev;
+    P.assign = balanced_assignment(c, gx);
+    return launch_checked(window_scan_probe_kernel, dim3(gx), dim3(256), 0, st, P, keep_mask_of(mask, n_slabs), slab0, n_it, cap, out_block,
+                          out_window, out_count, unit_block);
 }
 
 // ---- "power" layers: one operator S (identity + one value array), three terms  X0, S-input's own row, S * input ----

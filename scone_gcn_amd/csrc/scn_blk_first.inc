@@ -5,8 +5,8 @@
 // gather3_c1_kernel computes Y[p] = (x, S_lo x, S_up x)[p] from the 16-byte input pieces (the gather of fwd_c1, 12 bytes per
 // point out); dw_first_stream_kernel then reads dz exactly once, coalesced, with no LDS gather at all -- an HBM stream.
 // ------------------------------------------------------------------------------------------------
-// KEEP (gather3_c1_keep_kernel): only the (block, slab) items of a keep mask are visited, as in fwd_c32_w16_kernel<KEEP> -- the block's
-// window first, a block with an empty window skipped before load_block, the slab loop over the window's set bits (scn_keep_bits.h).
+// KEEP (gather3_c1_keep_kernel): only the (block, slab) items of a keep mask are visited, as in fwd_c32_w16_kernel<KEEP> -- the blocks
+// with a kept slab and their windows from the batched scan (scn_window_scan.inc), the slab loop over a window's set bits (scn_keep_bits.h).
 // The records of a kept item are the plain kernel's bits, every other row of Y is left untouched; X is read in full (it is the input).
 template <bool KEEP>
 __device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* __restrict__ X, float* __restrict__ Y, int n_rows,
@@ -15,16 +15,18 @@ __device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* _
     constexpr int PIECE = 16;
     const Smem sm = carve(smem, PIECE);
     const int tid = threadIdx.x;
-    int b, b_end, b_stride;
-    block_range(P.n_blocks, b, b_end, b_stride);
+    int u, b_end, b_stride;
+    block_range(P.n_blocks, u, b_end, b_stride);
     SCN_SLAB_RANGE();
     if (slab0 >= slab1) return;
-    for (; b < b_end; b += b_stride) {
-        uint64_t keep = ~0ull;                                    // KEEP: the cursor, its lowest set bit is the next visit's slab
-        if (KEEP) {
-            keep = keep_cut(keep_window(km, b, slab0), slab1 - slab0);
-            if (keep == 0) continue;
-        }
+    // KEEP: the blocks of this workgroup that have a kept slab, from the batched scan ahead of the loop (scn_window_scan.inc; its
+    // table sits behind the kernel's own LDS)
+    WindowWalk walk(KEEP, smem + smem_bytes(PIECE), P.n_blocks, nullptr, km, slab0, slab1 - slab0);
+next_units:
+    if (KEEP) walk.scan_units(u, b_end, b_stride);                // (u, b_end, b_stride now walk the scan's table)
+    for (; u < b_end; u += b_stride) {
+        const int b = KEEP ? walk.block(u) : u;
+        uint64_t keep = KEEP ? walk.window(u) : ~0ull;            // KEEP: the cursor, its lowest set bit is the next visit's slab
         wait_all_and_barrier();
         const BlockMeta m = load_block(P, b, sm);
         __syncthreads();
@@ -61,6 +63,7 @@ __device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* _
             for (int slab = slab0; slab < slab1; ++slab) visit(slab, slab - slab0, slab + 1 < slab1 ? slab + 1 : -1);
         }
     }
+    if (KEEP && walk.more()) goto next_units;
 }
 __global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, const float* __restrict__ X,
                                                                    float* __restrict__ Y, int n_rows, int n_cols,
@@ -174,20 +177,39 @@ __global__ __launch_bounds__(256) void clear_list_kernel(PlanDev P, WorkList wl,
 }
 
 // The mask-driven twin: +0 over the block's rows of slab s for every set bit (b, s) of a mask of scn_keep_mask's geometry (a bit at or
-// past n_slabs names no slab).  Plain 16-byte vector stores, no atomics; a workgroup walks its blocks' words with scalar loads.
+// past n_slabs names no slab).  Plain 16-byte vector stores, no atomics; a workgroup walks a listed block's words with scalar loads.
+// The workgroup's blocks b = blockIdx.x + k * gridDim.x are tested FIRST, one per thread with all loads in flight together (256 per
+// pass), and the non-empty ones listed in LDS; only those are then walked (a zero store is the same in any order).
 __global__ __launch_bounds__(256) void clear_mask_kernel(PlanDev P, KeepMask km, float* __restrict__ T, int n_rows, int n_slabs,
                                                          int row_floats) {
-    for (int b = blockIdx.x; b < P.n_blocks; b += gridDim.x) {
-        const uint32_t* mw = km.bits + (size_t)b * km.words;
-        const int row0 = P.blk_row0[b], count = P.blk_rows[b] * row_floats / 4;
-        for (int w = 0; w < km.words; ++w) {
-            for (uint32_t bits = mw[w]; bits; bits &= bits - 1) {
-                const int s = 32 * w + __builtin_ctz(bits);
-                if (s >= n_slabs) break;
-                f32x4* t = (f32x4*)(T + ((size_t)s * n_rows + row0) * row_floats);
-                for (int i = threadIdx.x; i < count; i += 256) t[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    __shared__ int32_t live[256];
+    __shared__ int32_t n_live;
+    for (int64_t b0 = blockIdx.x; b0 < P.n_blocks; b0 += (int64_t)gridDim.x * 256) {
+        if (threadIdx.x == 0) n_live = 0;
+        __syncthreads();
+        const int64_t bt = b0 + (int64_t)threadIdx.x * gridDim.x;
+        if (bt < P.n_blocks) {
+            const uint32_t* tw = km.bits + (size_t)bt * km.words;
+            uint32_t any = 0;
+            for (int w = 0; w < km.words; ++w) any |= tw[w];
+            if (any) live[atomicAdd(&n_live, 1)] = (int32_t)bt;
+        }
+        __syncthreads();
+        const int n = n_live;
+        for (int j = 0; j < n; ++j) {
+            const int b = __builtin_amdgcn_readfirstlane(live[j]);
+            const uint32_t* mw = km.bits + (size_t)b * km.words;
+            const int row0 = P.blk_row0[b], count = P.blk_rows[b] * row_floats / 4;
+            for (int w = 0; w < km.words; ++w) {
+                for (uint32_t bits = mw[w]; bits; bits &= bits - 1) {
+                    const int s = 32 * w + __builtin_ctz(bits);
+                    if (s >= n_slabs) break;
+                    f32x4* t = (f32x4*)(T + ((size_t)s * n_rows + row0) * row_floats);
+                    for (int i = threadIdx.x; i < count; i += 256) t[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
             }
         }
+        __syncthreads();                                          // (the list is rewritten by the next pass)
     }
 }
 

@@ -221,25 +221,21 @@ template <int I> __device__ __forceinline__ void fwd_prio() { __builtin_amdgcn_s
 constexpr int W16_FIRSTW_BYTES = 3 * 32 * 4;              // FROMY: the first layer's weights [g][32], behind the plain form's extra bytes
 // KEEP (plain and from-y forms, dense launches): the layer is the LAST one and only the readout reads its output -- `km` holds a bit
 // per (plan block, slab) (scn_keep_mask) and only the items whose bit is set are VISITED: a block's slab loop runs over the set
-// bits of its window (visit i = the slab of the i-th set bit), a block without one is left before its metadata is read.  An item
+// bits of its window (visit i = the slab of the i-th set bit), a block without one never enters the block loop: the workgroup's blocks
+// with a kept slab and their windows come from one batched scan ahead of the loop (scn_window_scan.inc), in unit order.  An item
 // whose bit is clear is not staged, gathered or contracted, and no byte of its rows is written; a visit that runs is staged,
 // gathered, contracted (or early-outed) and stored exactly as in the other forms, so a kept row holds the plain forward's bits.
 // The decision depends on the trajectories' last nodes, never on a value.  (The slab-pair kernel fwd_c16_w16_kernel<KEEP> still
 // visits every pair and only drops the store.)
-// keep_window: the bits of block b for the KEEP_WINDOW slabs from `first` on (bit j = slab first + j), fetched ONCE per block,
+// keep_window (the slab-pair form and the backward's DZMASK; the visiting forms take their windows from the scan, which follows the
+// same rule): the bits of block b for the KEEP_WINDOW slabs from `first` on (bit j = slab first + j), fetched ONCE per block,
 // ahead of the block's metadata, made wave-uniform and claimed there: nothing of it is in flight when the slab loop starts (a
 // scalar load in flight there turns the gather's counted lgkmcnt waits into lgkmcnt(0), a vector load is followed by vmcnt(0), a
 // wait for the LDS-DMA just issued: profiles/HISTORY.md section 3.2); the slab loop walks it in SGPRs (scn_keep_bits.h).  The host
 // hands a workgroup at most KEEP_WINDOW slabs.
 constexpr int KEEP_WINDOW = 64;
 __device__ __forceinline__ uint64_t keep_window(const KeepMask km, int b, int first) {
-    const uint32_t* mw = km.bits + (size_t)b * km.words;
-    const int w0 = first >> 5, sh = first & 31;
-    const int last = km.words - 1, w1 = w0 + 1 < last ? w0 + 1 : last, w2 = w0 + 2 < last ? w0 + 2 : last;   // three loads, no branch
-    const uint32_t a = mw[w0], c1 = mw[w1], d2 = mw[w2];
-    const uint32_t c = w0 + 1 <= last ? c1 : 0u, d = w0 + 2 <= last ? d2 : 0u;                                // (words past the row: no slab)
-    uint64_t win = (((uint64_t)c << 32) | a) >> sh;
-    if (sh) win |= (uint64_t)d << (64 - sh);
+    const uint64_t win = keep_window_lane(km, b, first);      // (scn_window_scan.inc: three loads, no branch; the one copy of the rule)
     uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)win), hi = __builtin_amdgcn_readfirstlane((uint32_t)(win >> 32));   // wave-uniform
     asm volatile("" : "+s"(lo), "+s"(hi));                    // the loads are waited for HERE
     return ((uint64_t)hi << 32) | lo;
@@ -299,6 +295,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     }
     SCN_UNIT_RANGE();
     if (!listed && slab0 >= slab1) return;
+    SCN_WINDOW_WALK(KEEP, km, smem + smem_bytes_c32(W16_EXTRA_BYTES + (FROMY ? W16_FIRSTW_BYTES : 0)));
 #if SCN_FWD_PRIO == 2
     if (wave >= 12) __builtin_amdgcn_s_setprio(3); else if (wave >= 8) __builtin_amdgcn_s_setprio(2); else if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #elif SCN_FWD_PRIO == 3
@@ -318,16 +315,12 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     // pending tile) keep their registers -- as one path the compiler paid ~20 register moves per visit to reconcile the two roles.
     auto run = [&](auto late_c) {
     constexpr int late = decltype(late_c)::value;
-    SCN_UNIT_BEGIN()
-        // KEEP: the block's window FIRST, cut to this workgroup's slab range (the bits above n_it are other workgroups' slabs); a
-        // block without a kept slab is left here, before its metadata is touched, before the barrier and before any LDS write.
-        // The window is the same scalar in all sixteen waves, so they leave together; a tile pending from an earlier block stays
-        // pending.  (dense launches only: k0 = slab0)
-        uint64_t keep = ~0ull;
-        if (KEEP) {
-            keep = keep_cut(keep_window(km, b, k0), n_it);
-            if (keep == 0) continue;
-        }
+    // KEEP: the units are the blocks of this workgroup that have a kept slab, with their windows cut to its slab range (the bits
+    // above n_it are other workgroups' slabs), from the batched scan ahead of the loop (scn_window_scan.inc): a block without a kept
+    // slab never enters the loop -- its metadata is not touched, no barrier, no LDS write; a tile pending from an earlier block
+    // stays pending.  The table is the same in all sixteen waves.  (dense launches only: k0 = slab0)
+    SCN_UNIT_BEGIN_MASKED(KEEP)
+        const uint64_t keep = win_;
         const int n_vis = KEEP ? keep_count(keep) : n_it;             // visits of this block: visit i = the slab of the i-th set bit
         wait_all_and_barrier();
         BlockMeta m;
@@ -581,6 +574,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
             }
         }
     }
+    SCN_UNIT_END_MASKED(KEEP);
     };
 #ifndef SCN_FWD_NO_STAGGER
     if (wave >> 3) run(std::integral_constant<int, 1>{});

@@ -57,6 +57,8 @@ int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y,
 int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* wl, hipStream_t st);
 int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st);
 int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st);
+int blocked_window_scan_probe(scn_conv_s* c, int n_slabs, const uint32_t* mask, int gx, int slab0, int n_it, int cap, int32_t* out_block,
+                              uint64_t* out_window, int32_t* out_count, int32_t* unit_block, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // generic kernels
@@ -667,6 +669,15 @@ int scn_clear_mask(scn_conv_t c, int32_t n_slabs, int32_t ns, int32_t channels, 
     if (!c || !tensor || !mask) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0 || ns <= 0 || channels <= 0) return SCN_ERR_BAD_SHAPE;
     return blocked_clear_mask(c, n_slabs, ns, channels, tensor, mask, (hipStream_t)stream);
+}
+
+int scn_window_scan_probe(scn_conv_t c, int32_t n_slabs, const uint32_t* mask, int32_t grid_x, int32_t slab0, int32_t n_it, int32_t cap,
+                          int32_t* out_block, uint64_t* out_window, int32_t* out_count, int32_t* unit_block, void* stream) {
+    if (!c || !mask || !out_block || !out_window || !out_count) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || grid_x < 8 || grid_x % 8 || grid_x > 65536 || slab0 < 0 || slab0 >= n_slabs || n_it < 1 || n_it > 64 || cap < 1)
+        return SCN_ERR_BAD_SHAPE;
+    return blocked_window_scan_probe(c, n_slabs, mask, grid_x, slab0, n_it, cap, out_block, out_window, out_count, unit_block,
+                                     (hipStream_t)stream);
 }
 
 int scn_conv_shifted_input_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,

@@ -606,6 +606,26 @@ class ConvOp:
               "scn_conv_plan_blocks")
         return row0
 
+    def window_scan_probe(self, mask, n_slabs, grid_x, slab0, n_it):
+        """Diagnostic (scn_window_scan_probe): what each of grid_x workgroups of a masked launch would visit for the slab range
+        [slab0, slab0 + n_it) of `mask` (int32 words [n_blocks][ceil(n_slabs / 32)]).  Returns (sequences, unit_block): sequences[g] =
+        [(plan block, window), ...] of workgroup g in visiting order (window: bit j = slab slab0 + j, never zero), unit_block = the
+        launch's unit -> block table (NumPy int32 [n_blocks])."""
+        nb = self.plan_info()[0]
+        cap = max(1, -(-(-(-nb // 8) + 1) // max(1, grid_x // 8)))   # units of a workgroup: its XCD's share over grid_x / 8, rounded up
+        dev = mask.device
+        blk = torch.full((grid_x, cap), -1, device=dev, dtype=torch.int32)
+        win = torch.zeros((grid_x, cap), device=dev, dtype=torch.int64)
+        cnt = torch.full((grid_x,), -1, device=dev, dtype=torch.int32)
+        ub = torch.full((nb,), -1, device=dev, dtype=torch.int32)
+        check(_lib.load().scn_window_scan_probe(self.handle, n_slabs, _dev(mask, torch.int32), grid_x, slab0, n_it, cap, _dev(blk, torch.int32),
+                                                _dev(win, torch.int64), _dev(cnt, torch.int32), _dev(ub, torch.int32), _stream()),
+              "scn_window_scan_probe")
+        torch.cuda.synchronize()
+        blk, win, cnt = blk.cpu().numpy(), win.cpu().numpy().view(np.uint64), cnt.cpu().numpy()
+        assert int(cnt.min()) >= 0 and int(cnt.max()) <= cap, "a workgroup's sequence is longer than its units"
+        return [[(int(blk[g, i]), int(win[g, i])) for i in range(cnt[g])] for g in range(grid_x)], ub.cpu().numpy()
+
     def dw_first_served(self, dz):
         """Whether dw_first takes this gradient tensor's shape (scn_conv_dw_first_workspace > 0)."""
         S, rows, ns, c = dz.shape
