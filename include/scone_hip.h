@@ -397,6 +397,39 @@ int scn_conv_shifted_input_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, co
                                 void* stream);
 int scn_clear_mask(scn_conv_t conv, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream);
 
+/* Unit lists.  A masked launch hands every workgroup a FIXED share of the plan's blocks, and the launch ends with its busiest
+ * workgroup; the items of a cone lie in a few neighbouring blocks per trajectory, so the shares are uneven.  The forward-side launches
+ * write items that do not depend on the workgroup that computes them, so they may take their units from one device-wide list of the
+ * mask's non-empty words instead: workgroup g of G takes entries g, g + G, g + 2 G, ...  (The visiting backwards sum dW in visit
+ * order and keep their shares.)
+ * A unit list of a mask[n_blocks][words]: uint32 entries b * words + w, one for every NON-ZERO word mask[b][w], each exactly once, in
+ *   no particular order, and their number in a device counter.  capacity (entries the caller's `units` holds) must be at least
+ *   n_blocks * words: SCN_ERR_WORKSPACE otherwise, before any launch; SCN_ERR_UNSUPPORTED where n_blocks * words exceeds 2^31 - 1.
+ * scn_keep_mask_units = scn_keep_mask that also writes the mask's list.  `mask` then has SCN_UNIT_COUNTERS more words behind its
+ *   n_blocks * words, which the call's one memset clears with the mask: word 0 of them receives the count, the others are left zero
+ *   for the caller (the counters of the masks hopped from this one).  units = NULL: scn_keep_mask, to the letter (no extra words).
+ * scn_mask_hop_units = scn_mask_hop that also writes the list of `out`; *unit_count must be zero on entry (device).  units =
+ *   unit_count = NULL: scn_mask_hop, to the letter.  Neither call adds a launch, a memset or a synchronisation.
+ * scn_conv_forward_keep_units / scn_conv_forward_from_y_keep_units / scn_conv_shifted_input_keep_units = the calls without _units
+ *   with the list of their mask `keep`: the same rows written with the same bits, whatever the order of the entries.  CONTRACT: the
+ *   list names every non-zero word of `keep` for the call's n_slabs exactly once (a word left out is not visited, a word named twice
+ *   is computed twice).  The list is used where the launch grid has one slab range (n_slabs <= 64 and no slab split); any other launch
+ *   walks the workgroups' fixed shares as the call without a list does -- never an error that call would not return.  units =
+ *   unit_count = NULL: the call without _units, to the letter; one of them NULL: SCN_ERR_BAD_ARG. */
+#define SCN_UNIT_COUNTERS 4
+int scn_keep_mask_units(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
+                        int32_t n_blocks, uint32_t* mask, uint32_t* units /* NULL: scn_keep_mask */, int64_t capacity, void* stream);
+int scn_mask_hop_units(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, const int32_t* adj_blk, const uint32_t* in, uint32_t* out,
+                       uint32_t* units /* NULL: scn_mask_hop */, uint32_t* unit_count, int64_t capacity, void* stream);
+int scn_conv_forward_keep_units(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
+                                const float* const* W, int32_t c_out, int32_t act, float* out, const uint32_t* keep,
+                                const uint32_t* units /* NULL: static shares */, const uint32_t* unit_count, void* stream);
+int scn_conv_forward_from_y_keep_units(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                                       const float* const* W, int32_t channels, int32_t act, float* out, const uint32_t* keep,
+                                       const uint32_t* units /* NULL: static shares */, const uint32_t* unit_count, void* stream);
+int scn_conv_shifted_input_keep_units(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
+                                      const uint32_t* units /* NULL: static shares */, const uint32_t* unit_count, void* stream);
+
 /* Diagnostic, like scn_conv_plan_blocks; no step uses it.  The masked launches above do not walk a workgroup's units one at a time:
  * ahead of the block loop a workgroup fetches the blocks and the mask windows of its units in batches and keeps, in order, the units
  * whose window is non-zero.  scn_window_scan_probe runs that same device helper on grid_x workgroups (a multiple of 8, at least 8)

@@ -19,6 +19,7 @@ SCN_MAX_SLOTS = 4
 ACT = {"none": 0, "tanh": 1, "relu": 2, "leaky_relu": 3}
 SCN_ERR_BAD_ARG = -1              # include/scone_hip.h
 SCN_ERR_UNSUPPORTED = -4
+SCN_ERR_WORKSPACE = -6
 SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
 SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sample_expand
 SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
@@ -136,6 +137,15 @@ SIGNATURES = {
                                                                   c_void_p, c_void_p]),
     "scn_conv_shifted_input_keep": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_clear_mask": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    "scn_keep_mask_units": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
+    "scn_mask_hop_units": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "scn_conv_forward_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
+                                                   c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_conv_forward_from_y_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
+                                                          ctypes.POINTER(c_void_p), c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p]),
+    "scn_conv_shifted_input_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p]),
     "scn_window_scan_probe": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,

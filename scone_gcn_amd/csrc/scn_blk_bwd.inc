@@ -209,7 +209,8 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     int e_run = 1 << 20;                                      // running exponent of the dW accumulators (see the header): none yet
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     SCN_UNIT_RANGE();
-    SCN_WINDOW_WALK(VISIT, (KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}), smem + smem_bytes_c32(B32_EXTRA_BYTES));
+    SCN_WINDOW_WALK(VISIT, (KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}), smem + smem_bytes_c32(B32_EXTRA_BYTES),
+                    (UnitList{nullptr, nullptr}));   // (dW is summed in visit order: the backward keeps its static units)
     uint32_t cqs[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) cqs[q] = (uint32_t)((n * 8 + h * 4 + q) ^ (n >> 1)) << 4;

@@ -318,8 +318,9 @@ __device__ __forceinline__ void block_range(int n_blocks, int& first, int& last,
 // unit's window, cut to this workgroup's slab range and non-zero.  The loop is SCN_UNIT_BEGIN's, token for token: a masked form points
 // its counters at the table (u_ = entry, u_end_ = entries, u_stride_ = 1) and comes back for the next WSCAN_CAP units behind the loop
 // (SCN_UNIT_END_MASKED, after the loop's closing brace), so the walk costs a masked form one scalar across its slab loop (the scans
-// done) and a form without a mask nothing.  SCN_WINDOW_WALK declares the walk, once, behind SCN_UNIT_RANGE().
-#define SCN_WINDOW_WALK(MASKED, KM, LDS) WindowWalk walk_((MASKED), (LDS), P.n_blocks, P.assign, (KM), slab0, slab1 - slab0)
+// done) and a form without a mask nothing.  SCN_WINDOW_WALK declares the walk, once, behind SCN_UNIT_RANGE(); UL: the mask's unit list
+// (the forward-side launches; WindowWalk's list mode) or an empty one.
+#define SCN_WINDOW_WALK(MASKED, KM, LDS, UL) WindowWalk walk_((MASKED), (LDS), P.n_blocks, P.assign, (KM), slab0, slab1 - slab0, (UL))
 #define SCN_UNIT_BEGIN_MASKED(MASKED)                                                \
     scn_next_units_:                                                                 \
     if (MASKED) walk_.scan_units(u_, u_end_, u_stride_);                             \

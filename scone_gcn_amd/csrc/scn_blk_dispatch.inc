@@ -81,6 +81,7 @@ static dim3 launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, int max_pe
 constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
 constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
 constexpr KeepMask NO_KEEP{nullptr, 0};
+constexpr UnitList NO_UNITS{nullptr, nullptr};
 
 // The masked 32-channel forms and gather3_c1_keep_kernel are launched with WSCAN_LDS_BYTES more dynamic LDS than the forms without a
 // mask, for the table of their window scan (scn_window_scan.inc); the grid is still picked from the plain form's footprint.
@@ -93,6 +94,12 @@ static_assert(W16_EXTRA_BYTES + W16_FIRSTW_BYTES + WSCAN_LDS_BYTES <= 160 * 1024
 // of its slab range in one 64-bit window (keep_window): false where the grid hands one more than that.
 static bool keep_fits(unsigned gy, int n_slabs) { return (n_slabs + (int)gy - 1) / (int)gy <= KEEP_WINDOW; }
 static KeepMask keep_mask_of(const uint32_t* keep, int n_slabs) { return KeepMask{keep, (n_slabs + 31) / 32}; }
+// The unit list of a forward-side masked launch (WindowWalk's list mode): served where the grid has ONE slab range of at most
+// KEEP_WINDOW slabs, so that an entry's word lies inside every workgroup's window; any other launch walks its static units, with the
+// same results.
+static UnitList unit_list_of(const uint32_t* units, const uint32_t* count, dim3 grid, int n_slabs) {
+    return units && count && grid.y == 1 && n_slabs <= KEEP_WINDOW ? UnitList{units, count} : NO_UNITS;
+}
 
 // What a launch of a blocked kernel starts from: the plan's device view with the block assignment of the chosen grid, the grid
 // (a work list carries its own slab lists: no slab split then), the operator's shape.
@@ -124,7 +131,8 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wlp,
                     hipStream_t st, const float* partial,              // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
-                    const uint32_t* keep) {                            // keep (32 -> 32 and 16 -> 16, dense, no partial): only the mask's items are stored (32 -> 32: visited)
+                    const uint32_t* keep,                              // keep (32 -> 32 and 16 -> 16, dense, no partial): only the mask's items are stored (32 -> 32: visited)
+                    const uint32_t* units, const uint32_t* unit_count) {   // the mask's unit list (32 -> 32; unit_list_of), or null
     const WorkList wl = wlp ? *wlp : NO_LIST;
     const int ci = c_in[0];
     if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
@@ -143,9 +151,9 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
             constexpr int ACT = decltype(A)::value;
             if (keep)
                 return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, src[0], nullptr, W[0], W[1], W[2],
-                                      out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(keep, n_slabs));
+                                      out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, L.grid, n_slabs));
             return launch_checked(partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0],
-                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP);
+                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP, NO_UNITS);
         });
     }
     if (ci == 16) {                                                       // 16 waves, f16 hi + lo split, two slabs per visit
@@ -170,12 +178,13 @@ int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src,
 
 // The y-only launch of the first layer (blocked_forward with out = nullptr) on the items of a keep mask: gather3_c1_keep_kernel on
 // the plain launch's grid.
-int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st) {
+int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st,
+                               const uint32_t* units, const uint32_t* unit_count) {      // the mask's unit list (unit_list_of), or null
     const size_t lds = smem_bytes(16);
     const dim3 grid = launch_grid(c, n_slabs, lds);
     if (!keep_fits(grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
     return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, st, c->plan.dev, x, y_out, c->n_rows, c->g[0].n_cols,
-                          n_slabs, keep_mask_of(keep, n_slabs));
+                          n_slabs, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, grid, n_slabs));
 }
 
 // Layer 2 of a stack whose first layer has one input channel, straight from the first layer's shifted-input records
@@ -185,7 +194,8 @@ bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
 }
 
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st, const uint32_t* keep) {      // keep: visits and stores by the mask (see blocked_forward)
+                           float* out, hipStream_t st, const uint32_t* keep,        // keep: visits and stores by the mask (see blocked_forward)
+                           const uint32_t* units, const uint32_t* unit_count) {     // the mask's unit list (unit_list_of), or null
     const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
     const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
@@ -194,9 +204,9 @@ int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const flo
         constexpr int ACT = decltype(A)::value;
         if (keep)
             return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, y, nullptr, W[0], W[1], W[2], out, L.nr,
-                                  L.nc, n_slabs, NO_LIST, fw, keep_mask_of(keep, n_slabs));
+                                  L.nc, n_slabs, NO_LIST, fw, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, L.grid, n_slabs));
         return launch_checked(fwd_c32_from_y<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
-                              out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP);
+                              out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP, NO_UNITS);
     });
 }
 
@@ -410,7 +420,7 @@ int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const flo
             return launch_checked(fwd_c16_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc,
                                   n_slabs, NO_LIST, NO_KEEP);
         return launch_checked(fwd_c32_power<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, x, x0, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs,
-                              NO_LIST, NO_FIRSTW, NO_KEEP);
+                              NO_LIST, NO_FIRSTW, NO_KEEP, NO_UNITS);
     });
 }
 

@@ -10,7 +10,7 @@
 // The records of a kept item are the plain kernel's bits, every other row of Y is left untouched; X is read in full (it is the input).
 template <bool KEEP>
 __device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* __restrict__ X, float* __restrict__ Y, int n_rows,
-                                                int n_cols, int n_slabs, const KeepMask km) {
+                                                int n_cols, int n_slabs, const KeepMask km, const UnitList ul) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 16;
     const Smem sm = carve(smem, PIECE);
@@ -21,7 +21,7 @@ __device__ __forceinline__ void gather3_c1_body(const PlanDev& P, const float* _
     if (slab0 >= slab1) return;
     // KEEP: the blocks of this workgroup that have a kept slab, from the batched scan ahead of the loop (scn_window_scan.inc; its
     // table sits behind the kernel's own LDS)
-    WindowWalk walk(KEEP, smem + smem_bytes(PIECE), P.n_blocks, nullptr, km, slab0, slab1 - slab0);
+    WindowWalk walk(KEEP, smem + smem_bytes(PIECE), P.n_blocks, nullptr, km, slab0, slab1 - slab0, ul);
 next_units:
     if (KEEP) walk.scan_units(u, b_end, b_stride);                // (u, b_end, b_stride now walk the scan's table)
     for (; u < b_end; u += b_stride) {
@@ -68,12 +68,12 @@ next_units:
 __global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_kernel(PlanDev P, const float* __restrict__ X,
                                                                    float* __restrict__ Y, int n_rows, int n_cols,
                                                                    int n_slabs) {
-    gather3_c1_body<false>(P, X, Y, n_rows, n_cols, n_slabs, KeepMask{nullptr, 0});
+    gather3_c1_body<false>(P, X, Y, n_rows, n_cols, n_slabs, KeepMask{nullptr, 0}, UnitList{nullptr, nullptr});
 }
 __global__ __launch_bounds__(BK_THREADS, 2) void gather3_c1_keep_kernel(PlanDev P, const float* __restrict__ X,
                                                                         float* __restrict__ Y, int n_rows, int n_cols,
-                                                                        int n_slabs, KeepMask km) {
-    gather3_c1_body<true>(P, X, Y, n_rows, n_cols, n_slabs, km);
+                                                                        int n_slabs, KeepMask km, UnitList ul) {
+    gather3_c1_body<true>(P, X, Y, n_rows, n_cols, n_slabs, km, ul);
 }
 
 constexpr int DWS_THREADS = 256, DWS_BLOCKS = 1024;

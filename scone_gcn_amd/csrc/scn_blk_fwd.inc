@@ -247,7 +247,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
                                                                      const float* __restrict__ W1,
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
-                                                                     int n_slabs, WorkList wl, FirstW fw, KeepMask km) {
+                                                                     int n_slabs, WorkList wl, FirstW fw, KeepMask km, UnitList ul) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave
     static_assert(!FROMY || (!EXT0 && !ACCUM), "the from-y form exists for the plain kernel");
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     }
     SCN_UNIT_RANGE();
     if (!listed && slab0 >= slab1) return;
-    SCN_WINDOW_WALK(KEEP, km, smem + smem_bytes_c32(W16_EXTRA_BYTES + (FROMY ? W16_FIRSTW_BYTES : 0)));
+    SCN_WINDOW_WALK(KEEP, km, smem + smem_bytes_c32(W16_EXTRA_BYTES + (FROMY ? W16_FIRSTW_BYTES : 0)), ul);
 #if SCN_FWD_PRIO == 2
     if (wave >= 12) __builtin_amdgcn_s_setprio(3); else if (wave >= 8) __builtin_amdgcn_s_setprio(2); else if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #elif SCN_FWD_PRIO == 3

@@ -20,7 +20,8 @@ void free_block_plan(scn_conv_s* c);
 bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in, int c_out);
 int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
                     const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wl,
-                    hipStream_t st, const float* partial = nullptr, const uint32_t* keep = nullptr);
+                    hipStream_t st, const float* partial = nullptr, const uint32_t* keep = nullptr, const uint32_t* units = nullptr,
+                    const uint32_t* unit_count = nullptr);
 bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux);
 size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux);
 int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
@@ -39,10 +40,12 @@ size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns
 int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
                            const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
                            hipStream_t st, const float* const* W_first = nullptr, const uint32_t* visit = nullptr);
-int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st);
+int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st,
+                               const uint32_t* units = nullptr, const uint32_t* unit_count = nullptr);
 bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
 int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st, const uint32_t* keep = nullptr);
+                           float* out, hipStream_t st, const uint32_t* keep = nullptr, const uint32_t* units = nullptr,
+                           const uint32_t* unit_count = nullptr);
 int build_terms_plan(scn_conv_s* c, const uint8_t* term, const int32_t* lvl_row0, const uint8_t* merged, const int32_t* bins,
                      int group_rows);
 int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
@@ -547,6 +550,13 @@ int scn_conv_forward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const float
 
 int scn_conv_forward_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
                           const float* const* W, int32_t c_out, int32_t act, float* out, const uint32_t* keep, void* stream) {
+    return scn_conv_forward_keep_units(c, n_slabs, ns, src, c_in, W, c_out, act, out, keep, nullptr, nullptr, stream);
+}
+
+int scn_conv_forward_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
+                                const float* const* W, int32_t c_out, int32_t act, float* out, const uint32_t* keep,
+                                const uint32_t* units, const uint32_t* unit_count, void* stream) {
+    if ((units != nullptr) != (unit_count != nullptr) || (units && !keep)) return SCN_ERR_BAD_ARG;
     if (!keep) return scn_conv_forward_list(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, stream);
     if (!c || !src || !c_in || !W || !out) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
@@ -556,7 +566,8 @@ int scn_conv_forward_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float
         if (!W[s]) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_in[0] != c_out || (c_out != 32 && c_out != 16) || !blocked_forward_supported(c, ns, c_in, c_out))
         return SCN_ERR_UNSUPPORTED;
-    return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, nullptr, (hipStream_t)stream, nullptr, keep);
+    return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, nullptr, (hipStream_t)stream, nullptr, keep, units,
+                           unit_count);
 }
 
 static int generic_bwd_blocks(const scn_conv_s* c, int n_slabs) {
@@ -636,11 +647,18 @@ int scn_conv_forward_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const flo
 int scn_conv_forward_from_y_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
                                  const float* const* W, int32_t channels, int32_t act, float* out, const uint32_t* keep,
                                  void* stream) {
+    return scn_conv_forward_from_y_keep_units(c, n_slabs, ns, y, W_first, W, channels, act, out, keep, nullptr, nullptr, stream);
+}
+
+int scn_conv_forward_from_y_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
+                                       const float* const* W, int32_t channels, int32_t act, float* out, const uint32_t* keep,
+                                       const uint32_t* units, const uint32_t* unit_count, void* stream) {
+    if ((units != nullptr) != (unit_count != nullptr) || (units && !keep)) return SCN_ERR_BAD_ARG;
     if (!c || !y || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !W || !W[0] || !W[1] || !W[2] || !out)
         return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
     if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream, keep);
+    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream, keep, units, unit_count);
 }
 
 int scn_conv_backward_fused_first_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
@@ -682,11 +700,16 @@ int scn_window_scan_probe(scn_conv_t c, int32_t n_slabs, const uint32_t* mask, i
 
 int scn_conv_shifted_input_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
                                 void* stream) {
-    if (!c || !x || !y_out || !keep) return SCN_ERR_BAD_ARG;
+    return scn_conv_shifted_input_keep_units(c, n_slabs, ns, x, y_out, keep, nullptr, nullptr, stream);
+}
+
+int scn_conv_shifted_input_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
+                                      const uint32_t* units, const uint32_t* unit_count, void* stream) {
+    if (!c || !x || !y_out || !keep || (units != nullptr) != (unit_count != nullptr)) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0) return SCN_ERR_BAD_SHAPE;
     const int32_t c_in = 1;
     if (n_slabs > 65535 || c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, 32)) return SCN_ERR_UNSUPPORTED;
-    return blocked_shifted_input_keep(c, n_slabs, x, y_out, keep, (hipStream_t)stream);
+    return blocked_shifted_input_keep(c, n_slabs, x, y_out, keep, (hipStream_t)stream, units, unit_count);
 }
 
 int scn_conv_backward_visit(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,

@@ -225,6 +225,13 @@ struct KeepMask {
     int32_t words;          // words per block = ceil(n_slabs / 32)
 };
 
+// optional unit list of a keep mask (scn_keep_mask_units / scn_mask_hop_units): entry = block * words + word of every non-empty word
+// of the mask, each once, in any order; units == nullptr: the workgroups walk their static units
+struct UnitList {
+    const uint32_t* units;
+    const uint32_t* count;  // the number of entries (device)
+};
+
 // extra plan arrays of a "terms" operator (fused Bunch layer, scn_terms.inc); the common part lives in BlockPlan
 struct TermsPlan {
     bool built = false;

@@ -325,18 +325,56 @@ __global__ __launch_bounds__(1024) void readout_dw_kernel(int nd, int c, const f
 // Keep mask of a last layer's forward (scn_keep_mask): thread = leaf i of slab i / ns, standing on node[i]; bit (b, slab) is set for
 // every block b of T(node[i]) (the `top` table of scn_field_lists).  A node outside [0, n_nodes) or a block outside [0, n_blocks)
 // is a caller's error that is only guarded against: nothing is read or written through it.
+// LIST (scn_keep_mask_units): the thread whose atomic OR found the word zero appends the word's index b * words + w to the mask's
+// unit list -- exactly once per non-empty word, in no particular order; the position is an atomicAdd on the list's counter.  Without
+// a list the kernel is the loop it always was.
+template <bool LIST>
 __global__ __launch_bounds__(256) void keep_mask_kernel(int n, int ns, const int32_t* __restrict__ node, int n_nodes,
                                                         const int32_t* __restrict__ top_ptr, const int32_t* __restrict__ top_blk,
-                                                        int n_blocks, int words, uint32_t* __restrict__ mask) {
+                                                        int n_blocks, int words, uint32_t* __restrict__ mask,
+                                                        uint32_t* __restrict__ units, uint32_t* __restrict__ count, uint32_t capacity) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int v = node[i];
     if (v < 0 || v >= n_nodes) return;
     const int s = i / ns;
     const uint32_t bit = 1u << (s & 31);
-    for (int t = top_ptr[v]; t < top_ptr[v + 1]; ++t) {
-        const int b = top_blk[t];
-        if (b >= 0 && b < n_blocks) atomicOr(&mask[(size_t)b * words + (s >> 5)], bit);
+    if (!LIST) {
+        for (int t = top_ptr[v]; t < top_ptr[v + 1]; ++t) {
+            const int b = top_blk[t];
+            if (b >= 0 && b < n_blocks) atomicOr(&mask[(size_t)b * words + (s >> 5)], bit);
+        }
+        return;
+    }
+    // The OR's old value is a memory round trip, and so is the list position: four blocks of T(v) at a time (most nodes have no
+    // more), their ORs in flight together, then ONE atomicAdd for the chunk's new words -- two dependent round trips per chunk, not
+    // two per block.
+    constexpr int CH = 4;
+    const int t1 = top_ptr[v + 1];
+    for (int t0 = top_ptr[v]; t0 < t1; t0 += CH) {
+        size_t w[CH];
+        bool ok[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int b = t0 + j < t1 ? top_blk[t0 + j] : -1;
+            ok[j] = b >= 0 && b < n_blocks;
+            w[j] = ok[j] ? (size_t)b * words + (s >> 5) : 0;
+        }
+        uint32_t before[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) before[j] = ok[j] ? atomicOr(&mask[w[j]], bit) : ~0u;
+        uint32_t fresh = 0;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) fresh += before[j] == 0;
+        if (fresh) {
+            uint32_t pos = atomicAdd(count, fresh);
+#pragma unroll
+            for (int j = 0; j < CH; ++j)
+                if (before[j] == 0) {
+                    if (pos < capacity) units[pos] = (uint32_t)w[j];   // (capacity >= n_blocks * words, checked by the host: always)
+                    ++pos;
+                }
+        }
     }
 }
 
@@ -346,9 +384,13 @@ __global__ __launch_bounds__(256) void keep_mask_kernel(int n, int ns, const int
 // forward is also where the readout's gradient can be non-zero.  Block b of the backward stages the blocks of A(b) (the `adj` table
 // of scn_field_lists): out[b][w] = OR of in[b'][w] over b' in A(b).  Pull form, thread = (b, w): one plain store per word, no atomics,
 // the result does not depend on any order.  A block outside [0, n_blocks) is only guarded against, as in field_hop_kernel.
+// LIST (scn_mask_hop_units): a thread whose word is non-zero appends its index t to the unit list of `out`; a wave reserves the
+// positions of its non-zero words with ONE atomicAdd on the list's counter.
+template <bool LIST>
 __global__ __launch_bounds__(256) void mask_hop_kernel(int n_blocks, int words, const int32_t* __restrict__ adj_ptr,
                                                        const int32_t* __restrict__ adj_blk, const uint32_t* __restrict__ in,
-                                                       uint32_t* __restrict__ out) {
+                                                       uint32_t* __restrict__ out, uint32_t* __restrict__ units,
+                                                       uint32_t* __restrict__ count, uint32_t capacity) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (int64_t)n_blocks * words) return;
     const int b = (int)(t / words), w = (int)(t - (int64_t)b * words);
@@ -358,6 +400,17 @@ __global__ __launch_bounds__(256) void mask_hop_kernel(int n_blocks, int words, 
         if (b2 >= 0 && b2 < n_blocks) acc |= in[(size_t)b2 * words + w];
     }
     out[t] = acc;
+    if (LIST) {
+        const uint64_t live = __builtin_amdgcn_ballot_w64(acc != 0);        // (of the wave's active lanes)
+        if (live) {
+            const int lead = __builtin_ctzll(live), lane = threadIdx.x & 63;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
+            uint32_t base = 0;
+            if (lane == lead) base = atomicAdd(count, (uint32_t)__builtin_popcountll(live));
+            base = __shfl(base, lead, 64);
+            if (acc != 0 && base + rank < capacity) units[base + rank] = (uint32_t)t;   // (capacity >= n_blocks * words: always)
+        }
+    }
 }
 
 __global__ __launch_bounds__(64) void node_readout_fwd_kernel(int ns, int n_nodes, const float* __restrict__ X,
@@ -721,8 +774,26 @@ int scn_keep_mask(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, c
     const int n_slabs = (n + ns - 1) / ns, words = (n_slabs + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
     SCN_HIP_TRY(hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)n_blocks * words, st));
-    hipLaunchKernelGGL(keep_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, ns, node, n_nodes, top_ptr, top_blk, n_blocks,
-                       words, mask);
+    hipLaunchKernelGGL(keep_mask_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, n, ns, node, n_nodes, top_ptr, top_blk, n_blocks,
+                       words, mask, nullptr, nullptr, 0u);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_keep_mask_units(int32_t n, int32_t ns, const int32_t* node, int32_t n_nodes, const int32_t* top_ptr, const int32_t* top_blk,
+                        int32_t n_blocks, uint32_t* mask, uint32_t* units, int64_t capacity, void* stream) {
+    if (!units) return scn_keep_mask(n, ns, node, n_nodes, top_ptr, top_blk, n_blocks, mask, stream);
+    if (!node || !top_ptr || !top_blk || !mask) return SCN_ERR_BAD_ARG;
+    if (n <= 0 || ns <= 0 || n_nodes <= 0 || n_blocks <= 0) return SCN_ERR_BAD_SHAPE;
+    const int n_slabs = (n + ns - 1) / ns, words = (n_slabs + 31) / 32;
+    const int64_t n_words = (int64_t)n_blocks * words;
+    if (n_words > INT32_MAX) return SCN_ERR_UNSUPPORTED;                  // (an entry and the count are 32-bit)
+    if (capacity < n_words) return SCN_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    // one memset clears the mask and the SCN_UNIT_COUNTERS words behind it; the first of them counts this mask's entries
+    SCN_HIP_TRY(hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)(n_words + SCN_UNIT_COUNTERS), st));
+    hipLaunchKernelGGL(keep_mask_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, n, ns, node, n_nodes, top_ptr, top_blk, n_blocks,
+                       words, mask, units, mask + n_words, (uint32_t)std::min<int64_t>(capacity, INT32_MAX));
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -732,8 +803,22 @@ int scn_mask_hop(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, const 
     if (!adj_ptr || !adj_blk || !in || !out || in == out) return SCN_ERR_BAD_ARG;
     if (n_blocks <= 0 || words <= 0) return SCN_ERR_BAD_SHAPE;
     const int64_t n = (int64_t)n_blocks * words;
-    hipLaunchKernelGGL(mask_hop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_blocks, words, adj_ptr,
-                       adj_blk, in, out);
+    hipLaunchKernelGGL(mask_hop_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_blocks, words,
+                       adj_ptr, adj_blk, in, out, nullptr, nullptr, 0u);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn_mask_hop_units(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, const int32_t* adj_blk, const uint32_t* in, uint32_t* out,
+                       uint32_t* units, uint32_t* unit_count, int64_t capacity, void* stream) {
+    if (!units && !unit_count) return scn_mask_hop(n_blocks, words, adj_ptr, adj_blk, in, out, stream);
+    if (!adj_ptr || !adj_blk || !in || !out || in == out || !units || !unit_count) return SCN_ERR_BAD_ARG;
+    if (n_blocks <= 0 || words <= 0) return SCN_ERR_BAD_SHAPE;
+    const int64_t n = (int64_t)n_blocks * words;
+    if (n > INT32_MAX) return SCN_ERR_UNSUPPORTED;                        // (an entry and the count are 32-bit)
+    if (capacity < n) return SCN_ERR_WORKSPACE;
+    hipLaunchKernelGGL(mask_hop_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_blocks, words,
+                       adj_ptr, adj_blk, in, out, units, unit_count, (uint32_t)std::min<int64_t>(capacity, INT32_MAX));
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

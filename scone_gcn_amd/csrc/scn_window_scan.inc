@@ -16,6 +16,15 @@
 // A workgroup with more than WSCAN_CAP units (small grids on large plans) repeats this per WSCAN_CAP units: one barrier before a scan
 // (every wave has left the previous table) and one after it.  The sequence a workgroup sees -- the same blocks in the same ascending
 // unit order with the same windows as the one-at-a-time walk, minus the empty ones -- is what scn_window_scan_probe writes out.
+// LIST MODE (the forward-side launches with a UnitList; include/scone_hip.h, "Unit lists").  A launch ends with its busiest
+// workgroup, and a cone's items lie in a few neighbouring blocks per trajectory, so the static shares are uneven: on the benchmark's
+// masks the busiest workgroup has 3 .. 6 x the mean visits (tools/cone_balance.py, profiles/cone_unit_list_ab.txt).  The forward-side
+// kernels write items that do not depend on the workgroup computing them, so there the scan's SOURCE changes and nothing else: a
+// unit is an entry of the mask's device-wide list of non-empty words (written by the mask kernels), workgroup g of G takes entries
+// g, g + G, ..., the block comes from the entry and the window is the block's, restricted to the entry's word.  Compaction, table,
+// barriers, the multi-scan loop and everything behind the table are the static walk's; the mode is a runtime branch in wave 0's scan,
+// ahead of the block loop.  The visiting backwards keep the static walk (an empty UnitList, a compile-time constant there): dW is
+// summed in visit order.
 // ------------------------------------------------------------------------------------------------
 constexpr int WSCAN_CHUNK = 64, WSCAN_CHUNKS = 4, WSCAN_CAP = WSCAN_CHUNK * WSCAN_CHUNKS;
 constexpr int WSCAN_LDS_BYTES = 16 + WSCAN_CAP * 12;        // [count, 3 pad words][block][window lo][window hi]
@@ -42,28 +51,36 @@ struct WindowWalk {
     uint32_t* tbl;
     const int32_t* assign;
     KeepMask km;
+    UnitList ul;
     int n_blocks, slab0, n_it, scans;
-    __device__ __forceinline__ WindowWalk(bool on, char* lds, int n_blocks_, const int32_t* assign_, KeepMask km_, int slab0_, int n_it_)
-        : tbl((uint32_t*)lds), assign(assign_), km(km_), n_blocks(on ? n_blocks_ : 0), slab0(slab0_), n_it(n_it_), scans(0) {}
-    // wave 0: the WSCAN_CAP units from cu on, compacted into the table
+    __device__ __forceinline__ WindowWalk(bool on, char* lds, int n_blocks_, const int32_t* assign_, KeepMask km_, int slab0_, int n_it_,
+                                          UnitList ul_ = UnitList{nullptr, nullptr})
+        : tbl((uint32_t*)lds), assign(assign_), km(km_), ul(ul_), n_blocks(on ? n_blocks_ : 0), slab0(slab0_), n_it(n_it_), scans(0) {}
+    // wave 0: the WSCAN_CAP units from cu on, compacted into the table.  LIST MODE (ul.units, see below): a unit is an entry of the
+    // mask's unit list -- its block comes from the entry, its window is the block's, restricted to the entry's word.
     __device__ __forceinline__ void scan(int cu, int last, int stride) {
         const int lane = threadIdx.x & 63;
-        int blk[WSCAN_CHUNKS];
+        const bool lst = ul.units != nullptr;
+        uint32_t ent[WSCAN_CHUNKS];
         bool ok[WSCAN_CHUNKS];
 #pragma unroll
         for (int j = 0; j < WSCAN_CHUNKS; ++j) {
             const int64_t u = (int64_t)cu + (int64_t)(j * WSCAN_CHUNK + lane) * stride;
             ok[j] = u < last;
             const int uc = ok[j] ? (int)u : cu;                       // (a lane past the range reads unit cu again: no branch)
-            blk[j] = assign ? assign[uc] : uc;
+            ent[j] = lst ? ul.units[uc] : (uint32_t)(assign ? assign[uc] : uc);
         }
+        int blk[WSCAN_CHUNKS];
+#pragma unroll
+        for (int j = 0; j < WSCAN_CHUNKS; ++j) blk[j] = lst ? unit_block(ent[j], km.words) : (int)ent[j];
         uint64_t win[WSCAN_CHUNKS];
 #pragma unroll
         for (int j = 0; j < WSCAN_CHUNKS; ++j) win[j] = keep_window_lane(km, blk[j], slab0);
         int base = 0;
 #pragma unroll
         for (int j = 0; j < WSCAN_CHUNKS; ++j) {
-            const uint64_t w = ok[j] ? keep_cut(win[j], n_it) : 0ull;
+            uint64_t w = ok[j] ? keep_cut(win[j], n_it) : 0ull;
+            if (lst) w = keep_word_cut(w, slab0, unit_word(ent[j], km.words));
             const uint64_t live = __builtin_amdgcn_ballot_w64(w != 0);
             const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
             if (w != 0) {                                             // (pos < WSCAN_CAP: one entry per unit at the most)
@@ -73,23 +90,35 @@ struct WindowWalk {
             }
             base += __builtin_popcountll(live);
         }
-        if (lane == 0) tbl[0] = (uint32_t)base;
+        if (lane == 0) {
+            tbl[0] = (uint32_t)base;
+            if (lst) tbl[1] = (uint32_t)last;                         // the list's length, parked for more()
+        }
     }
-    // first unit of the next scan and the range's end and stride
-    __device__ __forceinline__ int64_t next_unit(int& last, int& stride) const {
+    // first unit of the next scan and the range's end and stride.  LIST MODE: workgroup g takes entries g, g + G, g + 2 G, ... of
+    // the device-wide list (G workgroups, one slab range: the dispatch sees to it), so a launch's units are spread evenly whatever
+    // blocks they lie in; the list's length is one load per scan (`fresh`), and more() reads it back from the table's pad word, so
+    // that the walk still holds one scalar of its own across a slab loop.
+    __device__ __forceinline__ int64_t next_unit(int& last, int& stride, bool fresh) const {
+        if (ul.units) {
+            stride = (int)gridDim.x;
+            last = (int)__builtin_amdgcn_readfirstlane(fresh ? *ul.count : tbl[1]);
+            return (int64_t)blockIdx.x + (int64_t)scans * WSCAN_CAP * stride;
+        }
         int first;
         block_range(n_blocks, first, last, stride);
         return (int64_t)first + (int64_t)scans * WSCAN_CAP * stride;
     }
-    // whether units are left to scan
+    // whether units are left to scan (list mode: no scan done = the first one found the list too short for this workgroup)
     __device__ __forceinline__ bool more() const {
+        if (ul.units && scans == 0) return false;
         int last, stride;
-        return next_unit(last, stride) < last;
+        return next_unit(last, stride, false) < last;
     }
     // scans the next WSCAN_CAP units (none left: no entries) and sets the table cursor: entries e = u, u + u_stride, ... < u_end
     __device__ __forceinline__ void scan_units(int& u, int& u_end, int& u_stride) {
         int last, stride;
-        const int64_t cu = next_unit(last, stride);
+        const int64_t cu = next_unit(last, stride, true);
         u = 0;
         u_end = 0;
         u_stride = 1;

@@ -107,6 +107,14 @@ TOP_DZ_MASK = True
 # gradients between layers live in pooled all-zero buffers that a masked clear wipes where their producer wrote (scn_clear_mask).
 # Which items run depends on the last nodes, never on a value.  False: every layer below the top runs in full.
 READOUT_CONE = True
+# A masked launch ends with its busiest workgroup, and the static shares of the blocks (XCD eighths, strided) are uneven on a cone: a
+# trajectory's items lie in a few neighbouring blocks.  The three forward-side launches of a cone (y on M_{L-1}, the from-y layer,
+# the kept layers) write items that do not depend on the workgroup computing them, so with the switch on the mask kernels also write
+# each mask's UNIT LIST -- its non-empty words, once each -- and workgroup g of G takes entries g, g + G, ... of it (WindowWalk's list
+# mode, csrc/scn_window_scan.inc).  Every output bit is the static walk's.  The visiting backwards keep their shares: dW is summed in
+# visit order.  On wherever READOUT_CONE runs; False: the static walk everywhere.
+CONE_UNIT_LIST = True
+UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
 # step, one launch against the layer-by-layer kernels, ms (tools/small_step.py, profiles/r04_small_step_ab.txt):
@@ -283,6 +291,16 @@ def mask_hop_host(mask, adj_ptr, adj_blk):
     return out
 
 
+class UnitList(NamedTuple):
+    """The unit list of a keep mask (include/scone_hip.h, "Unit lists"): every non-empty word of the mask once, in no particular order."""
+    units: object       # int32 [n_blocks * words] device buffer; entry = block * words + word
+    count: object       # int32 [1] device: the number of entries
+
+
+def _unit_ptrs(units):
+    return (_dev(units.units, torch.int32), _dev(units.count, torch.int32)) if units is not None else (None, None)
+
+
 class FieldTables(NamedTuple):
     """Device copies of field_tables for one plan."""
     n_blocks: int
@@ -375,20 +393,51 @@ class ConvOp:
                                            _dev(mask, torch.int32), _dev(out, torch.int32), _stream()), "scn_mask_hop")
         return out
 
+    def keep_mask_units(self, nodes, ns, n_nodes, tabs, key="keep_mask"):
+        """keep_mask() that also writes the mask's unit list (scn_keep_mask_units): returns (mask, UnitList, counters).  The mask and
+        UNIT_COUNTERS counter words behind it are ONE fresh buffer that the call's one memset clears; counters[0] is this list's
+        count, counters[1:] are zero for the lists of the masks hopped from this one (mask_hop_units).  The entries are a fresh
+        buffer per call too: nothing is kept on the operator, two forwards never share a list."""
+        n = nodes.numel()
+        words = (-(-n // ns) + 31) // 32
+        n_words = tabs.n_blocks * words
+        buf = torch.empty(n_words + UNIT_COUNTERS, device=nodes.device, dtype=torch.int32)
+        mask, counters = buf[:n_words].view(tabs.n_blocks, words), buf[n_words:]
+        units = torch.empty(n_words, device=nodes.device, dtype=torch.int32)
+        with _timed(key, _nbytes(mask, nodes)):
+            check(_lib.load().scn_keep_mask_units(n, ns, _dev(nodes, torch.int32), n_nodes, _dev(tabs.top_ptr, torch.int32),
+                                                  _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32),
+                                                  _dev(units, torch.int32), units.numel(), _stream()), "scn_keep_mask_units")
+        return mask, UnitList(units, counters[0:1]), counters
+
+    def mask_hop_units(self, mask, tabs, counter):
+        """mask_hop() that also writes the unit list of its result (scn_mask_hop_units): returns (out, UnitList).  counter: one int32
+        device word that is zero (keep_mask_units hands them out)."""
+        out = torch.empty_like(mask)
+        units = torch.empty(mask.numel(), device=mask.device, dtype=torch.int32)
+        with _timed("dz_mask_hop", _nbytes(mask, out)):
+            check(_lib.load().scn_mask_hop_units(tabs.n_blocks, mask.shape[1], _dev(tabs.adj_ptr, torch.int32),
+                                                 _dev(tabs.adj_blk, torch.int32), _dev(mask, torch.int32), _dev(out, torch.int32),
+                                                 _dev(units, torch.int32), _dev(counter, torch.int32), units.numel(), _stream()),
+                  "scn_mask_hop_units")
+        return out, UnitList(units, counter)
+
     def clear_mask(self, t, mask):
         """+0 over the (block, slab) items of a [S, rows, ns, C] tensor whose bit is set in `mask` (scn_clear_mask)."""
         with _timed("clear_mask", None):
             check(_lib.load().scn_clear_mask(self.handle, t.shape[0], t.shape[2], t.shape[3], _dev(t), _dev(mask, torch.int32), _stream()),
                   "scn_clear_mask")
 
-    def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None):
+    def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None, units=None):
         """wl: WorkList (zero-skipping): only the listed items of `out` are written; `out` must be given, all-zero.
         partial: tensor of the output's shape added to the pre-activation (scn_conv_forward_accumulate; out defaults to it, in place).
         keep: keep_mask() of the launch (last layer, dense): only the kept (block, slab) items of `out` are written, the rest of it
-        holds whatever the buffer held; None when the shape is not served (scn_conv_forward_keep)."""
+        holds whatever the buffer held; None when the shape is not served (scn_conv_forward_keep).
+        units: the UnitList of `keep`: the workgroups take their units from it, with the same results (scn_conv_forward_keep_units)."""
         lib = _lib.load()
         assert wl is None or out is not None
         assert keep is None or (wl is None and partial is None)
+        assert units is None or keep is not None
         if partial is not None:
             assert wl is None and tuple(partial.shape) == (srcs[0].shape[0], self.n_rows, srcs[0].shape[2], c_out)
             out = partial if out is None else out
@@ -412,8 +461,12 @@ class ConvOp:
             # KEPT items only, and their count is on the device; pricing it at the input tensor would print a rate above the HBM
             # peak.  16 channels: every tile is still staged, the input tensor is the model)
             with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if c_in[0] == 32 else _nbytes(*srcs) + self.csr_bytes):
-                st = lib.scn_conv_forward_keep(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
-                                               _dev(keep, torch.int32), _stream())
+                if units is not None:
+                    st = lib.scn_conv_forward_keep_units(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act],
+                                                         _dev(out), _dev(keep, torch.int32), *_unit_ptrs(units), _stream())
+                else:
+                    st = lib.scn_conv_forward_keep(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
+                                                   _dev(keep, torch.int32), _stream())
             return out if _served(st, "scn_conv_forward_keep") else None
         with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if wl is not None else _nbytes(out, *srcs) + self.csr_bytes):
             check(lib.scn_conv_forward_list(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
@@ -495,10 +548,10 @@ class ConvOp:
                                             wl.ref() if wl is not None else None, _stream())
         return (out, y) if _served(st, "scn_conv_forward_first") else None
 
-    def shifted_input(self, x, keep=None):
+    def shifted_input(self, x, keep=None, units=None):
         """y = (x, S_lo x, S_up x, 0) per point of a 1-channel input WITHOUT the first layer's output (scn_conv_forward_first with
         out = NULL); None when the shape is not served.  keep: only the kept (block, slab) items of y are written, the rest of it is
-        uninitialised memory (scn_conv_shifted_input_keep)."""
+        uninitialised memory (scn_conv_shifted_input_keep).  units: the UnitList of `keep`, as in forward."""
         lib = _lib.load()
         S, rows, ns, c_in = x.shape
         if c_in != 1 or self.n_groups != 1 or self.n_slots != 3:
@@ -506,17 +559,21 @@ class ConvOp:
         y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
         if keep is not None:                          # (no byte model, see forward)
             with _timed("conv_fwd c1->y", None):
-                st = lib.scn_conv_shifted_input_keep(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32), _stream())
+                if units is not None:
+                    st = lib.scn_conv_shifted_input_keep_units(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32),
+                                                               *_unit_ptrs(units), _stream())
+                else:
+                    st = lib.scn_conv_shifted_input_keep(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32), _stream())
             return y if _served(st, "scn_conv_shifted_input_keep") else None
         dummy = _ptrs([x] * 3)                        # (the weights are not read without an output; the call checks them for NULL)
         with _timed("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes):
             st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
         return y if _served(st, "scn_conv_forward_first") else None
 
-    def forward_from_y(self, y, Ws_first, Ws, act, keep=None, out=None):
+    def forward_from_y(self, y, Ws_first, Ws, act, keep=None, out=None, units=None):
         """The layer AFTER a 1-channel first layer from that layer's shifted input y and weights Ws_first: act(sum_s (S_s H1) Ws[s]) with
         H1 rebuilt inside the kernel (scn_conv_forward_from_y); None when the shape is not served.  keep: as in forward
-        (scn_conv_forward_from_y_keep)."""
+        (scn_conv_forward_from_y_keep); units: the UnitList of `keep`, as in forward."""
         lib = _lib.load()
         S, rows, ns, _ = y.shape
         c = Ws[0].shape[1]
@@ -529,8 +586,12 @@ class ConvOp:
         # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
         if keep is not None:                          # (no byte model, see forward)
             with _timed("conv_fwd c%d->%d" % (c, c), None):
-                st = lib.scn_conv_forward_from_y_keep(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out),
-                                                      _dev(keep, torch.int32), _stream())
+                if units is not None:
+                    st = lib.scn_conv_forward_from_y_keep_units(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act],
+                                                                _dev(out), _dev(keep, torch.int32), *_unit_ptrs(units), _stream())
+                else:
+                    st = lib.scn_conv_forward_from_y_keep(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out),
+                                                          _dev(keep, torch.int32), _stream())
             return out if _served(st, "scn_conv_forward_from_y_keep") else None
         with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y, out) + self.csr_bytes):
             st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
@@ -1029,6 +1090,13 @@ class SconeState(NamedTuple):
                          # other row of hs[2:] and y0 is uninitialised memory), which the backward visits by; None: the stack ran in full
 
 
+class Cone(list):
+    """The masks [M0 .. M_{L-1}] of a readout's cone (SconeState.cone).  units: where the forward took its units from lists
+    (ops.CONE_UNIT_LIST), units[k] = the UnitList of M_k (None: M_k has none); None otherwise.  They belong to this forward's record
+    as the masks do: fresh buffers, shared with no other forward on the plan."""
+    units = None
+
+
 class BunchState(NamedTuple):
     """BunchPlan.forward -> backward."""
     states: list        # per layer boundary the three level tensors (None: not computed)
@@ -1113,17 +1181,22 @@ class SconePlan(Plan):
         hs, y0 = [x], None
         S, E, ns, _ = x.shape
         L = int(n_layers)
-        keep = self._keep_last(x, weights, activity, last_dev)
-        cone = self._readout_cone(x, weights, activity, keep)
+        # (the masks of a cone that runs on unit lists are built WITH their lists, M0's among them: asked for where the cone's own
+        # conditions hold, ahead of the mask they also need)
+        listed = CONE_UNIT_LIST and self._cone_shape(x, weights, activity)
+        keep = self._keep_last(x, weights, activity, last_dev, units=listed)
+        keep, units0, counters = keep if listed and keep is not None else (keep, None, None)
+        cone = self._readout_cone(x, weights, activity, keep, units0, counters)
         if cone is not None:                            # every layer on the readout's cone (READOUT_CONE); not served: the stack below, in full
-            y0, h = self.conv.shifted_input(x, keep=cone[L - 1]), None
+            ul = cone.units if cone.units is not None else [None] * L
+            y0, h = self.conv.shifted_input(x, keep=cone[L - 1], units=ul[L - 1]), None
             if y0 is not None:
-                h = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=cone[L - 2])
+                h = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=cone[L - 2], units=ul[L - 2])
             hs += [None, h]
             for i in range(2, L):
                 if hs[-1] is not None:
                     hs.append(self.conv.forward([hs[-1]], weights[3 * i:3 * i + 3], 32, self.act, out=out_last if i == L - 1 else None,
-                                                keep=cone[L - 1 - i]))
+                                                keep=cone[L - 1 - i], units=ul[L - 1 - i]))
             if hs[-1] is not None:
                 return hs, y0, cone
             hs, y0 = [x], None
@@ -1172,11 +1245,12 @@ class SconePlan(Plan):
     # on the graph-replayed steps of small complexes (the bound of SMALL_DZ_BYTES; tests set 0 to take the path on small complexes)
     KEEP_LAST_MIN_BYTES = 8 << 20
 
-    def _keep_last(self, x, weights, activity, last_dev):
+    def _keep_last(self, x, weights, activity, last_dev, units=False):
         """The keep mask the last layer of this stack runs with, or None: plain scone plan on its blocked operator, dense launches, a
         last layer of 32 -> 32 or 16 -> 16 channels (so at least two layers), an H_L above KEEP_LAST_MIN_BYTES, and the plan's
         node -> blocks table (field_tables_dev: none for a probed closure; it is built on the host at first use, so not under a
-        graph capture).  KEEP_LAST is the tests' and A/B's switch."""
+        graph capture).  KEEP_LAST is the tests' and A/B's switch.  units: the mask comes with its unit list, (mask, UnitList, counters)
+        of ConvOp.keep_mask_units."""
         if not KEEP_LAST or last_dev is None or activity is not None or not self.fused_conv or len(weights) < 7:
             return None
         S, E, ns, _ = x.shape
@@ -1188,29 +1262,48 @@ class SconePlan(Plan):
         if self._field is None and torch.cuda.is_current_stream_capturing():
             return None
         tabs = self.field_tables_dev()
-        return self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs) if tabs is not None else None
+        if tabs is None:
+            return None
+        return self.conv.keep_mask_units(last_dev, ns, self.n_nodes, tabs) if units else self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs)
 
     # the bound of KEEP_LAST_MIN_BYTES and SMALL_DZ_BYTES under a name of its own: a test that sets those two to 0 to take their paths on a
     # small complex stays on those paths; the tests of this one set all three
     READOUT_CONE_MIN_BYTES = 8 << 20
 
-    def _readout_cone(self, x, weights, activity, keep):
+    def _cone_shape(self, x, weights, activity):
+        """The conditions of _readout_cone that do not need the keep mask."""
+        L = (len(weights) - 1) // 3
+        if not READOUT_CONE or not TOP_DZ_MASK or L < 3 or self.conv_T is not self.conv:
+            return False
+        S, E, ns, _ = x.shape
+        nbytes = S * E * ns * 32 * 4
+        return not (S > 64 or nbytes <= self.SMALL_DZ_BYTES or nbytes <= self.READOUT_CONE_MIN_BYTES
+                    or not self._recompute_first(x, weights, activity))
+
+    def _readout_cone(self, x, weights, activity, keep, units0=None, counters=None):
         """The masks [M0 .. M_{L-1}] of the readout's cone (M0 = keep, M_k = one hop out from M_{k-1}), or None: exactly where _keep_last
         and _top_dz_mask are both served -- their switches on, `keep` built (plain scone plan on its blocked operator, dense launches,
         the sizes and the tables of _keep_last), symmetric shifts, the gradient buffers above SMALL_DZ_BYTES -- on a stack of three or
         more layers that runs without a stored H1 (1-channel input, hidden 32 throughout: _recompute_first), and at most 64 slabs,
-        where every masked launch is served whatever its grid.  READOUT_CONE is the tests' and A/B's switch."""
+        where every masked launch is served whatever its grid.  READOUT_CONE is the tests' and A/B's switch.
+        units0, counters (ops.CONE_UNIT_LIST): M0's UnitList and the zeroed counter words of ConvOp.keep_mask_units -- every hop then
+        writes its mask's list too (Cone.units; a stack deeper than the counters reach runs its lowest masks without one)."""
         L = (len(weights) - 1) // 3
-        if not READOUT_CONE or not TOP_DZ_MASK or keep is None or L < 3 or self.conv_T is not self.conv:
-            return None
-        S, E, ns, _ = x.shape
-        nbytes = S * E * ns * 32 * 4
-        if S > 64 or nbytes <= self.SMALL_DZ_BYTES or nbytes <= self.READOUT_CONE_MIN_BYTES or not self._recompute_first(x, weights, activity):
+        if keep is None or not self._cone_shape(x, weights, activity):
             return None
         tabs = self.field_tables_dev()
-        cone = [keep]
-        for _ in range(L - 1):
-            cone.append(self.conv.mask_hop(cone[-1], tabs))
+        cone = Cone([keep])
+        if units0 is not None:
+            cone.units = [units0]
+        for k in range(1, L):
+            if cone.units is not None and k < counters.numel():
+                m, u = self.conv.mask_hop_units(cone[-1], tabs, counters[k:k + 1])
+                cone.units.append(u)
+            else:
+                m = self.conv.mask_hop(cone[-1], tabs)
+                if cone.units is not None:
+                    cone.units.append(None)
+            cone.append(m)
         return cone
 
     def _recompute_first(self, x, weights, activity):
