@@ -395,6 +395,11 @@ int scn_conv_backward_fused_first_from_y_visit(scn_conv_t conv_t, int32_t n_slab
                                                const uint32_t* visit, void* stream);
 int scn_conv_shifted_input_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
                                 void* stream);
+/* The two visiting backwards run their units as a pipeline: a unit's prologue fetches the next unit's source rows and its last visit
+ * stages the next unit's first slab (csrc/scn_blk_bwd.inc).  scn_conv_visit_prefetch sets that for the launches that follow, for the
+ * whole process (on != 0: on, the default; 0: every unit starts with its full prologue; negative: no change), and returns the setting
+ * before the call.  Outputs are bit for bit the same either way: a switch for tests and A/B runs. */
+int scn_conv_visit_prefetch(int32_t on);
 int scn_clear_mask(scn_conv_t conv, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream);
 
 /* Unit lists.  A masked launch hands every workgroup a FIXED share of the plan's blocks, and the launch ends with its busiest

@@ -146,6 +146,7 @@ SIGNATURES = {
                                                           c_void_p]),
     "scn_conv_shifted_input_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                          c_void_p]),
+    "scn_conv_visit_prefetch": (ctypes.c_int, [c_i32]),
     "scn_window_scan_probe": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,

@@ -130,6 +130,30 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // (plain form) is written on the visited items only; aux / y outside V and dz of items no visited item stages are not read.  The
 // mask's words ride where the form has a free pointer: DZ0 in the plain form, aux in the FIRST + FROMY form.  A NaN / Inf weight
 // does NOT widen the window (DZMASK does): V is visited regardless, see scn_conv_backward_visit in include/scone_hip.h.
+// UNIT PIPELINE of the VISIT forms.  On a cone a unit has 1.3 visits on average, so the slab pipeline inside a unit (visit it + 1 is
+// staged from the side slots of visit it's contraction) rarely has a second visit to work on, and every unit started with four
+// dependent trips to memory and nothing beside them: header scalars, source rows + ELL tile, the wave's tile widths, the first slab's
+// LDS-DMA (profiles/visit_prefetch_ab.txt: two thirds of the busiest workgroup's time).  The workgroup's scan table already names
+// its next unit, so:
+//   * the staging parity runs over the workgroup's WHOLE visit sequence (vpar), not per unit: a unit's last visit gathers from one
+//     64 KB buffer and the other is free;
+//   * a unit's prologue also fetches the NEXT unit's source rows, in the round trip of its own metadata, into a second 512-byte row
+//     buffer behind the scan table (load_block_c32_ahead); the prologue's __syncthreads() publishes them;
+//   * the unit's LAST visit stages the next unit's first slab from them through the very side slots (and the early-out's branch)
+//     that stage "the next visit" otherwise: rows, chunk count and slab are the next unit's;
+//   * the next unit's prologue then finds its rows in place and its slab on the way: it loads the ELL tile only, and the tile
+//     widths ride with the header scalars.
+// The ELL tile itself cannot be written ahead (one tile fits the LDS, and the current unit's waves gather through it up to the
+// barrier at the next unit's top).  No arithmetic changes: the same tiles in the same order into the same accumulators.  A unit
+// without a successor in the table (the last entry of a scan, the workgroup's last unit) stages nothing ahead, and the unit behind
+// it runs the full prologue.  SCN_VISIT_PREFETCH=0 compiles the unit loop without any of this; a launch without
+// VISIT_FLAG_PREFETCH in wl.n_work (dense launches do not use the field otherwise) takes that loop at run time.
+#ifndef SCN_VISIT_PREFETCH
+#define SCN_VISIT_PREFETCH 1
+#endif
+constexpr int VISIT_FLAG_PREFETCH = 1;
+constexpr int VISIT_ROWS_BYTES = BK_SRC * 4;                  // the second source-row buffer: dynamic LDS of the VISIT launches, behind the scan table
+static_assert(WSCAN_LDS_BYTES % 16 == 0, "the second source-row buffer starts 16-byte aligned");
 template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false, bool DZMASK = false,
           bool VISIT = false>
 __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, const float* __restrict__ DZ,
@@ -158,6 +182,8 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = lane & 31, h = lane >> 5, n = p & 3, rt = wave * 8 + (p >> 2);
     STAMP_DECL;
+    STAMP_UNIT_DECL;
+    STAMP_MARK(0);
     // dgrad B fragments: (g, t, lane) holds W_g[ca = lane&31][c = 16*(lane>>5) + 8t + j] * sW, j = 0..7 (one scale for the three
     // matrices: their products share the dgrad accumulator)
     char* isel = wfrag + B32_WFRAG_BYTES;
@@ -216,20 +242,46 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     for (int q = 0; q < 4; ++q) cqs[q] = (uint32_t)((n * 8 + h * 4 + q) ^ (n >> 1)) << 4;
     const size_t slab_bytes = (size_t)n_cols * (PAIR ? 256 : PIECE);
     const bool second = PAIR && (((lane >> 2) ^ wave) & 1);       // this lane's LDS-DMA chunks come from slab B (see dma_k)
+    // UNIT PIPELINE (the VISIT forms; see the header).  All of it is workgroup-uniform and lives across units and table scans.
+    constexpr bool PIPE = VISIT && SCN_VISIT_PREFETCH != 0;
+    const bool pipe_on = PIPE && !listed && (wl.n_work & VISIT_FLAG_PREFETCH) != 0;   // (dense launches: n_work carries the launch's flags)
+    int32_t* const srcrows_b = (int32_t*)(smem + smem_bytes_c32(B32_EXTRA_BYTES) + WSCAN_LDS_BYTES);   // the second source-row buffer, behind the scan's table
+    const int sr_b = (int)(srcrows_b - sm.srcrows);             // its distance from the first, in rows
+    int vpar = 0;                                               // staging buffer of the unit's first visit: the workgroup's visits so far, mod 2
+    int sr_cur = 0;                                             // 0 / sr_b: which buffer holds the current unit's source rows
+    int pf_total = -1;                                          // >= 0: the previous unit staged this one's first slab (into buffer vpar) from
+                                                                // this many chunks, and left its rows in buffer sr_cur
     if (listed || slab0 < slab1) {
+    STAMP_MARK(1);
+    STAMP_START();
     // VISIT: the units are the blocks of this workgroup that have a visit, with their windows cut to its slab range, from the batched
     // scan ahead of the loop (scn_window_scan.inc): a block without a visit never enters the loop -- no barrier, no metadata.  The
     // table is the same in all eight waves.  (dense launches only: k0 = slab0)
     SCN_UNIT_BEGIN_MASKED(VISIT)
         uint64_t vw = VISIT ? win_ : 0;                           // the cursor: its lowest set bit is the visit handled next
+        STAMP_UADD(4);
+        STAMP_UCOUNT(0);
+        // PIPE: the table's next entry is the next unit (none: the last entry of a scan or of the workgroup -- the unit behind it
+        // takes the prologue below in full); `staged` = the previous unit brought this one's rows and first slab
+        const bool has_next = PIPE && pipe_on && u_ + 1 < u_end_;
+        const int nb = has_next ? walk_.block(u_ + 1) : b;
+        const int n_first = has_next ? keep_first(walk_.window(u_ + 1)) : 0;   // the next unit's first visit: slab k0 + n_first
+        const bool staged = PIPE && pf_total >= 0;
+        const int sr_next = PIPE ? sr_b - sr_cur : 0;
+        int n_next = 0, tw_p = 0, twu_p = 0;
         wait_all_and_barrier();
-        const BlockMeta m = load_block_c32<BK_THREADS>(P, b, sm);
+        STAMP_UADD(0);
+        const BlockMeta m = PIPE && pipe_on ? load_block_c32_ahead<BK_THREADS>(P, b, sm, sm.srcrows + sr_cur, staged, has_next, nb, sm.srcrows + sr_next,
+                                                                               n_next, wave, tw_p, twu_p)
+                                            : load_block_c32<BK_THREADS>(P, b, sm);
         // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
         const uint64_t dzm = DZMASK ? (keep_window(KeepMask{(const uint32_t*)DZ0, (n_slabs + 31) >> 5}, b, k0) | (w_bad ? ~0ull : 0ull)) : ~0ull;
         __syncthreads();
-        const int tw = P.tile_w[b * BK_WAVES + wave];
-        const int twu = EXT0 ? 0 : P.tile_wu[b * BK_WAVES + wave];
+        STAMP_UADD(1);
+        const int tw = PIPE && pipe_on ? tw_p : P.tile_w[b * BK_WAVES + wave];
+        const int twu = EXT0 ? 0 : (PIPE && pipe_on ? twu_p : P.tile_wu[b * BK_WAVES + wave]);
         const int rtc = rt < m.rows ? rt : m.rows - 1;
+        const int total_next = n_next * CPP;
         // LDS-DMA instruction k of this wave moves chunks c = (k * 8 + wave) * 64 + lane: slot = 2 * (k * 8 + wave) + (lane >> 5),
         // position lane & 31.  The swizzled source chunk only depends on slot & 3 = ((wave & 1) << 1) | (lane >> 5), i.e. it is ONE
         // lane constant for every k, and the slot's source row comes from LDS at a lane constant + 64 * k: no per-k offsets in
@@ -238,10 +290,11 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         const int dq = swz32(((wave & 1) << 1) | (lane >> 5), lane & 31);
         const uint32_t dchunk = PAIR ? (uint32_t)(((dq >> 3) * 4 + (dq & 3)) * 16) : (uint32_t)(dq * 16);
         const int32_t* my_src = sm.srcrows + 2 * wave + (lane >> 5);          // + 16 * k
-        auto dma_k = [&](int k, const char* Xs, int bufi) {
+        // (PIPE: sr = the source-row buffer to stage from, sr_cur or sr_next, and tot = the chunks of THAT unit's block)
+        auto dma_k = [&](int k, const char* Xs, int bufi, int sr = 0, int tot = -1) {
             const int base = (k * BK_WAVES + wave) * 64;
-            if (base + lane < total) {
-                const uint32_t off = (uint32_t)my_src[16 * k] * (PAIR ? 256u : (uint32_t)PIECE) + dchunk;
+            if (base + lane < (PIPE ? tot : total)) {
+                const uint32_t off = (uint32_t)my_src[16 * k + (PIPE ? sr : 0)] * (PAIR ? 256u : (uint32_t)PIECE) + dchunk;
                 const uint32_t dst = lds0 + (uint32_t)(bufi * (BK_SRC * 512) + base * 16);
                 if (PAIR) lds_dma16_v(Xs + off, dst);               // (the two lane groups stage from different slabs)
                 else lds_dma16(Xs, off, dst);
@@ -260,10 +313,10 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             return (const char*)DZ + (size_t)slab_of(vis, second ? 1 : 0) * slab_bytes;
         };
         auto src_of = [&](int slab) { return (const char*)DZ + (size_t)slab * slab_bytes; };   // VISIT: by slab, not by visit index
-        if (!DZMASK || (dzm & 1)) {
+        if (PIPE ? !staged : (!DZMASK || (dzm & 1))) {          // (PIPE, staged: on its way since the previous unit's last visit)
             const char* Xs = VISIT ? src_of(k0 + keep_first(vw)) : src_base(0);
 #pragma unroll
-            for (int i = 0; i < NDMA; ++i) dma_k(i, Xs, 0);
+            for (int i = 0; i < NDMA; ++i) dma_k(i, Xs, PIPE ? vpar : 0, sr_cur, total);
         }
         const int rows_left = m.rows - wave * 8;
         f32x4 G[3][4];
@@ -317,13 +370,14 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             }
             const int slab = VISIT ? v_slab : slab_of(it, PAIR ? p >> 4 : 0);   // PAIR: lanes p >= 16 hold slab B's channels
             const bool lane_live = !PAIR || p < 16 || 2 * it + 1 < n_it;
-            const uint32_t bufbit = (uint32_t)((it & 1) << 16);
+            const uint32_t bufbit = (uint32_t)(((PIPE ? it + vpar : it) & 1) << 16);
             const uint32_t cbs[4] = {cqs[0] | bufbit, cqs[1] | bufbit, cqs[2] | bufbit, cqs[3] | bufbit};
             // DZMASK (workgroup-uniform, scalar): the next visit's slab is to be staged (it + 1 < n_vis <= 64 where it is used)
             const bool dz_next = !DZMASK || ((dzm >> ((it + 1) & 63)) & 1);
-            STAMP_START();
+            STAMP_VISIT_TOP(VISIT && it == 0);
+            STAMP_UCOUNT(1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            STAMP_ADD(0);
+            STAMP_VISIT_WAITED(VISIT && it == 0);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             STAMP_ADD(1);
@@ -409,10 +463,11 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 // neighbourhood -- nearly every tile of a real batch leaves here.  Its share of the staging is still issued.
                 if (!w_bad && mgb == 0) {
                     const int vdma0 = it + 1;
-                    if (vdma0 < n_vis && dz_next) {
-                        const char* Xn0 = VISIT ? src_of(v_next) : src_base(vdma0);
+                    const bool nx0 = PIPE && has_next && vdma0 == n_vis;   // (PIPE: the next unit's first slab from a unit's last visit, see below)
+                    if (nx0 || (vdma0 < n_vis && dz_next)) {
+                        const char* Xn0 = VISIT ? src_of(nx0 ? k0 + n_first : v_next) : src_base(vdma0);
 #pragma unroll
-                        for (int i = 0; i < NDMA; ++i) dma_k(i, Xn0, vdma0 & 1);
+                        for (int i = 0; i < NDMA; ++i) dma_k(i, Xn0, (PIPE ? vdma0 + vpar : vdma0) & 1, nx0 ? sr_next : sr_cur, nx0 ? total_next : total);
                     }
                     if (!FIRST && dp) {
 #pragma unroll
@@ -483,12 +538,17 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                 }
             }
             // ---------------- CONTRACT
+            STAMP_UCOUNT(2);
             const int vdma = it + 1;                                     // the visit whose slab this contraction stages
-            const bool more = vdma < n_vis && dz_next;                  // (DZMASK: a slab without a source in the mask is not staged)
-            const char* Xn = VISIT ? src_of(v_next) : src_base(more ? vdma : it);
-            const int nbuf = vdma & 1;
+            // PIPE: a unit's LAST visit stages the first slab of the NEXT unit instead -- its rows (buffer sr_next, published by this
+            // unit's __syncthreads()), its chunk count, its slab -- into the buffer this visit does not gather from (the visit counter
+            // runs on across units: vpar)
+            const bool nx = PIPE && has_next && vdma == n_vis;
+            const bool more = nx || (vdma < n_vis && dz_next);          // (DZMASK: a slab without a source in the mask is not staged)
+            const char* Xn = VISIT ? src_of(nx ? k0 + n_first : v_next) : src_base(more ? vdma : it);
+            const int nbuf = (PIPE ? vdma + vpar : vdma) & 1;
             auto side = [&](int k) {                                     // (all eight right after the barrier instead: +2 %)
-                if (k < NDMA && more) dma_k(k, Xn, nbuf);
+                if (k < NDMA && more) dma_k(k, Xn, nbuf, nx ? sr_next : sr_cur, nx ? total_next : total);
             };
             // Per segment g: [transpose + dgrad] over its two k-steps, then straight into dW_g.  The transpose keeps the two
             // parts of the split in TWO accumulators (T_hi, T_lo = hi / lo of G_g sG, one channel per lane): each holds exactly
@@ -572,10 +632,16 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             }
             STAMP_ADD(4);
         }
+        if (PIPE && pipe_on) {                                   // hand-over: the visit counter runs on; what the last visit staged
+            vpar = (vpar + n_vis) & 1;
+            sr_cur = has_next ? sr_next : sr_cur;
+            pf_total = has_next ? total_next : -1;
+        }
     }
     SCN_UNIT_END_MASKED(VISIT);
     }
-    STAMP_FLUSH();
+    STAMP_MARK(2);
+    if (!VISIT) { STAMP_FLUSH(); }                             // (the VISIT forms flush per workgroup at the exit: the global sums' atomics would be most of a masked launch)
     wait_all_and_barrier();
     float* red = (float*)sm.buf(0);
     // out of the wave's running units: x 2^-e_run, in two exact steps where one factor would leave the normal range (a wave without
@@ -623,6 +689,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             partial_first[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 96 + threadIdx.x] = s;
         }
     }
+    if (VISIT) { STAMP_FLUSH_WG(); }
 }
 
 // The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so the trailing partial_first and fw are always passed; the

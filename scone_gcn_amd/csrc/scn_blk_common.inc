@@ -119,6 +119,43 @@ __device__ __forceinline__ BlockMeta load_block_c32(const PlanDev& P, int b, con
     return m;
 }
 
+// load_block_c32 of the visiting backwards' unit pipeline (scn_blk_bwd.inc): one round trip for the header scalars and one for the
+// metadata, as there, but the second also carries the source rows of the NEXT unit's block nb (ahead: there is one) into rows_next,
+// so that the current unit's last visit can stage the next unit's first slab; the block's own rows go to rows_cur unless they are
+// there already (have_rows: the previous unit brought them).  The wave's tile widths ride with the header instead of waiting for
+// it behind the __syncthreads() (as compiled by hipcc 7.2 the two byte loads sink back behind the barrier, and the header's loads
+// split into more waited batches than load_block_c32's: profiles/visit_prefetch_ab.txt, section 3 -- the next thing to mend).
+// n_next = the next block's source count (ahead only).
+template <int NT>
+__device__ __forceinline__ BlockMeta load_block_c32_ahead(const PlanDev& P, int b, const SmemC32& sm, int32_t* rows_cur, bool have_rows, bool ahead,
+                                                          int nb, int32_t* rows_next, int& n_next, int wave, int& tw, int& twu) {
+    static_assert(BK_SRC <= NT, "a block's source rows: one per thread");
+    BlockMeta m;
+    m.row0 = P.blk_row0[b];
+    m.rows = P.blk_rows[b];
+    const int sp0 = P.src_ptr[b];
+    m.nsrc = P.src_ptr[b + 1] - sp0;
+    m.w = P.width[b];
+    const int ep = P.ell_ptr[b];
+    const int np0 = P.src_ptr[nb];                                // (nb = b without a next unit)
+    n_next = P.src_ptr[nb + 1] - np0;
+    tw = P.tile_w[b * BK_WAVES + wave];
+    twu = P.tile_wu[b * BK_WAVES + wave];
+    const int t = threadIdx.x;
+    const bool l0 = !have_rows && t < m.nsrc, l1 = ahead && t < n_next;
+    int32_t r0 = 0, r1 = 0;
+    if (l0) r0 = P.src_rows[sp0 + t];
+    if (l1) r1 = P.src_rows[np0 + t];
+    for (int i = t; i < m.w * m.rows; i += NT) {
+        sm.enc[i] = P.ell_enc[ep + i];
+        sm.v[i] = P.ell_v[ep + i];
+    }
+    if (t < BK_R) sm.self[t] = P.self_slot[(size_t)b * BK_R + t];
+    if (l0) rows_cur[t] = r0;
+    if (l1) rows_next[t] = r1;
+    return m;
+}
+
 // Gather of one lane's NQ 16-byte chunks of row `row` from the staged 512-byte pieces: identity term gs, and the ELL row
 // (entry pairs) accumulated into gl (val0 operator) and gu (val1 operator).
 //  * cb[q] = (this lane's swizzled chunk index << 4) | (buffer index << 16); the LDS address of a chunk is cb[q] ^ enc with

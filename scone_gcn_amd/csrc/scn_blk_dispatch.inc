@@ -88,6 +88,16 @@ constexpr UnitList NO_UNITS{nullptr, nullptr};
 static_assert(W16_EXTRA_BYTES + W16_FIRSTW_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16) &&
               B32_EXTRA_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
               "the scan's table fits behind the kernels' own LDS");
+// The VISIT backwards take VISIT_ROWS_BYTES more behind the table (the unit pipeline's second source-row buffer, scn_blk_bwd.inc), and
+// their launch flags in the work list's n_work, which a dense launch does not use otherwise.  g_visit_prefetch: scn_conv_visit_prefetch.
+constexpr size_t VISIT_LDS_BYTES = WSCAN_LDS_BYTES + VISIT_ROWS_BYTES;
+static_assert(B32_EXTRA_BYTES + VISIT_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
+              "the scan's table and the second source-row buffer fit behind the backward's own LDS");
+static int g_visit_prefetch = 1;
+static WorkList visit_launch_flags(WorkList wl) {
+    wl.n_work = g_visit_prefetch ? VISIT_FLAG_PREFETCH : 0;
+    return wl;
+}
 
 // The keep mask of a launch (scn_conv_forward_keep / _from_y_keep; the source mask of scn_conv_backward_dzmask has its geometry and
 // its window limit): words per block from the slab count.  A workgroup holds the bits
@@ -251,8 +261,9 @@ int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz,
         constexpr int ACT = decltype(A)::value;
         if (mask)                                                // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
             return launch_checked(dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS),
-                                  lds + (dzmask ? 0 : WSCAN_LDS_BYTES), st, L.P, dz[0],
-                                  (const float*)mask, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, wl, nullptr, NO_FIRSTW);
+                                  lds + (dzmask ? 0 : VISIT_LDS_BYTES), st, L.P, dz[0],
+                                  (const float*)mask, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, dzmask ? wl : visit_launch_flags(wl),
+                                  nullptr, NO_FIRSTW);
         const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
                               n_slabs, wl, nullptr, NO_FIRSTW);
@@ -303,8 +314,8 @@ int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const fl
     int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         if (visit)                                               // (the mask's words ride in aux, which this form does not read)
-            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, dz, y, W[0], W[1], W[2],
-                                  (const float*)visit, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw);
+            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + VISIT_LDS_BYTES, st, L.P, dz, y, W[0], W[1], W[2],
+                                  (const float*)visit, nullptr, partial, L.nr, L.nc, n_slabs, visit_launch_flags(wl), partial_first, fw);
         const auto k = W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2], W_first ? nullptr : aux, nullptr, partial,
                               L.nr, L.nc, n_slabs, wl, partial_first, fw);

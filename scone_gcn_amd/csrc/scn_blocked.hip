@@ -50,11 +50,37 @@ __device__ unsigned long long g_stamps_w[16][10];
     atomicMax(&g_stamps[6], s_); atomicAdd(&g_stamps[7], 1ull); atomicAdd(&g_stamps_w[w_][6], sq_); atomicAdd(&g_stamps_w[w_][7], nint_); \
     atomicAdd(&g_stamps_w[w_][8], (unsigned long long)((__builtin_amdgcn_s_getreg((4 << 0) | (4 << 6) | ((2 - 1) << 11))) & 3)); \
     atomicAdd(&g_stamps_w[w_][9], 1ull); } } while (0)
+// The unit prologue of the VISIT forms (bwd_c32_bf16_kernel), kept apart from the visit's own segments and PER WORKGROUP, because a
+// masked launch ends with its busiest workgroup.  Row [workgroup][wave] (the first STAMP_WG_CAP workgroups of the last stamped launch):
+//   [0..4] the visit's segments as above, without the first visit's wait of a unit       [5] drain + barrier at the unit's top
+//   [6] header and metadata loads up to the __syncthreads()   [7] tile_w / tile_wu and the issue of the first slab's LDS-DMA
+//   [8] the wait for that DMA (the first visit's s_waitcnt)    [9] the window scans        [10] units  [11] visits  [12] visits that
+//   were contracted (no zero-tile early-out)   [13] kernel entry -> first scan   [14] entry -> behind the unit loop   [15] entry -> exit
+constexpr int STAMP_WG_CAP = 1024, STAMP_WG_WORDS = 16;
+__device__ unsigned long long g_stamps_wg[STAMP_WG_CAP][8][STAMP_WG_WORDS];
+#define STAMP_UNIT_DECL unsigned long long uacc_[5] = {0, 0, 0, 0, 0}, tk_[4] = {0, 0, 0, 0}; unsigned ucnt_[3] = {0, 0, 0}
+#define STAMP_UADD(i) do { STAMP(t1_); uacc_[i] += t1_ - t0_; t0_ = t1_; } while (0)
+#define STAMP_UCOUNT(i) (++ucnt_[i])
+#define STAMP_MARK(k) STAMP(tk_[k])
+// the top of a visit: the first visit of a unit closes the prologue's issue segment and books its wait to the prologue
+#define STAMP_VISIT_TOP(first) do { if (first) STAMP_UADD(2); else STAMP_START(); } while (0)
+#define STAMP_VISIT_WAITED(first) do { if (first) STAMP_UADD(3); else STAMP_ADD(0); } while (0)
+#define STAMP_FLUSH_WG() do { const int g_ = blockIdx.y * gridDim.x + blockIdx.x; STAMP_MARK(3); \
+    if ((threadIdx.x & 63) == 0 && g_ < STAMP_WG_CAP) { unsigned long long* o_ = g_stamps_wg[g_][(threadIdx.x >> 6) & 7]; \
+    for (int i_ = 0; i_ < 5; ++i_) { o_[i_] = acc_[i_]; o_[5 + i_] = uacc_[i_]; } \
+    for (int i_ = 0; i_ < 3; ++i_) { o_[10 + i_] = ucnt_[i_]; o_[13 + i_] = tk_[1 + i_] - tk_[0]; } } } while (0)
 #else
 #define STAMP_DECL
 #define STAMP_ADD(i)
 #define STAMP_START()
 #define STAMP_FLUSH()
+#define STAMP_UNIT_DECL
+#define STAMP_UADD(i)
+#define STAMP_UCOUNT(i)
+#define STAMP_MARK(k)
+#define STAMP_VISIT_TOP(first)
+#define STAMP_VISIT_WAITED(first)
+#define STAMP_FLUSH_WG()
 #endif
 
 #include "scn_blk_layout.inc"
@@ -69,6 +95,14 @@ __device__ unsigned long long g_stamps_w[16][10];
 #include "scn_terms.inc"
 
 }  // namespace scn
+
+// The unit pipeline of the visiting backwards (scn_blk_bwd.inc) for the launches that follow, process-wide: on != 0 / 0 sets it, a
+// negative value only asks.  Returns the setting before the call.  Every output bit is the same either way.
+extern "C" int scn_conv_visit_prefetch(int32_t on) {
+    const int was = scn::g_visit_prefetch;
+    if (on >= 0) scn::g_visit_prefetch = on != 0;
+    return was;
+}
 
 
 // Host-only layout helper (no reference counterpart: the reference's dense operators have no storage order).
@@ -151,6 +185,16 @@ extern "C" int scn_debug_stamps(unsigned long long* out8, int reset) {
 extern "C" int scn_debug_stamps_waves(unsigned long long* out160, int reset) {
     if (hipMemcpyFromSymbol(out160, HIP_SYMBOL(scn::g_stamps_w), 1280) != hipSuccess) return -3;
     if (reset) { unsigned long long z[160] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(scn::g_stamps_w), z, 1280) != hipSuccess) return -3; }
+    return 0;
+}
+// rows [workgroup][wave][STAMP_WG_WORDS] of the last stamped VISIT launch (see g_stamps_wg); out: STAMP_WG_CAP * 8 * STAMP_WG_WORDS words
+extern "C" int scn_debug_stamps_wg(unsigned long long* out, int reset) {
+    const size_t bytes = sizeof(unsigned long long) * scn::STAMP_WG_CAP * 8 * scn::STAMP_WG_WORDS;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(scn::g_stamps_wg), bytes) != hipSuccess) return -3;
+    if (reset) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(scn::g_stamps_wg)) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) return -3;
+    }
     return 0;
 }
 #endif

@@ -114,6 +114,11 @@ READOUT_CONE = True
 # mode, csrc/scn_window_scan.inc).  Every output bit is the static walk's.  The visiting backwards keep their shares: dW is summed in
 # visit order.  On wherever READOUT_CONE runs; False: the static walk everywhere.
 CONE_UNIT_LIST = True
+# On a cone a unit of the visiting backwards has 1.3 visits on average, so nearly every visit paid a unit's whole prologue (four
+# dependent trips to memory) with nothing beside it.  With the switch on, a unit's prologue also fetches the next unit's source rows and
+# its last visit stages the next unit's first slab (csrc/scn_blk_bwd.inc, scn_conv_visit_prefetch).  Every output bit is the same.
+# On wherever READOUT_CONE runs; False: every unit starts with its full prologue.
+VISIT_PREFETCH = True
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
@@ -196,6 +201,12 @@ def _served(status, name):
         return False
     check(status, name)
     return True
+
+
+def _visit_prefetch(lib):
+    """Hands VISIT_PREFETCH to the library ahead of a visiting backward (a build from before the switch has no unit pipeline)."""
+    if hasattr(lib, "scn_conv_visit_prefetch"):
+        lib.scn_conv_visit_prefetch(1 if VISIT_PREFETCH else 0)
 
 
 class WorkList:
@@ -519,6 +530,7 @@ class ConvOp:
             return dx if need_dx else None
         if visit is not None:                         # (the key of the plain backward; no byte model: the visited items' count is on the device)
             with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"), None):
+                _visit_prefetch(lib)
                 st = lib.scn_conv_backward_visit(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
                                                  _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _dev(visit, torch.int32), _stream())
             if not _served(st, "scn_conv_backward_visit"):
@@ -641,6 +653,7 @@ class ConvOp:
             if aux is not None or wl is not None:
                 return False
             with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None):
+                _visit_prefetch(lib)
                 st = lib.scn_conv_backward_fused_first_from_y_visit(self.handle, S, ns, _dev(dz), _ptrs(Ws), _ptrs(Ws_first), c, ACT[act],
                                                                     _dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws,
                                                                     _dev(visit, torch.int32), _stream())
