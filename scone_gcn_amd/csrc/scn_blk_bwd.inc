@@ -54,6 +54,9 @@ __device__ __forceinline__ int pow2_scale_exp(uint32_t mbits) {
 constexpr int B32_EXTRA_BYTES = B32_WFRAG_BYTES + 2048 + 64;   // weight fragments, selection fragments, one word per wave (weights_abs_max)
 static_assert(B32_EXTRA_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16), "weight + selection fragments fit behind the staging buffers");
 
+// FORM: the kernel's form, an OR of the BWD_* bits below; the kernel's first lines name them and assert which combinations exist.
+// What DZ0 carries depends on the form, and has ONE name each (top of the kernel): dz_own (EXT0), dx_partial (ACCUM), y_rec (FIRST);
+// it is null in every other form.  A mask (DZMASK's source mask, VISIT's visit mask) comes typed, in `km`, and the launch's flags in `flags`.
 // EXT0 (see fwd_c32_w16_kernel): segment 0 of G is the upstream gradient itself (DZ0, own rows from HBM), the staged tensor
 // DZ is S^T dz: segment 1 its own row, segment 2 its gathered shift (S^T)^2 dz.  Composes with PAIR (Ebli at hidden 16).
 // PAIR: C = 16 on TWO slabs per visit -- the staged 512-byte piece is a point's 32 VIRTUAL channels (slab A's 16, slab B's 16:
@@ -108,13 +111,13 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // scn_conv_forward_first).  The input gradient dx = dL/d(pre-activation of layer 1) is then needed for one thing only -- the
 // first layer's weight gradient dW_first[g][c] = sum_p y[p][g] dx[p][c] -- so it is contracted with y right here, in registers
 // (y is broadcast across the lanes of a half wave with ds_swizzle: 48 cross-lane reads + 48 FMAs per tile), and never written:
-// no 4*E*C-byte dx tensor, no separate streaming kernel over it.  DZ0 carries y in this variant.
+// no 4*E*C-byte dx tensor, no separate streaming kernel over it.  DZ0 carries y in this variant (y_rec).
 // FROMY (FIRST, plain C = 32): aux = H1 is not read at all -- `fw` carries the first layer's three weight rows and the tile's sixteen
 // aux values per lane are rebuilt from the y records the lane group already holds for dW_first (the same row_newbcast hand-over,
 // first_layer_value: the bits fwd_c1_kernel would have stored), after the zero-tile early-out.
 // DZMASK (plain C = 32, dense launches): the layer is the LAST one and DZ is the readout's gradient, which lives on the rows the
-// readout reads -- DZ0 carries a bit per (plan block, slab) (a KeepMask's words: scn_keep_mask, one hop out: scn_mask_hop; the kernel's
-// parameter list stays the other forms') that is set wherever one of the block's SOURCE blocks holds such a row.  A visit whose bit
+// readout reads -- `km` carries a bit per (plan block, slab) (scn_keep_mask, one hop out: scn_mask_hop) that is set wherever one of
+// the block's SOURCE blocks holds such a row.  A visit whose bit
 // is clear would stage and gather zeros only to find the zero-tile early-out: it stages nothing, waits for nothing, requests no aux,
 // gathers nothing and writes the early-out's zero tile.  Every (block, slab) item is still visited and dx is still written in full:
 // this is not the zero-skipping mode.  The decision depends on the trajectories' last nodes, never on a value.  The block's bits
@@ -127,8 +130,8 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // loop runs over the window's set bits with its cursor in SGPRs (scn_keep_bits.h): no memory operation for the walk inside the slab loop.  A visit that runs is staged, gathered, contracted
 // (or early-outed) and stored exactly as in the plain forms, in ascending slab order on the plain call's grid, so wherever every
 // item outside V would have taken the zero-tile early-out the weight-gradient partials see the same tiles in the same order.  dx
-// (plain form) is written on the visited items only; aux / y outside V and dz of items no visited item stages are not read.  The
-// mask's words ride where the form has a free pointer: DZ0 in the plain form, aux in the FIRST + FROMY form.  A NaN / Inf weight
+// (plain form) is written on the visited items only; aux / y outside V and dz of items no visited item stages are not read.  V is
+// `km` in both forms (the host builds it with keep_mask_of, as for the forward's KEEP forms).  A NaN / Inf weight
 // does NOT widen the window (DZMASK does): V is visited regardless, see scn_conv_backward_visit in include/scone_hip.h.
 // UNIT PIPELINE of the VISIT forms.  On a cone a unit has 1.3 visits on average, so the slab pipeline inside a unit (visit it + 1 is
 // staged from the side slots of visit it's contraction) rarely has a second visit to work on, and every unit started with four
@@ -147,15 +150,15 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 // barrier at the next unit's top).  No arithmetic changes: the same tiles in the same order into the same accumulators.  A unit
 // without a successor in the table (the last entry of a scan, the workgroup's last unit) stages nothing ahead, and the unit behind
 // it runs the full prologue.  SCN_VISIT_PREFETCH=0 compiles the unit loop without any of this; a launch without
-// VISIT_FLAG_PREFETCH in wl.n_work (dense launches do not use the field otherwise) takes that loop at run time.
+// VISIT_FLAG_PREFETCH in its `flags` argument takes that loop at run time.
 #ifndef SCN_VISIT_PREFETCH
 #define SCN_VISIT_PREFETCH 1
 #endif
 constexpr int VISIT_FLAG_PREFETCH = 1;
 constexpr int VISIT_ROWS_BYTES = BK_SRC * 4;                  // the second source-row buffer: dynamic LDS of the VISIT launches, behind the scan table
 static_assert(WSCAN_LDS_BYTES % 16 == 0, "the second source-row buffer starts 16-byte aligned");
-template <int ACT, bool EXT0 = false, bool PAIR = false, bool FIRST = false, bool ACCUM = false, bool FROMY = false, bool DZMASK = false,
-          bool VISIT = false>
+enum : unsigned { BWD_EXT0 = 1, BWD_PAIR = 2, BWD_FIRST = 4, BWD_ACCUM = 8, BWD_FROMY = 16, BWD_DZMASK = 32, BWD_VISIT = 64 };
+template <int ACT, unsigned FORM = 0>
 __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, const float* __restrict__ DZ,
                                                                      const float* __restrict__ DZ0,
                                                                      const float* __restrict__ W0,
@@ -164,19 +167,25 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                                                                      const float* __restrict__ aux,
                                                                      float* __restrict__ dx, float* __restrict__ partial,
                                                                      int n_rows, int n_cols, int n_slabs, WorkList wl,
-                                                                     float* __restrict__ partial_first = nullptr,
-                                                                     FirstW fw = FirstW{{nullptr, nullptr, nullptr}}) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+                                                                     float* __restrict__ partial_first, FirstW fw, KeepMask km,
+                                                                     int flags) {
+    constexpr bool EXT0 = (FORM & BWD_EXT0) != 0, PAIR = (FORM & BWD_PAIR) != 0, FIRST = (FORM & BWD_FIRST) != 0, ACCUM = (FORM & BWD_ACCUM) != 0,
+                   FROMY = (FORM & BWD_FROMY) != 0, DZMASK = (FORM & BWD_DZMASK) != 0, VISIT = (FORM & BWD_VISIT) != 0;
     static_assert(!FROMY || (FIRST && !PAIR), "the aux-free form exists for the fused-first C = 32 kernel");
     static_assert(!DZMASK || (!EXT0 && !PAIR && !FIRST && !ACCUM && !FROMY), "the source mask exists for the plain C = 32 kernel");
     static_assert(!FIRST || !EXT0, "the fused first-layer gradient exists for the plain forms (C = 32, and C = 16 on slab pairs)");
     static_assert(!VISIT || (!EXT0 && !PAIR && !ACCUM && !DZMASK && FIRST == FROMY), "the visit mask exists for the plain and the fused-first from-y C = 32 kernel");
+    static_assert(!ACCUM || (!EXT0 && !FIRST && !PAIR), "the accumulate form exists for the plain C = 32 kernel");
+    // the one thing DZ0 is in this form (null in a form that has none of the three)
+    const float* const dz_own = EXT0 ? DZ0 : nullptr;          // EXT0: the upstream gradient itself, segment 0 of G
+    const float* const dx_partial = ACCUM ? DZ0 : nullptr;     // ACCUM: the input gradient's partial sum, of dx's shape
+    const float* const y_rec = FIRST ? DZ0 : nullptr;          // FIRST: the first layer's shifted-input records
+    extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / BK_THREADS;
     constexpr int CH = PAIR ? 16 : 32;                       // channels of a stored point
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     char* wfrag = smem + smem_bytes_c32();
-    static_assert(!ACCUM || (!EXT0 && !FIRST && !PAIR), "the accumulate form exists for the plain C = 32 kernel");
     constexpr bool accumulate = ACCUM;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -235,7 +244,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     int e_run = 1 << 20;                                      // running exponent of the dW accumulators (see the header): none yet
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     SCN_UNIT_RANGE();
-    SCN_WINDOW_WALK(VISIT, (KeepMask{(const uint32_t*)(FIRST ? aux : DZ0), (n_slabs + 31) >> 5}), smem + smem_bytes_c32(B32_EXTRA_BYTES),
+    SCN_WINDOW_WALK(VISIT, km, smem + smem_bytes_c32(B32_EXTRA_BYTES),
                     (UnitList{nullptr, nullptr}));   // (dW is summed in visit order: the backward keeps its static units)
     uint32_t cqs[4];
 #pragma unroll
@@ -244,7 +253,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     const bool second = PAIR && (((lane >> 2) ^ wave) & 1);       // this lane's LDS-DMA chunks come from slab B (see dma_k)
     // UNIT PIPELINE (the VISIT forms; see the header).  All of it is workgroup-uniform and lives across units and table scans.
     constexpr bool PIPE = VISIT && SCN_VISIT_PREFETCH != 0;
-    const bool pipe_on = PIPE && !listed && (wl.n_work & VISIT_FLAG_PREFETCH) != 0;   // (dense launches: n_work carries the launch's flags)
+    const bool pipe_on = PIPE && !listed && (flags & VISIT_FLAG_PREFETCH) != 0;
     int32_t* const srcrows_b = (int32_t*)(smem + smem_bytes_c32(B32_EXTRA_BYTES) + WSCAN_LDS_BYTES);   // the second source-row buffer, behind the scan's table
     const int sr_b = (int)(srcrows_b - sm.srcrows);             // its distance from the first, in rows
     int vpar = 0;                                               // staging buffer of the unit's first visit: the workgroup's visits so far, mod 2
@@ -275,7 +284,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                                                                                n_next, wave, tw_p, twu_p)
                                             : load_block_c32<BK_THREADS>(P, b, sm);
         // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
-        const uint64_t dzm = DZMASK ? (keep_window(KeepMask{(const uint32_t*)DZ0, (n_slabs + 31) >> 5}, b, k0) | (w_bad ? ~0ull : 0ull)) : ~0ull;
+        const uint64_t dzm = DZMASK ? (keep_window(km, b, k0) | (w_bad ? ~0ull : 0ull)) : ~0ull;
         __syncthreads();
         STAMP_UADD(1);
         const int tw = PIPE && pipe_on ? tw_p : P.tile_w[b * BK_WAVES + wave];
@@ -397,11 +406,11 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                     a[r] = ok ? v : 0.f;
                 }
             }
-            // ACCUM form (plain kernel): DZ0 is a tensor of dx's shape holding the input gradient's partial sum
+            // ACCUM form (plain kernel): dx_partial is a tensor of dx's shape holding the input gradient's partial sum
             // over the output blocks before this one (hidden widths above 32, see fwd_c32_w16_kernel); it may be dx itself
             float dxp[16];
             if (accumulate) {
-                const float* pp = DZ0 + (rows_left > 0 ? tuni : 0);
+                const float* pp = dx_partial + (rows_left > 0 ? tuni : 0);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const bool ok = 2 * (r >> 2) + h < rows_left && lane_live;
@@ -413,7 +422,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             // this lane group's slab
             float yv[3] = {0.f, 0.f, 0.f};
             if (FIRST) {
-                const float* yt = DZ0 + (((size_t)slab * n_rows + m.row0 + wave * 8) * BK_NS) * Y_STRIDE;
+                const float* yt = y_rec + (((size_t)slab * n_rows + m.row0 + wave * 8) * BK_NS) * Y_STRIDE;
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     const int idx = 16 * q + (lane & 15), r = idx / 3, g = idx - 3 * r;
@@ -429,7 +438,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
             // ---------------- GATHER: all three segments (the tile's scale needs the largest of them all)
             if (EXT0) {
                 // (PAIR: the lane's sixteen virtual channels 16 h .. 16 h + 15 are slab h's sixteen)
-                const float* g0 = DZ0 + (((size_t)(PAIR ? slab_of(it, h) : slab) * n_rows + m.row0 + rtc) * BK_NS + n) * CH + (PAIR ? 0 : 16 * h);
+                const float* g0 = dz_own + (((size_t)(PAIR ? slab_of(it, h) : slab) * n_rows + m.row0 + rtc) * BK_NS + n) * CH + (PAIR ? 0 : 16 * h);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) G[0][q] = *(const f32x4*)(g0 + 4 * q);
                 f32x4 unused[4];
@@ -692,17 +701,16 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     if (VISIT) { STAMP_FLUSH_WG(); }
 }
 
-// The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so the trailing partial_first and fw are always passed; the
-// dispatch never spells the boolean pack).  The static_asserts inside the kernel say which combinations exist; what DZ, DZ0, aux and
-// fw carry in each:
-template <int ACT> constexpr auto bwd_c32_plain = bwd_c32_bf16_kernel<ACT>;                                  // DZ = dz, DZ0 null
-template <int ACT> constexpr auto bwd_c32_pair = bwd_c32_bf16_kernel<ACT, false, true>;                      // the same at C = 16, on slab pairs
-template <int ACT> constexpr auto bwd_c32_plain_dzmask = bwd_c32_bf16_kernel<ACT, false, false, false, false, false, true>;   // DZ = dz staged by DZ0 = source mask words
-template <int ACT> constexpr auto bwd_c32_power = bwd_c32_bf16_kernel<ACT, true>;                            // DZ = g1 = S^T dz, DZ0 = dz
-template <int ACT> constexpr auto bwd_c32_power_pair = bwd_c32_bf16_kernel<ACT, true, true>;                 // the same at C = 16
-template <int ACT> constexpr auto bwd_c32_accum = bwd_c32_bf16_kernel<ACT, false, false, false, true>;       // DZ0 = dx_partial, added to dx
-template <int ACT> constexpr auto bwd_c32_first = bwd_c32_bf16_kernel<ACT, false, false, true>;              // DZ0 = y, dx null: -> partial_first
-template <int ACT> constexpr auto bwd_c32_first_pair = bwd_c32_bf16_kernel<ACT, false, true, true>;          // the same at C = 16
-template <int ACT> constexpr auto bwd_c32_first_from_y = bwd_c32_bf16_kernel<ACT, false, false, true, false, true>;   // and aux null: rebuilt from y and fw
-template <int ACT> constexpr auto bwd_c32_plain_visit = bwd_c32_bf16_kernel<ACT, false, false, false, false, false, false, true>;   // DZ = dz, DZ0 = visit mask words
-template <int ACT> constexpr auto bwd_c32_first_from_y_visit = bwd_c32_bf16_kernel<ACT, false, false, true, false, true, false, true>;   // DZ0 = y, aux = visit mask words
+// The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so partial_first, fw, km and flags are always passed).  The
+// static_asserts inside the kernel say which combinations exist; what DZ, DZ0, aux, fw and km carry in each (null where not named):
+template <int ACT> constexpr auto bwd_c32_plain = bwd_c32_bf16_kernel<ACT>;                                              // DZ = dz
+template <int ACT> constexpr auto bwd_c32_pair = bwd_c32_bf16_kernel<ACT, BWD_PAIR>;                                     // the same at C = 16, on slab pairs
+template <int ACT> constexpr auto bwd_c32_plain_dzmask = bwd_c32_bf16_kernel<ACT, BWD_DZMASK>;                           // DZ = dz, staged by km = the source mask
+template <int ACT> constexpr auto bwd_c32_power = bwd_c32_bf16_kernel<ACT, BWD_EXT0>;                                    // DZ = g1 = S^T dz, DZ0 = dz
+template <int ACT> constexpr auto bwd_c32_power_pair = bwd_c32_bf16_kernel<ACT, BWD_EXT0 | BWD_PAIR>;                    // the same at C = 16
+template <int ACT> constexpr auto bwd_c32_accum = bwd_c32_bf16_kernel<ACT, BWD_ACCUM>;                                   // DZ0 = dx_partial, added to dx
+template <int ACT> constexpr auto bwd_c32_first = bwd_c32_bf16_kernel<ACT, BWD_FIRST>;                                   // DZ0 = y, dx null: -> partial_first
+template <int ACT> constexpr auto bwd_c32_first_pair = bwd_c32_bf16_kernel<ACT, BWD_FIRST | BWD_PAIR>;                   // the same at C = 16
+template <int ACT> constexpr auto bwd_c32_first_from_y = bwd_c32_bf16_kernel<ACT, BWD_FIRST | BWD_FROMY>;                // and aux null: rebuilt from y and fw
+template <int ACT> constexpr auto bwd_c32_plain_visit = bwd_c32_bf16_kernel<ACT, BWD_VISIT>;                             // DZ = dz, km = the visit mask, flags
+template <int ACT> constexpr auto bwd_c32_first_from_y_visit = bwd_c32_bf16_kernel<ACT, BWD_FIRST | BWD_FROMY | BWD_VISIT>;   // DZ0 = y, aux null, km = the visit mask, flags

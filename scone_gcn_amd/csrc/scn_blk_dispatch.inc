@@ -78,7 +78,6 @@ static dim3 launch_grid(const scn_conv_s* c, int n_slabs, size_t lds, int max_pe
     return dim3(bx, by);
 }
 
-constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
 constexpr FirstW NO_FIRSTW{{nullptr, nullptr, nullptr}};
 constexpr KeepMask NO_KEEP{nullptr, 0};
 constexpr UnitList NO_UNITS{nullptr, nullptr};
@@ -88,16 +87,13 @@ constexpr UnitList NO_UNITS{nullptr, nullptr};
 static_assert(W16_EXTRA_BYTES + W16_FIRSTW_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16) &&
               B32_EXTRA_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
               "the scan's table fits behind the kernels' own LDS");
-// The VISIT backwards take VISIT_ROWS_BYTES more behind the table (the unit pipeline's second source-row buffer, scn_blk_bwd.inc), and
-// their launch flags in the work list's n_work, which a dense launch does not use otherwise.  g_visit_prefetch: scn_conv_visit_prefetch.
+// The VISIT backwards take VISIT_ROWS_BYTES more behind the table (the unit pipeline's second source-row buffer, scn_blk_bwd.inc).
+// Their `flags` argument carries the process-wide switch g_visit_prefetch (scn_conv_visit_prefetch).
 constexpr size_t VISIT_LDS_BYTES = WSCAN_LDS_BYTES + VISIT_ROWS_BYTES;
 static_assert(B32_EXTRA_BYTES + VISIT_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
               "the scan's table and the second source-row buffer fit behind the backward's own LDS");
 static int g_visit_prefetch = 1;
-static WorkList visit_launch_flags(WorkList wl) {
-    wl.n_work = g_visit_prefetch ? VISIT_FLAG_PREFETCH : 0;
-    return wl;
-}
+static int visit_flags() { return g_visit_prefetch ? VISIT_FLAG_PREFETCH : 0; }
 
 // The keep mask of a launch (scn_conv_forward_keep / _from_y_keep; the source mask of scn_conv_backward_dzmask has its geometry and
 // its window limit): words per block from the slab count.  A workgroup holds the bits
@@ -138,63 +134,58 @@ bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in,
     return (ci == 32 && c_out == 32) || (ci == 16 && c_out == 16) || (ci == 1 && (c_out == 16 || c_out == 32));
 }
 
-int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
-                    const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wlp,
-                    hipStream_t st, const float* partial,              // partial (32 -> 32 only): out = act(partial + ...), see fwd_c32_w16_kernel
-                    const uint32_t* keep,                              // keep (32 -> 32 and 16 -> 16, dense, no partial): only the mask's items are stored (32 -> 32: visited)
-                    const uint32_t* units, const uint32_t* unit_count) {   // the mask's unit list (32 -> 32; unit_list_of), or null
-    const WorkList wl = wlp ? *wlp : NO_LIST;
-    const int ci = c_in[0];
-    if (partial && ci != 32) return SCN_ERR_UNSUPPORTED;
-    if (keep && (partial || wl.block || !out || (ci != 32 && ci != 16))) return SCN_ERR_UNSUPPORTED;   // (the first layer is never the last)
-    if (!out) {                                                           // first layer, shifted input only (scn_conv_forward_first with out = NULL)
-        if (ci != 1 || !y_out || wl.block) return SCN_ERR_UNSUPPORTED;
+int blocked_forward(scn_conv_s* c, const FwdLaunch& a) {
+    const int n_slabs = a.n_slabs, ci = a.c_in;
+    const float* const* W = a.W;
+    const WorkList& wl = a.wl;
+    hipStream_t st = a.st;
+    if (a.partial && ci != 32) return SCN_ERR_UNSUPPORTED;
+    if (a.keep && (a.partial || wl.block || !a.out || (ci != 32 && ci != 16))) return SCN_ERR_UNSUPPORTED;   // (the first layer is never the last)
+    if (!a.out) {                                                         // first layer, shifted input only (scn_conv_forward_first with out = NULL)
+        if (ci != 1 || !a.y_out || wl.block) return SCN_ERR_UNSUPPORTED;
         const size_t lds = smem_bytes(16);
-        return launch_checked(gather3_c1_kernel, launch_grid(c, n_slabs, lds), dim3(BK_THREADS), lds, st, c->plan.dev, src[0], y_out,
+        return launch_checked(gather3_c1_kernel, launch_grid(c, n_slabs, lds), dim3(BK_THREADS), lds, st, c->plan.dev, a.src, a.y_out,
                               c->n_rows, c->g[0].n_cols, n_slabs);
     }
     if (ci == 32) {                                                       // 16 waves, f16 hi + lo split
         const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES);
         const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
-        if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
-        return with_act(act, [&](auto A) -> int {
+        if (a.keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
+        return with_act(a.act, [&](auto A) -> int {
             constexpr int ACT = decltype(A)::value;
-            if (keep)
-                return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, src[0], nullptr, W[0], W[1], W[2],
-                                      out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, L.grid, n_slabs));
-            return launch_checked(partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0],
-                                  partial, W[0], W[1], W[2], out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP, NO_UNITS);
+            if (a.keep)
+                return launch_checked(fwd_c32_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, a.src, nullptr, W[0], W[1], W[2],
+                                      a.out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, keep_mask_of(a.keep, n_slabs),
+                                      unit_list_of(a.units, a.unit_count, L.grid, n_slabs));
+            return launch_checked(a.partial ? fwd_c32_accum<ACT> : fwd_c32_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, a.src,
+                                  a.partial, W[0], W[1], W[2], a.out, L.nr, L.nc, n_slabs, wl, NO_FIRSTW, NO_KEEP, NO_UNITS);
         });
     }
     if (ci == 16) {                                                       // 16 waves, f16 hi + lo split, two slabs per visit
         const size_t lds = smem_bytes_c32(16 + 64);
         const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
-        if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
-        return with_act(act, [&](auto A) -> int {
+        if (a.keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
+        return with_act(a.act, [&](auto A) -> int {
             constexpr int ACT = decltype(A)::value;
-            if (keep)
-                return launch_checked(fwd_c16_plain_keep<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1], W[2],
-                                      out, L.nr, L.nc, n_slabs, wl, keep_mask_of(keep, n_slabs));
-            return launch_checked(fwd_c16_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, src[0], nullptr, W[0], W[1],
-                                  W[2], out, L.nr, L.nc, n_slabs, wl, NO_KEEP);
+            return launch_checked(a.keep ? fwd_c16_plain_keep<ACT> : fwd_c16_plain<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, a.src, nullptr,
+                                  W[0], W[1], W[2], a.out, L.nr, L.nc, n_slabs, wl, a.keep ? keep_mask_of(a.keep, n_slabs) : NO_KEEP);
         });
     }
     const size_t lds = smem_bytes(16, 2 * BK_R * BK_NS * 12);
     // 8-wave workgroups at 64 VGPRs and 23 KB of LDS: three per CU (4.45 -> 3.9 ms; four: 4.8)
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl, 3);
-    return launch_checked(c_out == 32 ? fwd_c1_kernel<32> : fwd_c1_kernel<16>, L.grid, dim3(BK_THREADS), lds, st, L.P, src[0], W[0], W[1],
-                          W[2], out, y_out, L.nr, L.nc, n_slabs, act, wl);
+    return launch_checked(a.c_out == 32 ? fwd_c1_kernel<32> : fwd_c1_kernel<16>, L.grid, dim3(BK_THREADS), lds, st, L.P, a.src, W[0], W[1],
+                          W[2], a.out, a.y_out, L.nr, L.nc, n_slabs, a.act, wl);
 }
 
 // The y-only launch of the first layer (blocked_forward with out = nullptr) on the items of a keep mask: gather3_c1_keep_kernel on
-// the plain launch's grid.
-int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st,
-                               const uint32_t* units, const uint32_t* unit_count) {      // the mask's unit list (unit_list_of), or null
+// the plain launch's grid.  Of the record: n_slabs, src, y_out, keep, units / unit_count, st.
+int blocked_shifted_input_keep(scn_conv_s* c, const FwdLaunch& a) {
     const size_t lds = smem_bytes(16);
-    const dim3 grid = launch_grid(c, n_slabs, lds);
-    if (!keep_fits(grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
-    return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, st, c->plan.dev, x, y_out, c->n_rows, c->g[0].n_cols,
-                          n_slabs, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, grid, n_slabs));
+    const dim3 grid = launch_grid(c, a.n_slabs, lds);
+    if (!keep_fits(grid.y, a.n_slabs)) return SCN_ERR_UNSUPPORTED;
+    return launch_checked(gather3_c1_keep_kernel, grid, dim3(BK_THREADS), lds + WSCAN_LDS_BYTES, a.st, c->plan.dev, a.src, a.y_out, c->n_rows,
+                          c->g[0].n_cols, a.n_slabs, keep_mask_of(a.keep, a.n_slabs), unit_list_of(a.units, a.unit_count, grid, a.n_slabs));
 }
 
 // Layer 2 of a stack whose first layer has one input channel, straight from the first layer's shifted-input records
@@ -203,20 +194,21 @@ bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch) {
     return scone_shape(c) && ns == BK_NS && ch == 32 && c->n_rows == c->g[0].n_cols;
 }
 
-int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st, const uint32_t* keep,        // keep: visits and stores by the mask (see blocked_forward)
-                           const uint32_t* units, const uint32_t* unit_count) {     // the mask's unit list (unit_list_of), or null
-    const FirstW fw{{W_first[0], W_first[1], W_first[2]}};
+int blocked_forward_from_y(scn_conv_s* c, const FromYLaunch& a) {
+    const int n_slabs = a.n_slabs;
+    const float* const* W = a.W;
+    const FirstW fw{{a.W_first[0], a.W_first[1], a.W_first[2]}};
     const size_t lds = smem_bytes_c32(W16_EXTRA_BYTES + W16_FIRSTW_BYTES);
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds);
-    if (keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
-    return with_act(act, [&](auto A) -> int {
+    if (a.keep && !keep_fits(L.grid.y, n_slabs)) return SCN_ERR_UNSUPPORTED;
+    return with_act(a.act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
-        if (keep)
-            return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, st, L.P, y, nullptr, W[0], W[1], W[2], out, L.nr,
-                                  L.nc, n_slabs, NO_LIST, fw, keep_mask_of(keep, n_slabs), unit_list_of(units, unit_count, L.grid, n_slabs));
-        return launch_checked(fwd_c32_from_y<ACT>, L.grid, dim3(W16_THREADS), lds, st, L.P, y, nullptr, W[0], W[1], W[2],
-                              out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP, NO_UNITS);
+        if (a.keep)
+            return launch_checked(fwd_c32_from_y_keep<ACT>, L.grid, dim3(W16_THREADS), lds + WSCAN_LDS_BYTES, a.st, L.P, a.y, nullptr, W[0], W[1], W[2],
+                                  a.out, L.nr, L.nc, n_slabs, NO_LIST, fw, keep_mask_of(a.keep, n_slabs),
+                                  unit_list_of(a.units, a.unit_count, L.grid, n_slabs));
+        return launch_checked(fwd_c32_from_y<ACT>, L.grid, dim3(W16_THREADS), lds, a.st, L.P, a.y, nullptr, W[0], W[1], W[2],
+                              a.out, L.nr, L.nc, n_slabs, NO_LIST, fw, NO_KEEP, NO_UNITS);
     });
 }
 
@@ -243,32 +235,27 @@ size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, cons
     return bwd_workgroups(c, n_slabs) * c_aux * 3 * c_dz[0] * sizeof(float);
 }
 
-int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
-                     const float* const* W, const float* aux, int c_aux, int act, float* dx,
-                     float* const* dW, void* ws, size_t ws_bytes, const WorkList* wlp, hipStream_t st,
-                     const float* dx_partial,             // dx_partial (32 -> 32 only): dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
-                     const uint32_t* dzmask,              // dzmask (32 -> 32, dense, no partial): dz is staged by the mask, see there
-                     const uint32_t* visit) {             // visit (the same shapes, no dzmask): only the mask's items are visited, see there
-    const WorkList wl = wlp ? *wlp : NO_LIST;
-    const int cd = c_dz[0];
-    float* partial = (float*)ws;
+int blocked_backward(scn_conv_s* c, const BwdLaunch& a) {
+    const int n_slabs = a.n_slabs, cd = a.c_dz, c_aux = a.c_aux;
+    const float* const* W = a.W;
+    const WorkList& wl = a.wl;
+    float* partial = (float*)a.ws;
     const size_t lds = bwd_lds();
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
-    if (dx_partial && (c_aux != 32 || !dx)) return SCN_ERR_UNSUPPORTED;
-    const uint32_t* mask = dzmask ? dzmask : visit;
-    if (mask && ((dzmask && visit) || dx_partial || wl.block || c_aux != 32 || cd != 32 || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
-    const int st_k = with_act(act, [&](auto A) -> int {
+    if (a.dx_partial && (c_aux != 32 || !a.dx)) return SCN_ERR_UNSUPPORTED;
+    const uint32_t* mask = a.dzmask ? a.dzmask : a.visit;
+    if (mask && ((a.dzmask && a.visit) || a.dx_partial || wl.block || c_aux != 32 || cd != 32 || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
+    const int st_k = with_act(a.act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
-        if (mask)                                                // (the mask's words ride in DZ0: ceil(n_slabs / 32) per block)
-            return launch_checked(dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS),
-                                  lds + (dzmask ? 0 : VISIT_LDS_BYTES), st, L.P, dz[0],
-                                  (const float*)mask, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, dzmask ? wl : visit_launch_flags(wl),
-                                  nullptr, NO_FIRSTW);
-        const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
-        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz[0], dx_partial, W[0], W[1], W[2], aux, dx, partial, L.nr, L.nc,
-                              n_slabs, wl, nullptr, NO_FIRSTW);
+        if (mask)
+            return launch_checked(a.dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS),
+                                  lds + (a.dzmask ? 0 : VISIT_LDS_BYTES), a.st, L.P, a.dz, nullptr, W[0], W[1], W[2], a.aux, a.dx, partial, L.nr, L.nc,
+                                  n_slabs, wl, nullptr, NO_FIRSTW, keep_mask_of(mask, n_slabs), a.dzmask ? 0 : visit_flags());
+        const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (a.dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
+        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.dx_partial, W[0], W[1], W[2], a.aux, a.dx, partial, L.nr, L.nc,
+                              n_slabs, wl, nullptr, NO_FIRSTW, NO_KEEP, 0);
     });
-    return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), c_aux, cd, dW, st);
+    return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), c_aux, cd, a.dW, a.st);
 }
 
 // Backward of the layer that follows the first one, fused with the first layer's weight gradient (bwd_c32_first and its kin).
@@ -298,35 +285,34 @@ __global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* _
     }
 }
 
-int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
-                           const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st, const float* const* W_first,   // W_first (32 channels): aux is rebuilt from y, not read
-                           const uint32_t* visit) {                       // visit (with W_first, dense): only the mask's items are visited
-    const WorkList wl = wlp ? *wlp : NO_LIST;
+int blocked_backward_first(scn_conv_s* c, const BwdFirstLaunch& a) {
+    const int n_slabs = a.n_slabs, ch = a.ch;
+    const float* const* W = a.W;
+    const WorkList& wl = a.wl;
     const size_t lds = bwd_lds();
     const BlockedLaunch L = blocked_launch(c, n_slabs, lds, wl);
     const int n_wg = L.n_wg();
-    float* partial = (float*)ws;
+    float* partial = (float*)a.ws;
     float* partial_first = partial + (size_t)n_wg * 3 * ch * ch;
-    if (W_first && ch != 32) return SCN_ERR_UNSUPPORTED;
-    if (visit && (!W_first || wl.block || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
-    const FirstW fw = W_first ? FirstW{{W_first[0], W_first[1], W_first[2]}} : NO_FIRSTW;
-    int st_k = with_act(act, [&](auto A) -> int {
+    if (a.W_first && ch != 32) return SCN_ERR_UNSUPPORTED;
+    if (a.visit && (!a.W_first || wl.block || !keep_fits(L.grid.y, n_slabs))) return SCN_ERR_UNSUPPORTED;
+    const FirstW fw = a.W_first ? FirstW{{a.W_first[0], a.W_first[1], a.W_first[2]}} : NO_FIRSTW;
+    int st_k = with_act(a.act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
-        if (visit)                                               // (the mask's words ride in aux, which this form does not read)
-            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + VISIT_LDS_BYTES, st, L.P, dz, y, W[0], W[1], W[2],
-                                  (const float*)visit, nullptr, partial, L.nr, L.nc, n_slabs, visit_launch_flags(wl), partial_first, fw);
-        const auto k = W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
-        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, st, L.P, dz, y, W[0], W[1], W[2], W_first ? nullptr : aux, nullptr, partial,
-                              L.nr, L.nc, n_slabs, wl, partial_first, fw);
+        if (a.visit)
+            return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + VISIT_LDS_BYTES, a.st, L.P, a.dz, a.y, W[0], W[1], W[2],
+                                  nullptr, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw, keep_mask_of(a.visit, n_slabs), visit_flags());
+        const auto k = a.W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
+        return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.y, W[0], W[1], W[2], a.W_first ? nullptr : a.aux, nullptr, partial,
+                              L.nr, L.nc, n_slabs, wl, partial_first, fw, NO_KEEP, 0);
     });
-    if (st_k == SCN_OK) st_k = reduce_dw(partial, n_wg, ch, ch, dW, st);
+    if (st_k == SCN_OK) st_k = reduce_dw(partial, n_wg, ch, ch, a.dW, a.st);
     if (st_k != SCN_OK) return st_k;
     if (ch == 32)
-        return launch_checked(dw_first_reduce_kernel, dim3(96), dim3(64), 0, st, partial_first, n_wg, 32, dW_first[0], dW_first[1],
-                              dW_first[2]);
-    return launch_checked(dw_first_reduce_pair_kernel, dim3(48), dim3(64), 0, st, partial_first, n_wg, dW_first[0], dW_first[1],
-                          dW_first[2]);
+        return launch_checked(dw_first_reduce_kernel, dim3(96), dim3(64), 0, a.st, partial_first, n_wg, 32, a.dW_first[0], a.dW_first[1],
+                              a.dW_first[2]);
+    return launch_checked(dw_first_reduce_pair_kernel, dim3(48), dim3(64), 0, a.st, partial_first, n_wg, a.dW_first[0], a.dW_first[1],
+                          a.dW_first[2]);
 }
 
 // (with a y handed in the operator only supplies the row count and, for work lists, the block table)
@@ -443,7 +429,7 @@ int blocked_power_backward(scn_conv_s* c, int n_slabs, const float* dz, const fl
     const int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         return launch_checked(ch == 32 ? bwd_c32_power<ACT> : bwd_c32_power_pair<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, g1, dz, W[0],
-                              W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, NO_LIST, nullptr, NO_FIRSTW);
+                              W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, NO_LIST, nullptr, NO_FIRSTW, NO_KEEP, 0);
     });
     return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), ch, ch, dW, st);
 }

@@ -234,13 +234,16 @@ constexpr int W16_FIRSTW_BYTES = 3 * 32 * 4;              // FROMY: the first la
 // wait for the LDS-DMA just issued: profiles/HISTORY.md section 3.2); the slab loop walks it in SGPRs (scn_keep_bits.h).  The host
 // hands a workgroup at most KEEP_WINDOW slabs.
 constexpr int KEEP_WINDOW = 64;
+// FORM: the form of the 16-wave forwards, an OR of these bits (fwd_c16_w16_kernel: FWD_EXT0 and FWD_KEEP); the kernels' first lines
+// name them and assert which combinations exist.
+enum : unsigned { FWD_EXT0 = 1, FWD_ACCUM = 2, FWD_FROMY = 4, FWD_KEEP = 8 };
 __device__ __forceinline__ uint64_t keep_window(const KeepMask km, int b, int first) {
     const uint64_t win = keep_window_lane(km, b, first);      // (scn_window_scan.inc: three loads, no branch; the one copy of the rule)
     uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)win), hi = __builtin_amdgcn_readfirstlane((uint32_t)(win >> 32));   // wave-uniform
     asm volatile("" : "+s"(lo), "+s"(hi));                    // the loads are waited for HERE
     return ((uint64_t)hi << 32) | lo;
 }
-template <int ACT, bool EXT0 = false, bool ACCUM = false, bool FROMY = false, bool KEEP = false>
+template <int ACT, unsigned FORM = 0>
 __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, const float* __restrict__ X,
                                                                      const float* __restrict__ X0,
                                                                      const float* __restrict__ W0,
@@ -248,10 +251,12 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
                                                                      int n_slabs, WorkList wl, FirstW fw, KeepMask km, UnitList ul) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave
+    constexpr bool EXT0 = (FORM & FWD_EXT0) != 0, ACCUM = (FORM & FWD_ACCUM) != 0, FROMY = (FORM & FWD_FROMY) != 0, KEEP = (FORM & FWD_KEEP) != 0;
     static_assert(!FROMY || (!EXT0 && !ACCUM), "the from-y form exists for the plain kernel");
     static_assert(!KEEP || (!EXT0 && !ACCUM), "the keep mask exists for the plain and the from-y kernel");
+    static_assert(!(EXT0 && ACCUM), "the accumulate form exists for the plain kernel");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int PIECE = 512, CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     char* wfrag = smem + smem_bytes_c32();
@@ -420,7 +425,6 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
         }
         f32x4 z[3][2];                                 // [segment][chunk q]: channels 8*kq + 4*q .. +3 of this lane's point
         f32x4 addv[2];                                 // accumulate form: the partial pre-activations of this lane's eight outputs
-        static_assert(!(EXT0 && ACCUM), "the accumulate form exists for the plain kernel");
         constexpr bool accumulate = ACCUM;
         auto tile_of = [&](int slab) { return ((size_t)slab * n_rows + m.row0) * (BK_NS * 32); };   // (scalar) first float of the block's rows in a slab
         // ---------------- GATHER of slab `it` (staged in buffer it & 1) into z
@@ -589,14 +593,14 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c32_w16_kernel(PlanDev P, 
     }
 }
 
-// The forms of fwd_c32_w16_kernel by name (one function-pointer type; the dispatch never spells the boolean pack).  The
+// The forms of fwd_c32_w16_kernel by name (one function-pointer type; the dispatch never spells FORM).  The
 // static_asserts inside the kernel say which combinations exist; here is what X, X0 and fw carry in each:
 template <int ACT> constexpr auto fwd_c32_plain = fwd_c32_w16_kernel<ACT>;                        // X = the layer's input; X0 null, fw null
-template <int ACT> constexpr auto fwd_c32_power = fwd_c32_w16_kernel<ACT, true>;                  // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
-template <int ACT> constexpr auto fwd_c32_accum = fwd_c32_w16_kernel<ACT, false, true>;           // X0 = partial pre-activation, added before act
-template <int ACT> constexpr auto fwd_c32_from_y = fwd_c32_w16_kernel<ACT, false, false, true>;   // X = the first layer's records y, fw = its weight rows
-template <int ACT> constexpr auto fwd_c32_plain_keep = fwd_c32_w16_kernel<ACT, false, false, false, true>;   // plain, visits by km
-template <int ACT> constexpr auto fwd_c32_from_y_keep = fwd_c32_w16_kernel<ACT, false, false, true, true>;   // from y, visits by km
+template <int ACT> constexpr auto fwd_c32_power = fwd_c32_w16_kernel<ACT, FWD_EXT0>;              // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
+template <int ACT> constexpr auto fwd_c32_accum = fwd_c32_w16_kernel<ACT, FWD_ACCUM>;             // X0 = partial pre-activation, added before act
+template <int ACT> constexpr auto fwd_c32_from_y = fwd_c32_w16_kernel<ACT, FWD_FROMY>;            // X = the first layer's records y, fw = its weight rows
+template <int ACT> constexpr auto fwd_c32_plain_keep = fwd_c32_w16_kernel<ACT, FWD_KEEP>;         // plain, visits by km
+template <int ACT> constexpr auto fwd_c32_from_y_keep = fwd_c32_w16_kernel<ACT, FWD_FROMY | FWD_KEEP>;   // from y, visits by km
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = C_out = 16, sixteen waves, f16 hi + lo split -- the C=32 machinery on TWO slabs at a time:
@@ -623,7 +627,7 @@ __device__ __forceinline__ void split2_4(const f32x4 x, float s, f16x4& hi, f16x
 // EXT0 (the power form, see fwd_c32_w16_kernel): act(X0 W0 + X W1 + (S X) W2), segment 0 = the point's own channels of X0 in
 // slab A / slab B straight from HBM, the operator has one value array.
 // KEEP (plain form, dense launches): see fwd_c32_w16_kernel; each slab of a pair has its own bit.
-template <int ACT, bool EXT0 = false, bool KEEP = false>
+template <int ACT, unsigned FORM = 0>
 __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, const float* __restrict__ X,
                                                                      const float* __restrict__ X0,
                                                                      const float* __restrict__ W0,
@@ -631,9 +635,10 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
                                                                      const float* __restrict__ W2,
                                                                      float* __restrict__ out, int n_rows, int n_cols,
                                                                      int n_slabs, WorkList wl, KeepMask km) {
+    constexpr bool EXT0 = (FORM & FWD_EXT0) != 0, KEEP = (FORM & FWD_KEEP) != 0;
+    static_assert((FORM & ~(FWD_EXT0 | FWD_KEEP)) == 0 && (!KEEP || !EXT0), "the slab-pair forward has the power form and the keep mask, on the plain kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CPP = 32, NDMA = BK_SRC * CPP / W16_THREADS;   // 4 LDS-DMA instructions per wave and slab pair
-    static_assert(!KEEP || !EXT0, "the keep mask exists for the plain kernel");
     const SmemC32 sm = carve_c32(smem);
     const uint32_t lds0 = lds_addr_of(smem);                  // LDS byte address of staging buffer 0
     uint8_t* tws = (uint8_t*)(smem + smem_bytes_c32());
@@ -811,10 +816,10 @@ __global__ __launch_bounds__(W16_THREADS, 4) void fwd_c16_w16_kernel(PlanDev P, 
         if (pend_ptr[q]) *(f32x4*)(pend_ptr[q]) = pend[q];
 }
 
-// The forms of fwd_c16_w16_kernel by name (one function-pointer type; the dispatch never spells the boolean pack):
+// The forms of fwd_c16_w16_kernel by name (one function-pointer type; the dispatch never spells FORM):
 template <int ACT> constexpr auto fwd_c16_plain = fwd_c16_w16_kernel<ACT>;            // X = the layer's input, X0 unused (null)
-template <int ACT> constexpr auto fwd_c16_power = fwd_c16_w16_kernel<ACT, true>;      // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
-template <int ACT> constexpr auto fwd_c16_plain_keep = fwd_c16_w16_kernel<ACT, false, true>;   // plain, stores by km
+template <int ACT> constexpr auto fwd_c16_power = fwd_c16_w16_kernel<ACT, FWD_EXT0>;  // X = x, X0 = x0 of act(x0 W0 + x W1 + (S x) W2)
+template <int ACT> constexpr auto fwd_c16_plain_keep = fwd_c16_w16_kernel<ACT, FWD_KEEP>;   // plain, stores by km
 
 // ------------------------------------------------------------------------------------------------
 // forward, C_in = 1 -> C_out = C (first layer, TE:143-147 with flow (E,1)): three gathered scalars per point,

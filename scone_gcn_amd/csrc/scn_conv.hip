@@ -14,55 +14,6 @@ void set_hip_error(hipError_t e, const char* where) {
     g_hip_err = std::string(where) + ": " + hipGetErrorString(e);
 }
 
-// implemented in scn_blocked.hip
-int build_block_plan(scn_conv_s* c);
-void free_block_plan(scn_conv_s* c);
-bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in, int c_out);
-int blocked_forward(scn_conv_s* c, int n_slabs, int ns, const float* const* src, const int32_t* c_in,
-                    const float* const* W, int c_out, int act, float* out, float* y_out, const WorkList* wl,
-                    hipStream_t st, const float* partial = nullptr, const uint32_t* keep = nullptr, const uint32_t* units = nullptr,
-                    const uint32_t* unit_count = nullptr);
-bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux);
-size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux);
-int blocked_backward(scn_conv_s* c, int n_slabs, int ns, const float* const* dz, const int32_t* c_dz,
-                     const float* const* W, const float* aux, int c_aux, int act, float* dx,
-                     float* const* dW, void* ws, size_t ws_bytes, const WorkList* wl, hipStream_t st,
-                     const float* dx_partial = nullptr, const uint32_t* dzmask = nullptr, const uint32_t* visit = nullptr);
-bool blocked_spmm_supported(const scn_conv_s* c, int k);
-bool blocked_power_supported(const scn_conv_s* c, int ns, int ch);
-size_t blocked_power_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
-int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const float* x, const float* const* W, int ch, int act,
-                          float* out, hipStream_t st);
-int blocked_power_backward(scn_conv_s* c, int n_slabs, const float* dz, const float* g1, const float* const* W,
-                           const float* aux, int ch, int act, float* dx, float* const* dW, void* ws, hipStream_t st);
-bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch);
-size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
-int blocked_backward_first(scn_conv_s* c, int n_slabs, const float* dz, const float* const* W, const float* aux, int ch, int act,
-                           const float* y, float* const* dW, float* const* dW_first, void* ws, const WorkList* wlp,
-                           hipStream_t st, const float* const* W_first = nullptr, const uint32_t* visit = nullptr);
-int blocked_shifted_input_keep(scn_conv_s* c, int n_slabs, const float* x, float* y_out, const uint32_t* keep, hipStream_t st,
-                               const uint32_t* units = nullptr, const uint32_t* unit_count = nullptr);
-bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
-int blocked_forward_from_y(scn_conv_s* c, int n_slabs, const float* y, const float* const* W_first, const float* const* W, int act,
-                           float* out, hipStream_t st, const uint32_t* keep = nullptr, const uint32_t* units = nullptr,
-                           const uint32_t* unit_count = nullptr);
-int build_terms_plan(scn_conv_s* c, const uint8_t* term, const int32_t* lvl_row0, const uint8_t* merged, const int32_t* bins,
-                     int group_rows);
-int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
-                  hipStream_t st);
-size_t terms_backward_workspace(const scn_conv_s* c, int n_slabs);
-int terms_backward(scn_conv_s* c, int n_slabs, const float* const* dz, const float* const* W, const float* const* aux, int act,
-                   float* const* dx, float* const* dW, const float* const* y, float* const* dW_first, void* ws, hipStream_t st);
-bool blocked_dw_first_supported(const scn_conv_s* c, int ns, int cd);
-size_t blocked_dw_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int cd);
-int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y, const float* dz, int cd,
-                     float* const* dW, void* ws, const WorkList* wl, hipStream_t st);
-int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* wl, hipStream_t st);
-int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st);
-int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st);
-int blocked_window_scan_probe(scn_conv_s* c, int n_slabs, const uint32_t* mask, int gx, int slab0, int n_it, int cap, int32_t* out_block,
-                              uint64_t* out_window, int32_t* out_count, int32_t* unit_block, hipStream_t st);
-
 // ------------------------------------------------------------------------------------------------
 // generic kernels
 // ------------------------------------------------------------------------------------------------
@@ -291,6 +242,23 @@ static void fill_op(const scn_conv_s* c, OpArrays& op) {
 
 using namespace scn;
 
+static bool valid_list(const scn_work_list* wl) {
+    return !wl || (wl->n_work >= 0 && wl->block && wl->ptr && (wl->slab || wl->n_work == 0));
+}
+// the optional work list of an entry point as the launches take it (NULL: dense)
+static WorkList list_of(const scn_work_list* wl) { return wl ? WorkList{wl->n_work, wl->block, wl->ptr, wl->slab} : NO_LIST; }
+// The checks the entry points share, each said once: a set of three matrices, one matrix per slot of the operator, the activation
+// code, the slab count a blocked grid can take, the workspace.  Which of them an entry makes, and in which order, is the entry's.
+static bool all3(const float* const* p) { return p && p[0] && p[1] && p[2]; }
+static bool per_slot(const scn_conv_s* c, const float* const* p) {
+    for (int s = 0; s < c->n_slots; ++s)
+        if (!p[s]) return false;
+    return true;
+}
+static bool act_ok(int act) { return act >= 0 && act <= 3; }
+constexpr int MAX_SLABS = 65535;
+static bool ws_short(size_t have, size_t need) { return have < need; }
+
 extern "C" {
 
 int scn_version(void) { return 100; }
@@ -440,8 +408,8 @@ int scn_terms_forward(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* co
                       int32_t act, float* const* out, void* stream) {
     if (!c || !x || !W || !out) return SCN_ERR_BAD_ARG;
     if (!c->terms.built) return SCN_ERR_UNSUPPORTED;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (ns != BK_NS || channels != 32 || n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (ns != BK_NS || channels != 32 || n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
     for (int l = 0; l < 3; ++l)
         if (out[l] && c->terms.lvl_row0[l + 1] == c->terms.lvl_row0[l]) return SCN_ERR_BAD_SHAPE;
     return terms_forward(c, n_slabs, x, W, act, out, (hipStream_t)stream);
@@ -457,8 +425,8 @@ int scn_terms_backward(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* c
                        void* workspace, size_t workspace_bytes, void* stream) {
     if (!c || !dz || !W || !aux || !dx || !dW || !workspace) return SCN_ERR_BAD_ARG;
     if (!c->terms.built) return SCN_ERR_UNSUPPORTED;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (ns != BK_NS || channels != 32 || n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (ns != BK_NS || channels != 32 || n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
     if (workspace_bytes < scn_terms_backward_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
     return terms_backward(c, n_slabs, dz, W, aux, act, dx, dW, nullptr, nullptr, workspace, (hipStream_t)stream);
 }
@@ -468,8 +436,8 @@ int scn_terms_backward_fused_first(scn_conv_t c, int32_t n_slabs, int32_t ns, co
                                    float* const* dW_first, void* workspace, size_t workspace_bytes, void* stream) {
     if (!c || !dz || !W || !aux || !y || !dW || !dW_first || !workspace) return SCN_ERR_BAD_ARG;
     if (!c->terms.built) return SCN_ERR_UNSUPPORTED;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (ns != BK_NS || channels != 32 || n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (ns != BK_NS || channels != 32 || n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
     if (workspace_bytes < scn_terms_backward_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
     for (int l = 0; l < 3; ++l)
         if ((y[l] == nullptr) != (dW_first[l] == nullptr)) return SCN_ERR_BAD_ARG;
@@ -493,11 +461,6 @@ int scn_conv_plan_blocks(scn_conv_t c, int32_t* row0_out) {
     return SCN_OK;
 }
 
-static bool valid_list(const scn_work_list* wl) {
-    return !wl || (wl->n_work >= 0 && wl->block && wl->ptr && (wl->slab || wl->n_work == 0));
-}
-static WorkList to_list(const scn_work_list* wl) { return WorkList{wl->n_work, wl->block, wl->ptr, wl->slab}; }
-
 int scn_conv_forward(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
                      const float* const* W, int32_t c_out, int32_t act, float* out, void* stream) {
     return scn_conv_forward_list(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, stream);
@@ -506,30 +469,30 @@ int scn_conv_forward(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* con
 int scn_conv_forward_accumulate(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
                                 const float* const* W, int32_t c_out, int32_t act, const float* partial, float* out, void* stream) {
     if (!c || !src || !c_in || !W || !out || !partial) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
-    if (!src[0] || c_in[0] <= 0) return SCN_ERR_BAD_ARG;
-    for (int s = 0; s < c->n_slots; ++s)
-        if (!W[s]) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
+    if (!src[0] || c_in[0] <= 0 || !per_slot(c, W)) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_in[0] != 32 || c_out != 32 || !blocked_forward_supported(c, ns, c_in, c_out)) return SCN_ERR_UNSUPPORTED;
-    return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, nullptr, (hipStream_t)stream, partial);
+    FwdLaunch L{n_slabs, src[0], c_in[0], W, c_out, act, out, (hipStream_t)stream};
+    L.partial = partial;
+    return blocked_forward(c, L);
 }
 
 int scn_conv_forward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* src, const int32_t* c_in,
                           const float* const* W, int32_t c_out, int32_t act, float* out, const scn_work_list* wl,
                           void* stream) {
     if (!c || !src || !c_in || !W || !out || !valid_list(wl)) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
+    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
     for (int g = 0; g < c->n_groups; ++g)
         if (!src[g] || c_in[g] <= 0) return SCN_ERR_BAD_ARG;
-    for (int s = 0; s < c->n_slots; ++s)
-        if (!W[s]) return SCN_ERR_BAD_ARG;
+    if (!per_slot(c, W)) return SCN_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    if (blocked_forward_supported(c, ns, c_in, c_out))
-        return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, wl ? &wlist : nullptr, st);
+    if (blocked_forward_supported(c, ns, c_in, c_out)) {
+        FwdLaunch L{n_slabs, src[0], c_in[0], W, c_out, act, out, st};
+        L.wl = list_of(wl);
+        return blocked_forward(c, L);
+    }
     if (wl) return SCN_ERR_UNSUPPORTED;            // work lists exist for the LDS-blocked kernels only
     FwdArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -559,15 +522,16 @@ int scn_conv_forward_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns, const
     if ((units != nullptr) != (unit_count != nullptr) || (units && !keep)) return SCN_ERR_BAD_ARG;
     if (!keep) return scn_conv_forward_list(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, stream);
     if (!c || !src || !c_in || !W || !out) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
-    if (!src[0] || c_in[0] <= 0) return SCN_ERR_BAD_ARG;
-    for (int s = 0; s < c->n_slots; ++s)
-        if (!W[s]) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_out <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
+    if (!src[0] || c_in[0] <= 0 || !per_slot(c, W)) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_in[0] != c_out || (c_out != 32 && c_out != 16) || !blocked_forward_supported(c, ns, c_in, c_out))
         return SCN_ERR_UNSUPPORTED;
-    return blocked_forward(c, n_slabs, ns, src, c_in, W, c_out, act, out, nullptr, nullptr, (hipStream_t)stream, nullptr, keep, units,
-                           unit_count);
+    FwdLaunch L{n_slabs, src[0], c_in[0], W, c_out, act, out, (hipStream_t)stream};
+    L.keep = keep;
+    L.units = units;
+    L.unit_count = unit_count;
+    return blocked_forward(c, L);
 }
 
 static int generic_bwd_blocks(const scn_conv_s* c, int n_slabs) {
@@ -592,14 +556,12 @@ size_t scn_conv_dw_first_workspace(scn_conv_t c, int32_t n_slabs, int32_t ns, in
 int scn_conv_dw_first(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, const float* y, const float* dz,
                       int32_t c_dz, float* const* dW, void* workspace, size_t workspace_bytes, const scn_work_list* wl,
                       void* stream) {
-    if (!c || (!x && !y) || !dz || !dW || !dW[0] || !dW[1] || !dW[2] || !workspace || !valid_list(wl) || (wl && !y))
-        return SCN_ERR_BAD_ARG;
+    if (!c || (!x && !y) || !dz || !all3(dW) || !workspace || !valid_list(wl) || (wl && !y)) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0) return SCN_ERR_BAD_SHAPE;
     if (!blocked_dw_first_supported(c, ns, c_dz)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < blocked_dw_first_workspace(c, n_slabs, ns, c_dz)) return SCN_ERR_WORKSPACE;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    return blocked_dw_first(c, n_slabs, x, y, dz, c_dz, dW, workspace, wl ? &wlist : nullptr, (hipStream_t)stream);
+    if (ws_short(workspace_bytes, blocked_dw_first_workspace(c, n_slabs, ns, c_dz))) return SCN_ERR_WORKSPACE;
+    const WorkList list = list_of(wl);
+    return blocked_dw_first(c, n_slabs, x, y, dz, c_dz, dW, workspace, &list, (hipStream_t)stream);
 }
 
 size_t scn_conv_backward_fused_first_workspace(scn_conv_t c, int32_t n_slabs, int32_t ns, int32_t channels) {
@@ -611,37 +573,35 @@ int scn_conv_backward_fused_first(scn_conv_t c, int32_t n_slabs, int32_t ns, con
                                   const float* aux, int32_t channels, int32_t act, const float* y, float* const* dW,
                                   float* const* dW_first, void* workspace, size_t workspace_bytes, const scn_work_list* wl,
                                   void* stream) {
-    if (!c || !dz || !W || !W[0] || !W[1] || !W[2] || !aux || !y || !dW || !dW[0] || !dW[1] || !dW[2] || !dW_first ||
-        !dW_first[0] || !dW_first[1] || !dW_first[2] || !workspace || !valid_list(wl))
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < blocked_backward_first_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    return blocked_backward_first(c, n_slabs, dz, W, aux, channels, act, y, dW, dW_first, workspace, wl ? &wlist : nullptr,
-                                  (hipStream_t)stream);
+    if (!c || !dz || !all3(W) || !aux || !y || !all3(dW) || !all3(dW_first) || !workspace || !valid_list(wl)) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (ws_short(workspace_bytes, blocked_backward_first_workspace(c, n_slabs, ns, channels))) return SCN_ERR_WORKSPACE;
+    BwdFirstLaunch L{n_slabs, dz, W, channels, act, y, dW, dW_first, workspace, (hipStream_t)stream};
+    L.aux = aux;
+    L.wl = list_of(wl);
+    return blocked_backward_first(c, L);
 }
 
 int scn_conv_forward_first(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x, const float* const* W, int32_t c_out,
                            int32_t act, float* out, float* y_out, const scn_work_list* wl, void* stream) {
-    if (!c || !x || !W || !W[0] || !W[1] || !W[2] || !y_out || !valid_list(wl)) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (!c || !x || !all3(W) || !y_out || !valid_list(wl)) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
     if (!out && wl) return SCN_ERR_UNSUPPORTED;        // y only: dense launches
     const int32_t c_in = 1;
     if (c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, c_out)) return SCN_ERR_UNSUPPORTED;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    return blocked_forward(c, n_slabs, ns, &x, &c_in, W, c_out, act, out, y_out, wl ? &wlist : nullptr, (hipStream_t)stream);
+    FwdLaunch L{n_slabs, x, c_in, W, c_out, act, out, (hipStream_t)stream};
+    L.y_out = y_out;
+    L.wl = list_of(wl);
+    return blocked_forward(c, L);
 }
 
 int scn_conv_forward_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
                             const float* const* W, int32_t channels, int32_t act, float* out, void* stream) {
-    if (!c || !y || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !W || !W[0] || !W[1] || !W[2] || !out)
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream);
+    if (!c || !y || !all3(W_first) || !all3(W) || !out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    return blocked_forward_from_y(c, FromYLaunch{n_slabs, y, W_first, W, act, out, (hipStream_t)stream});
 }
 
 int scn_conv_forward_from_y_keep(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* y, const float* const* W_first,
@@ -654,33 +614,34 @@ int scn_conv_forward_from_y_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns
                                        const float* const* W, int32_t channels, int32_t act, float* out, const uint32_t* keep,
                                        const uint32_t* units, const uint32_t* unit_count, void* stream) {
     if ((units != nullptr) != (unit_count != nullptr) || (units && !keep)) return SCN_ERR_BAD_ARG;
-    if (!c || !y || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !W || !W[0] || !W[1] || !W[2] || !out)
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535 || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    return blocked_forward_from_y(c, n_slabs, y, W_first, W, act, out, (hipStream_t)stream, keep, units, unit_count);
+    if (!c || !y || !all3(W_first) || !all3(W) || !out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || !blocked_forward_from_y_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    FromYLaunch L{n_slabs, y, W_first, W, act, out, (hipStream_t)stream};
+    L.keep = keep;
+    L.units = units;
+    L.unit_count = unit_count;
+    return blocked_forward_from_y(c, L);
 }
 
 int scn_conv_backward_fused_first_from_y(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
                                          const float* const* W_first, int32_t channels, int32_t act, const float* y,
                                          float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
                                          const scn_work_list* wl, void* stream) {
-    if (!c || !dz || !W || !W[0] || !W[1] || !W[2] || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !y || !dW ||
-        !dW[0] || !dW[1] || !dW[2] || !dW_first || !dW_first[0] || !dW_first[1] || !dW_first[2] || !workspace || !valid_list(wl))
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535 || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < blocked_backward_first_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    return blocked_backward_first(c, n_slabs, dz, W, nullptr, channels, act, y, dW, dW_first, workspace, wl ? &wlist : nullptr,
-                                  (hipStream_t)stream, W_first);
+    if (!c || !dz || !all3(W) || !all3(W_first) || !y || !all3(dW) || !all3(dW_first) || !workspace || !valid_list(wl)) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (ws_short(workspace_bytes, blocked_backward_first_workspace(c, n_slabs, ns, channels))) return SCN_ERR_WORKSPACE;
+    BwdFirstLaunch L{n_slabs, dz, W, channels, act, y, dW, dW_first, workspace, (hipStream_t)stream};
+    L.W_first = W_first;
+    L.wl = list_of(wl);
+    return blocked_backward_first(c, L);
 }
 
 int scn_clear_list(scn_conv_t c, int32_t ns, int32_t channels, float* tensor, const scn_work_list* wl, void* stream) {
     if (!c || !tensor || !wl || !valid_list(wl) || channels <= 0) return SCN_ERR_BAD_ARG;
-    WorkList wlist = to_list(wl);
-    return blocked_clear_list(c, ns, channels, tensor, &wlist, (hipStream_t)stream);
+    const WorkList list = list_of(wl);
+    return blocked_clear_list(c, ns, channels, tensor, &list, (hipStream_t)stream);
 }
 
 int scn_clear_mask(scn_conv_t c, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream) {
@@ -708,43 +669,47 @@ int scn_conv_shifted_input_keep_units(scn_conv_t c, int32_t n_slabs, int32_t ns,
     if (!c || !x || !y_out || !keep || (units != nullptr) != (unit_count != nullptr)) return SCN_ERR_BAD_ARG;
     if (n_slabs <= 0) return SCN_ERR_BAD_SHAPE;
     const int32_t c_in = 1;
-    if (n_slabs > 65535 || c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, 32)) return SCN_ERR_UNSUPPORTED;
-    return blocked_shifted_input_keep(c, n_slabs, x, y_out, keep, (hipStream_t)stream, units, unit_count);
+    if (n_slabs > MAX_SLABS || c->n_groups != 1 || c->n_slots != 3 || !blocked_forward_supported(c, ns, &c_in, 32)) return SCN_ERR_UNSUPPORTED;
+    FwdLaunch L{n_slabs, x, c_in, /* W, c_out, act, out: the shifted input only */ nullptr, 0, SCN_ACT_NONE, nullptr, (hipStream_t)stream};
+    L.y_out = y_out;
+    L.keep = keep;
+    L.units = units;
+    L.unit_count = unit_count;
+    return blocked_shifted_input_keep(c, L);
 }
 
 int scn_conv_backward_visit(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
                             const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, float* const* dW,
                             void* workspace, size_t workspace_bytes, const uint32_t* visit, void* stream) {
     if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace || !visit) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
-    if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
-    for (int s = 0; s < c->n_slots; ++s)
-        if (!W[s] || !dW[s]) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
+    if (!dz[0] || c_dz[0] <= 0 || !per_slot(c, W) || !per_slot(c, dW)) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
-    return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
-                            (hipStream_t)stream, nullptr, nullptr, visit);
+    if (ws_short(workspace_bytes, scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux))) return SCN_ERR_WORKSPACE;
+    BwdLaunch L{n_slabs, dz[0], c_dz[0], W, aux, c_aux, act, dx, dW, workspace, (hipStream_t)stream};
+    L.visit = visit;
+    return blocked_backward(c, L);
 }
 
 int scn_conv_backward_fused_first_from_y_visit(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
                                                const float* const* W_first, int32_t channels, int32_t act, const float* y,
                                                float* const* dW, float* const* dW_first, void* workspace, size_t workspace_bytes,
                                                const uint32_t* visit, void* stream) {
-    if (!c || !dz || !W || !W[0] || !W[1] || !W[2] || !W_first || !W_first[0] || !W_first[1] || !W_first[2] || !y || !dW ||
-        !dW[0] || !dW[1] || !dW[2] || !dW_first || !dW_first[0] || !dW_first[1] || !dW_first[2] || !workspace || !visit)
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535 || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < blocked_backward_first_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
-    return blocked_backward_first(c, n_slabs, dz, W, nullptr, channels, act, y, dW, dW_first, workspace, nullptr, (hipStream_t)stream,
-                                  W_first, visit);
+    if (!c || !dz || !all3(W) || !all3(W_first) || !y || !all3(dW) || !all3(dW_first) || !workspace || !visit) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (ws_short(workspace_bytes, blocked_backward_first_workspace(c, n_slabs, ns, channels))) return SCN_ERR_WORKSPACE;
+    BwdFirstLaunch L{n_slabs, dz, W, channels, act, y, dW, dW_first, workspace, (hipStream_t)stream};
+    L.W_first = W_first;
+    L.visit = visit;
+    return blocked_backward_first(c, L);
 }
 
 int scn_conv_forward_power(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x0, const float* x,
                            const float* const* W, int32_t channels, int32_t act, float* out, void* stream) {
-    if (!c || !x0 || !x || !W || !W[0] || !W[1] || !W[2] || !out) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (!c || !x0 || !x || !all3(W) || !out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
     if (!blocked_power_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
     return blocked_power_forward(c, n_slabs, x0, x, W, channels, act, out, (hipStream_t)stream);
 }
@@ -758,11 +723,10 @@ size_t scn_conv_backward_power_workspace(scn_conv_t c, int32_t n_slabs, int32_t 
 int scn_conv_backward_power(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* g1,
                             const float* const* W, const float* aux, int32_t channels, int32_t act, float* dx,
                             float* const* dW, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!c || !dz || !g1 || !W || !W[0] || !W[1] || !W[2] || !aux || !dW || !dW[0] || !dW[1] || !dW[2] || !workspace)
-        return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (!c || !dz || !g1 || !all3(W) || !aux || !all3(dW) || !workspace) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
     if (!blocked_power_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < scn_conv_backward_power_workspace(c, n_slabs, ns, channels)) return SCN_ERR_WORKSPACE;
+    if (ws_short(workspace_bytes, scn_conv_backward_power_workspace(c, n_slabs, ns, channels))) return SCN_ERR_WORKSPACE;
     return blocked_power_backward(c, n_slabs, dz, g1, W, aux, channels, act, dx, dW, workspace, (hipStream_t)stream);
 }
 
@@ -777,12 +741,13 @@ int scn_conv_backward_accumulate(scn_conv_t c, int32_t n_slabs, int32_t ns, cons
                                  const float* const* W, const float* aux, int32_t c_aux, int32_t act, const float* dx_partial,
                                  float* dx, float* const* dW, void* workspace, size_t workspace_bytes, void* stream) {
     if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace || !dx || !dx_partial) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
     if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
-    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
-    return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
-                            (hipStream_t)stream, dx_partial);
+    if (ws_short(workspace_bytes, scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux))) return SCN_ERR_WORKSPACE;
+    BwdLaunch L{n_slabs, dz[0], c_dz[0], W, aux, c_aux, act, dx, dW, workspace, (hipStream_t)stream};
+    L.dx_partial = dx_partial;
+    return blocked_backward(c, L);
 }
 
 int scn_conv_backward_dzmask(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
@@ -791,16 +756,15 @@ int scn_conv_backward_dzmask(scn_conv_t c, int32_t n_slabs, int32_t ns, const fl
     if (!dzmask)
         return scn_conv_backward_list(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr, stream);
     if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
-    if (n_slabs > 65535) return SCN_ERR_UNSUPPORTED;
-    if (!dz[0] || c_dz[0] <= 0) return SCN_ERR_BAD_ARG;
-    for (int s = 0; s < c->n_slots; ++s)
-        if (!W[s] || !dW[s]) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
+    if (!dz[0] || c_dz[0] <= 0 || !per_slot(c, W) || !per_slot(c, dW)) return SCN_ERR_BAD_ARG;
     if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(dx) & 15) return SCN_ERR_UNSUPPORTED;           // (the zero tiles go out in 16-byte stores)
-    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
-    return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes, nullptr,
-                            (hipStream_t)stream, nullptr, dzmask);
+    if (ws_short(workspace_bytes, scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux))) return SCN_ERR_WORKSPACE;
+    BwdLaunch L{n_slabs, dz[0], c_dz[0], W, aux, c_aux, act, dx, dW, workspace, (hipStream_t)stream};
+    L.dzmask = dzmask;
+    return blocked_backward(c, L);
 }
 
 int scn_conv_backward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
@@ -808,16 +772,16 @@ int scn_conv_backward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const floa
                            float* const* dW, void* workspace, size_t workspace_bytes, const scn_work_list* wl,
                            void* stream) {
     if (!c || !dz || !c_dz || !W || !aux || !dW || !workspace || !valid_list(wl)) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || act < 0 || act > 3) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
     for (int g = 0; g < c->n_groups; ++g)
         if (!dz[g] || c_dz[g] <= 0) return SCN_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (workspace_bytes < scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux)) return SCN_ERR_WORKSPACE;
-    WorkList wlist{0, nullptr, nullptr, nullptr};
-    if (wl) wlist = to_list(wl);
-    if (blocked_backward_supported(c, ns, c_dz, c_aux))
-        return blocked_backward(c, n_slabs, ns, dz, c_dz, W, aux, c_aux, act, dx, dW, workspace, workspace_bytes,
-                                wl ? &wlist : nullptr, st);
+    if (ws_short(workspace_bytes, scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux))) return SCN_ERR_WORKSPACE;
+    if (blocked_backward_supported(c, ns, c_dz, c_aux)) {
+        BwdLaunch L{n_slabs, dz[0], c_dz[0], W, aux, c_aux, act, dx, dW, workspace, st};
+        L.wl = list_of(wl);
+        return blocked_backward(c, L);
+    }
     if (wl) return SCN_ERR_UNSUPPORTED;
 
     BwdArgs a;
@@ -853,7 +817,7 @@ int scn_conv_backward_list(scn_conv_t c, int32_t n_slabs, int32_t ns, const floa
 
 int scn_spmm_dual(scn_conv_t c, int32_t n_slabs, int32_t k, const float* x, float* ya, float* yb, void* stream) {
     if (!c || !x || !ya) return SCN_ERR_BAD_ARG;
-    if (n_slabs <= 0 || k <= 0 || n_slabs > 65535) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs <= 0 || k <= 0 || n_slabs > MAX_SLABS) return SCN_ERR_BAD_SHAPE;
     const Group& G = c->g[0];
     if (G.n_vals < 1 || (yb && G.n_vals < 2)) return SCN_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;

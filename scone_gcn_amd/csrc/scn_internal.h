@@ -274,4 +274,105 @@ struct scn_conv_s {
 
 namespace scn {
 int small_prepare(scn_conv_s* c);      // scn_small.hip: the entry pack + LDS limit of scn_small_step, at create time
+
+// ---- scn_blocked.hip as scn_conv.hip calls it: the ONE declaration of each ----
+constexpr WorkList NO_LIST{0, nullptr, nullptr, nullptr};
+
+// What a launch of a fused layer kernel is given, one record per family.  The leading fields are what every launch of the family has
+// (aggregate-initialised, in this order); the ones with a default are options, absent unless a call site sets them BY NAME.
+struct FwdLaunch {                          // blocked_forward (and blocked_shifted_input_keep: src, y_out, keep, units)
+    int n_slabs;
+    const float* src;                       // the layer's input, c_in channels
+    int c_in;
+    const float* const* W;
+    int c_out, act;
+    float* out;                             // null (c_in = 1): the first layer's shifted input only, into y_out
+    hipStream_t st;
+    float* y_out = nullptr;                 // c_in = 1: the shifted-input records, beside out
+    WorkList wl = NO_LIST;                  // zero-skipping work list
+    const float* partial = nullptr;         // 32 -> 32: out = act(partial + ...), see fwd_c32_w16_kernel
+    const uint32_t* keep = nullptr;         // 32 -> 32 and 16 -> 16, dense, no partial: only the mask's items are stored (32 -> 32: visited)
+    const uint32_t* units = nullptr;        // the mask's unit list and its count (32 -> 32 and the shifted input; unit_list_of)
+    const uint32_t* unit_count = nullptr;
+};
+struct FromYLaunch {                        // blocked_forward_from_y: 32 channels, dense
+    int n_slabs;
+    const float* y;                         // the first layer's shifted-input records
+    const float* const* W_first;
+    const float* const* W;
+    int act;
+    float* out;
+    hipStream_t st;
+    const uint32_t* keep = nullptr;         // visits and stores by the mask, as FwdLaunch
+    const uint32_t* units = nullptr;
+    const uint32_t* unit_count = nullptr;
+};
+struct BwdLaunch {                          // blocked_backward
+    int n_slabs;
+    const float* dz;
+    int c_dz;
+    const float* const* W;
+    const float* aux;
+    int c_aux, act;
+    float* dx;                              // null: weight gradients only
+    float* const* dW;
+    void* ws;                               // blocked_backward_workspace bytes
+    hipStream_t st;
+    WorkList wl = NO_LIST;
+    const float* dx_partial = nullptr;      // 32 -> 32: dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
+    const uint32_t* dzmask = nullptr;       // 32 -> 32, dense, no partial: dz is staged by the source mask, see there
+    const uint32_t* visit = nullptr;        // the same shapes, no dzmask: only the mask's items are visited, see there
+};
+struct BwdFirstLaunch {                     // blocked_backward_first: the layer behind the first one, fused with dW_first
+    int n_slabs;
+    const float* dz;
+    const float* const* W;
+    int ch, act;
+    const float* y;                         // the first layer's shifted-input records
+    float* const* dW;
+    float* const* dW_first;
+    void* ws;                               // blocked_backward_first_workspace bytes
+    hipStream_t st;
+    const float* aux = nullptr;             // the first layer's output; absent with W_first
+    const float* const* W_first = nullptr;  // 32 channels: aux is rebuilt from y, not read
+    WorkList wl = NO_LIST;
+    const uint32_t* visit = nullptr;        // with W_first, dense: only the mask's items are visited
+};
+
+int build_block_plan(scn_conv_s* c);
+void free_block_plan(scn_conv_s* c);
+bool blocked_forward_supported(const scn_conv_s* c, int ns, const int32_t* c_in, int c_out);
+int blocked_forward(scn_conv_s* c, const FwdLaunch& a);
+int blocked_shifted_input_keep(scn_conv_s* c, const FwdLaunch& a);
+bool blocked_forward_from_y_supported(const scn_conv_s* c, int ns, int ch);
+int blocked_forward_from_y(scn_conv_s* c, const FromYLaunch& a);
+bool blocked_backward_supported(const scn_conv_s* c, int ns, const int32_t* c_dz, int c_aux);
+size_t blocked_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, const int32_t* c_dz, int c_aux);
+int blocked_backward(scn_conv_s* c, const BwdLaunch& a);
+bool blocked_backward_first_supported(const scn_conv_s* c, int ns, int ch);
+size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
+int blocked_backward_first(scn_conv_s* c, const BwdFirstLaunch& a);
+bool blocked_power_supported(const scn_conv_s* c, int ns, int ch);
+size_t blocked_power_backward_workspace(const scn_conv_s* c, int n_slabs, int ns, int ch);
+int blocked_power_forward(scn_conv_s* c, int n_slabs, const float* x0, const float* x, const float* const* W, int ch, int act,
+                          float* out, hipStream_t st);
+int blocked_power_backward(scn_conv_s* c, int n_slabs, const float* dz, const float* g1, const float* const* W,
+                           const float* aux, int ch, int act, float* dx, float* const* dW, void* ws, hipStream_t st);
+bool blocked_dw_first_supported(const scn_conv_s* c, int ns, int cd);
+size_t blocked_dw_first_workspace(const scn_conv_s* c, int n_slabs, int ns, int cd);
+int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y, const float* dz, int cd,
+                     float* const* dW, void* ws, const WorkList* wl, hipStream_t st);
+int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* wl, hipStream_t st);
+int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st);
+bool blocked_spmm_supported(const scn_conv_s* c, int k);
+int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st);
+int blocked_window_scan_probe(scn_conv_s* c, int n_slabs, const uint32_t* mask, int gx, int slab0, int n_it, int cap, int32_t* out_block,
+                              uint64_t* out_window, int32_t* out_count, int32_t* unit_block, hipStream_t st);
+int build_terms_plan(scn_conv_s* c, const uint8_t* term, const int32_t* lvl_row0, const uint8_t* merged, const int32_t* bins,
+                     int group_rows);
+int terms_forward(scn_conv_s* c, int n_slabs, const float* const* x, const float* const* W, int act, float* const* out,
+                  hipStream_t st);
+size_t terms_backward_workspace(const scn_conv_s* c, int n_slabs);
+int terms_backward(scn_conv_s* c, int n_slabs, const float* const* dz, const float* const* W, const float* const* aux, int act,
+                   float* const* dx, float* const* dW, const float* const* y, float* const* dW_first, void* ws, hipStream_t st);
 }

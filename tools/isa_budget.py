@@ -4,7 +4,11 @@
 itemised next to the PMC totals (profiles/r03_isa_budget_*.txt).
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Iscone_gcn_amd/csrc --cuda-device-only -S scone_gcn_amd/csrc/scn_blocked.hip -o /tmp/scn_blocked.s
-    python tools/isa_budget.py /tmp/scn_blocked.s fwd_c32_w16_kernelILi1ELb0
+    python tools/isa_budget.py /tmp/scn_blocked.s fwd_c32_w16_kernelILi1ELj0E
+
+The second argument is a piece of the kernel's mangled name: ILi<ACT>E is the activation (SCN_ACT_*: 1 = tanh), Lj<FORM>E the form, the
+decimal value of its FWD_* / BWD_* bits (scn_blk_fwd.inc, scn_blk_bwd.inc: Lj0E is the plain form, bwd_c32_bf16_kernelILi1ELj84E the
+fused-first from-y visiting backward).  tools/isa_forms_diff.py compares every form of the fused layer kernels between two such files.
 """
 import collections
 import re
