@@ -400,6 +400,13 @@ int scn_conv_shifted_input_keep(scn_conv_t conv, int32_t n_slabs, int32_t ns, co
  * whole process (on != 0: on, the default; 0: every unit starts with its full prologue; negative: no change), and returns the setting
  * before the call.  Outputs are bit for bit the same either way: a switch for tests and A/B runs. */
 int scn_conv_visit_prefetch(int32_t on);
+/* With the pipeline on, a unit's top also takes the block's header, its tile widths and the next unit's source range from a packed
+ * 32-byte record per block, which the workgroup's window scan has left in LDS for its first 64 live entries (an entry past them: one
+ * 32-byte load), and issues all of its loads under one wait (csrc/scn_blk_record.h, csrc/scn_blk_bwd.inc).  scn_conv_visit_records
+ * sets that in the same way (on != 0: on, the default; 0: the header from the plan's separate arrays; negative: no change) and
+ * returns the setting before the call.  Outputs are bit for bit the same either way. */
+int scn_conv_visit_records(int32_t on);
+int scn_conv_visit_records_cap(void);   /* the table's entries per scan (64) */
 int scn_clear_mask(scn_conv_t conv, int32_t n_slabs, int32_t ns, int32_t channels, float* tensor, const uint32_t* mask, void* stream);
 
 /* Unit lists.  A masked launch hands every workgroup a FIXED share of the plan's blocks, and the launch ends with its busiest

@@ -147,6 +147,8 @@ SIGNATURES = {
     "scn_conv_shifted_input_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                          c_void_p]),
     "scn_conv_visit_prefetch": (ctypes.c_int, [c_i32]),
+    "scn_conv_visit_records": (ctypes.c_int, [c_i32]),
+    "scn_conv_visit_records_cap": (ctypes.c_int, []),
     "scn_window_scan_probe": (ctypes.c_int, [c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
     "scn_terms_create": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,

@@ -56,7 +56,8 @@ static_assert(B32_EXTRA_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 1
 
 // FORM: the kernel's form, an OR of the BWD_* bits below; the kernel's first lines name them and assert which combinations exist.
 // What DZ0 carries depends on the form, and has ONE name each (top of the kernel): dz_own (EXT0), dx_partial (ACCUM), y_rec (FIRST);
-// it is null in every other form.  A mask (DZMASK's source mask, VISIT's visit mask) comes typed, in `km`, and the launch's flags in `flags`.
+// it is null in every other form.  A mask (DZMASK's source mask, VISIT's visit mask) comes typed, in `km`, the launch's flags in `flags`, and the plan's
+// packed block records (VISIT; null elsewhere) in `recs`.
 // EXT0 (see fwd_c32_w16_kernel): segment 0 of G is the upstream gradient itself (DZ0, own rows from HBM), the staged tensor
 // DZ is S^T dz: segment 1 its own row, segment 2 its gathered shift (S^T)^2 dz.  Composes with PAIR (Ebli at hidden 16).
 // PAIR: C = 16 on TWO slabs per visit -- the staged 512-byte piece is a point's 32 VIRTUAL channels (slab A's 16, slab B's 16:
@@ -154,8 +155,19 @@ __device__ __forceinline__ void first_aux_tile(std::integer_sequence<int, Rs...>
 #ifndef SCN_VISIT_PREFETCH
 #define SCN_VISIT_PREFETCH 1
 #endif
-constexpr int VISIT_FLAG_PREFETCH = 1;
+// PACKED RECORDS at the unit's top (VISIT_FLAG_RECORDS, on top of the unit pipeline).  The pipeline left a unit's top with two dependent
+// trips: the header scalars (five arrays, a cold line each) and then the metadata they address; and the two tile-width bytes were
+// loaded again behind the __syncthreads().  The window scan knows a unit's block one trip before the unit starts, so it also fetches
+// the blocks' 32-byte records (scn_blk_record.h) into an LDS table behind the second source-row buffer (scn_window_scan.inc).  A unit's
+// top then reads header, tile widths and the NEXT unit's source range as uniform LDS reads made scalar, and issues everything else
+// (own rows unless staged, next rows, ELL tile, self slots) under one wait ahead of the __syncthreads() (load_block_c32_rec); nothing
+// is loaded behind it.  The same blocks, rows and widths as from the separate arrays: no visit, order or arithmetic changes.  A launch
+// without the flag (scn_conv_visit_records) takes the loop above as it was.
+// (Touching the next unit's ELL lines ahead, from its record, during a unit's first visit was built and measured: it COST the two
+// launches 4.7 and 1.3 us, profiles/visit_records_ab.txt section 2.)
+constexpr int VISIT_FLAG_PREFETCH = 1, VISIT_FLAG_RECORDS = 2;
 constexpr int VISIT_ROWS_BYTES = BK_SRC * 4;                  // the second source-row buffer: dynamic LDS of the VISIT launches, behind the scan table
+static_assert((WSCAN_LDS_BYTES + VISIT_ROWS_BYTES) % 16 == 0, "the record table (WSCAN_HDR_BYTES behind the row buffer) starts 16-byte aligned");
 static_assert(WSCAN_LDS_BYTES % 16 == 0, "the second source-row buffer starts 16-byte aligned");
 enum : unsigned { BWD_EXT0 = 1, BWD_PAIR = 2, BWD_FIRST = 4, BWD_ACCUM = 8, BWD_FROMY = 16, BWD_DZMASK = 32, BWD_VISIT = 64 };
 template <int ACT, unsigned FORM = 0>
@@ -168,7 +180,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
                                                                      float* __restrict__ dx, float* __restrict__ partial,
                                                                      int n_rows, int n_cols, int n_slabs, WorkList wl,
                                                                      float* __restrict__ partial_first, FirstW fw, KeepMask km,
-                                                                     int flags) {
+                                                                     int flags, const BlockRec* __restrict__ recs) {
     constexpr bool EXT0 = (FORM & BWD_EXT0) != 0, PAIR = (FORM & BWD_PAIR) != 0, FIRST = (FORM & BWD_FIRST) != 0, ACCUM = (FORM & BWD_ACCUM) != 0,
                    FROMY = (FORM & BWD_FROMY) != 0, DZMASK = (FORM & BWD_DZMASK) != 0, VISIT = (FORM & BWD_VISIT) != 0;
     static_assert(!FROMY || (FIRST && !PAIR), "the aux-free form exists for the fused-first C = 32 kernel");
@@ -244,8 +256,11 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     int e_run = 1 << 20;                                      // running exponent of the dW accumulators (see the header): none yet
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     SCN_UNIT_RANGE();
-    SCN_WINDOW_WALK(VISIT, km, smem + smem_bytes_c32(B32_EXTRA_BYTES),
-                    (UnitList{nullptr, nullptr}));   // (dW is summed in visit order: the backward keeps its static units)
+    // RECORDS (the VISIT forms with the unit pipeline on; see the header): the walk's scans also fill the record table
+    const bool rec_on = VISIT && SCN_VISIT_PREFETCH != 0 && !listed && (flags & (VISIT_FLAG_PREFETCH | VISIT_FLAG_RECORDS)) == (VISIT_FLAG_PREFETCH | VISIT_FLAG_RECORDS);
+    SCN_WINDOW_WALK_RECS(VISIT, km, smem + smem_bytes_c32(B32_EXTRA_BYTES),
+                         (UnitList{nullptr, nullptr}),   // (dW is summed in visit order: the backward keeps its static units)
+                         VISIT && rec_on ? recs : nullptr, smem + smem_bytes_c32(B32_EXTRA_BYTES) + WSCAN_LDS_BYTES + VISIT_ROWS_BYTES);
     uint32_t cqs[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) cqs[q] = (uint32_t)((n * 8 + h * 4 + q) ^ (n >> 1)) << 4;
@@ -280,9 +295,19 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
         int n_next = 0, tw_p = 0, twu_p = 0;
         wait_all_and_barrier();
         STAMP_UADD(0);
-        const BlockMeta m = PIPE && pipe_on ? load_block_c32_ahead<BK_THREADS>(P, b, sm, sm.srcrows + sr_cur, staged, has_next, nb, sm.srcrows + sr_next,
-                                                                               n_next, wave, tw_p, twu_p)
-                                            : load_block_c32<BK_THREADS>(P, b, sm);
+        BlockMeta m;
+        if (VISIT && rec_on) {                                   // the header from the unit's record, the next unit's source range from ITS record
+            uint32_t rw[8], nw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            walk_.record(u_, b, rw);
+            if (has_next) walk_.record(u_ + 1, nb, nw);
+            n_next = (int)(nw[3] & 255u);
+            m = load_block_c32_rec<BK_THREADS>(P, b, rw, sm, sm.srcrows + sr_cur, staged, has_next, (int)nw[2], n_next, sm.srcrows + sr_next, wave, tw_p,
+                                               twu_p);
+        } else if (PIPE && pipe_on) {
+            m = load_block_c32_ahead<BK_THREADS>(P, b, sm, sm.srcrows + sr_cur, staged, has_next, nb, sm.srcrows + sr_next, n_next, wave, tw_p, twu_p);
+        } else {
+            m = load_block_c32<BK_THREADS>(P, b, sm);
+        }
         // DZMASK: bit v = the slab k0 + v of visit v has a source to stage in this block (all ones under a NaN / Inf weight)
         const uint64_t dzm = DZMASK ? (keep_window(km, b, k0) | (w_bad ? ~0ull : 0ull)) : ~0ull;
         __syncthreads();
@@ -701,7 +726,7 @@ __global__ __launch_bounds__(BK_THREADS, 2) void bwd_c32_bf16_kernel(PlanDev P, 
     if (VISIT) { STAMP_FLUSH_WG(); }
 }
 
-// The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so partial_first, fw, km and flags are always passed).  The
+// The forms of bwd_c32_bf16_kernel by name (one function-pointer type, so partial_first, fw, km, flags and recs are always passed).  The
 // static_asserts inside the kernel say which combinations exist; what DZ, DZ0, aux, fw and km carry in each (null where not named):
 template <int ACT> constexpr auto bwd_c32_plain = bwd_c32_bf16_kernel<ACT>;                                              // DZ = dz
 template <int ACT> constexpr auto bwd_c32_pair = bwd_c32_bf16_kernel<ACT, BWD_PAIR>;                                     // the same at C = 16, on slab pairs

@@ -156,6 +156,54 @@ __device__ __forceinline__ BlockMeta load_block_c32_ahead(const PlanDev& P, int 
     return m;
 }
 
+// load_block_c32_ahead with the header taken from the block's packed record (scn_blk_record.h): rw = its eight words, already in
+// SGPRs (WindowWalk::record), and np0 / n_next = the next unit's source range from ITS record -- so nothing here depends on a trip to
+// memory, and every load of the unit's top (own rows unless have_rows, the next unit's rows, the ELL tile in up to three pieces per
+// thread, the self slots) is issued before the first of them is used: one waited batch ahead of the caller's __syncthreads(), and the
+// wave's tile widths come out of the record's words, so nothing is loaded behind it.
+template <int NT>
+__device__ __forceinline__ BlockMeta load_block_c32_rec(const PlanDev& P, int b, const uint32_t (&rw)[8], const SmemC32& sm, int32_t* rows_cur,
+                                                        bool have_rows, bool ahead, int np0, int n_next, int32_t* rows_next, int wave, int& tw,
+                                                        int& twu) {
+    static_assert(BK_SRC <= NT, "a block's source rows: one per thread");
+    static_assert((BK_R & (BK_R - 1)) == 0, "t & (BK_R - 1) below");
+    constexpr int NE = (BK_ELL_CAP + NT - 1) / NT;                // ELL entries per thread
+    BlockMeta m;
+    m.row0 = (int)rw[0];
+    const int ep = (int)rw[1], sp0 = (int)rw[2];
+    m.nsrc = (int)(rw[3] & 255u);
+    m.rows = (int)(rw[3] >> 8 & 255u);
+    m.w = (int)(rw[3] >> 16 & 255u);
+    tw = (int)(rw[4 + (wave >> 2)] >> (8 * (wave & 3)) & 255u);
+    twu = (int)(rw[6 + (wave >> 2)] >> (8 * (wave & 3)) & 255u);
+    const int t = threadIdx.x, ne = m.w * m.rows;
+    const bool l0 = !have_rows && t < m.nsrc, l1 = ahead && t < n_next;
+    // every load is unconditional -- a thread without an element reads element 0 of the array (every plan array has one) and drops
+    // it -- so that no branch and no merge of a loaded value stands between two loads: predicated, hipcc 7.2 waited for each ELL
+    // piece's slots before requesting the next piece
+    uint16_t enc[NE];
+    float2 v[NE];
+    const int32_t r0 = P.src_rows[l0 ? sp0 + t : 0], r1 = P.src_rows[l1 ? np0 + t : 0];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+        const int i = t + j * NT < ne ? ep + t + j * NT : 0;
+        enc[j] = P.ell_enc[i];
+        v[j] = P.ell_v[i];
+    }
+    const uint8_t self = P.self_slot[(size_t)b * BK_R + (t & (BK_R - 1))];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NE; ++j)
+        if (t + j * NT < ne) {
+            sm.enc[t + j * NT] = enc[j];
+            sm.v[t + j * NT] = v[j];
+        }
+    if (t < BK_R) sm.self[t] = self;
+    if (l0) rows_cur[t] = r0;
+    if (l1) rows_next[t] = r1;
+    return m;
+}
+
 // Gather of one lane's NQ 16-byte chunks of row `row` from the staged 512-byte pieces: identity term gs, and the ELL row
 // (entry pairs) accumulated into gl (val0 operator) and gu (val1 operator).
 //  * cb[q] = (this lane's swizzled chunk index << 4) | (buffer index << 16); the LDS address of a chunk is cb[q] ^ enc with
@@ -358,6 +406,9 @@ __device__ __forceinline__ void block_range(int n_blocks, int& first, int& last,
 // done) and a form without a mask nothing.  SCN_WINDOW_WALK declares the walk, once, behind SCN_UNIT_RANGE(); UL: the mask's unit list
 // (the forward-side launches; WindowWalk's list mode) or an empty one.
 #define SCN_WINDOW_WALK(MASKED, KM, LDS, UL) WindowWalk walk_((MASKED), (LDS), P.n_blocks, P.assign, (KM), slab0, slab1 - slab0, (UL))
+// (the visiting backwards: RECS / HDR = the plan's packed records and the LDS record table the scans fill, or null -- WindowWalk::record)
+#define SCN_WINDOW_WALK_RECS(MASKED, KM, LDS, UL, RECS, HDR) \
+    WindowWalk walk_((MASKED), (LDS), P.n_blocks, P.assign, (KM), slab0, slab1 - slab0, (UL), (RECS), (HDR))
 #define SCN_UNIT_BEGIN_MASKED(MASKED)                                                \
     scn_next_units_:                                                                 \
     if (MASKED) walk_.scan_units(u_, u_end_, u_stride_);                             \

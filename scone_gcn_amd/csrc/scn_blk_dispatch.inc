@@ -88,12 +88,14 @@ static_assert(W16_EXTRA_BYTES + W16_FIRSTW_BYTES + WSCAN_LDS_BYTES <= 160 * 1024
               B32_EXTRA_BYTES + WSCAN_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
               "the scan's table fits behind the kernels' own LDS");
 // The VISIT backwards take VISIT_ROWS_BYTES more behind the table (the unit pipeline's second source-row buffer, scn_blk_bwd.inc).
-// Their `flags` argument carries the process-wide switch g_visit_prefetch (scn_conv_visit_prefetch).
-constexpr size_t VISIT_LDS_BYTES = WSCAN_LDS_BYTES + VISIT_ROWS_BYTES;
+// and WSCAN_HDR_BYTES behind that (the record table of their scans, scn_window_scan.inc): 163 216 of the CU's 163 840 bytes.
+// Their `flags` argument carries the process-wide switches g_visit_prefetch (scn_conv_visit_prefetch) and g_visit_records
+// (scn_conv_visit_records; it acts where the pipeline is on).
+constexpr size_t VISIT_LDS_BYTES = WSCAN_LDS_BYTES + VISIT_ROWS_BYTES + WSCAN_HDR_BYTES;
 static_assert(B32_EXTRA_BYTES + VISIT_LDS_BYTES <= 160 * 1024 - (2 * BK_SRC * 512 + BK_ELL_CAP * 10 + BK_SRC * 4 + BK_R + 16),
-              "the scan's table and the second source-row buffer fit behind the backward's own LDS");
-static int g_visit_prefetch = 1;
-static int visit_flags() { return g_visit_prefetch ? VISIT_FLAG_PREFETCH : 0; }
+              "the scan's table, the second source-row buffer and the record table fit behind the backward's own LDS");
+static int g_visit_prefetch = 1, g_visit_records = 1;
+static int visit_flags() { return (g_visit_prefetch ? VISIT_FLAG_PREFETCH : 0) | (g_visit_records ? VISIT_FLAG_RECORDS : 0); }
 
 // The keep mask of a launch (scn_conv_forward_keep / _from_y_keep; the source mask of scn_conv_backward_dzmask has its geometry and
 // its window limit): words per block from the slab count.  A workgroup holds the bits
@@ -250,10 +252,10 @@ int blocked_backward(scn_conv_s* c, const BwdLaunch& a) {
         if (mask)
             return launch_checked(a.dzmask ? bwd_c32_plain_dzmask<ACT> : bwd_c32_plain_visit<ACT>, L.grid, dim3(BK_THREADS),
                                   lds + (a.dzmask ? 0 : VISIT_LDS_BYTES), a.st, L.P, a.dz, nullptr, W[0], W[1], W[2], a.aux, a.dx, partial, L.nr, L.nc,
-                                  n_slabs, wl, nullptr, NO_FIRSTW, keep_mask_of(mask, n_slabs), a.dzmask ? 0 : visit_flags());
+                                  n_slabs, wl, nullptr, NO_FIRSTW, keep_mask_of(mask, n_slabs), a.dzmask ? 0 : visit_flags(), a.dzmask ? nullptr : c->plan.blk_rec);
         const auto k = c_aux != 32 ? bwd_c32_pair<ACT> : (a.dx_partial ? bwd_c32_accum<ACT> : bwd_c32_plain<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.dx_partial, W[0], W[1], W[2], a.aux, a.dx, partial, L.nr, L.nc,
-                              n_slabs, wl, nullptr, NO_FIRSTW, NO_KEEP, 0);
+                              n_slabs, wl, nullptr, NO_FIRSTW, NO_KEEP, 0, nullptr);
     });
     return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), c_aux, cd, a.dW, a.st);
 }
@@ -301,10 +303,10 @@ int blocked_backward_first(scn_conv_s* c, const BwdFirstLaunch& a) {
         constexpr int ACT = decltype(A)::value;
         if (a.visit)
             return launch_checked(bwd_c32_first_from_y_visit<ACT>, L.grid, dim3(BK_THREADS), lds + VISIT_LDS_BYTES, a.st, L.P, a.dz, a.y, W[0], W[1], W[2],
-                                  nullptr, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw, keep_mask_of(a.visit, n_slabs), visit_flags());
+                                  nullptr, nullptr, partial, L.nr, L.nc, n_slabs, wl, partial_first, fw, keep_mask_of(a.visit, n_slabs), visit_flags(), c->plan.blk_rec);
         const auto k = a.W_first ? bwd_c32_first_from_y<ACT> : (ch == 32 ? bwd_c32_first<ACT> : bwd_c32_first_pair<ACT>);
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.y, W[0], W[1], W[2], a.W_first ? nullptr : a.aux, nullptr, partial,
-                              L.nr, L.nc, n_slabs, wl, partial_first, fw, NO_KEEP, 0);
+                              L.nr, L.nc, n_slabs, wl, partial_first, fw, NO_KEEP, 0, nullptr);
     });
     if (st_k == SCN_OK) st_k = reduce_dw(partial, n_wg, ch, ch, a.dW, a.st);
     if (st_k != SCN_OK) return st_k;
@@ -429,7 +431,7 @@ int blocked_power_backward(scn_conv_s* c, int n_slabs, const float* dz, const fl
     const int st_k = with_act(act, [&](auto A) -> int {
         constexpr int ACT = decltype(A)::value;
         return launch_checked(ch == 32 ? bwd_c32_power<ACT> : bwd_c32_power_pair<ACT>, L.grid, dim3(BK_THREADS), lds, st, L.P, g1, dz, W[0],
-                              W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, NO_LIST, nullptr, NO_FIRSTW, NO_KEEP, 0);
+                              W[1], W[2], aux, dx, partial, L.nr, L.nc, n_slabs, NO_LIST, nullptr, NO_FIRSTW, NO_KEEP, 0, nullptr);
     });
     return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), ch, ch, dW, st);
 }

@@ -14,7 +14,6 @@
 // half, scaling included) and three -- the fused kernels were bound by exactly those two instruction streams (profiles/HISTORY.md section 3.2).
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
 

@@ -188,6 +188,13 @@ int build_block_plan(scn_conv_s* c) {
     if ((st = upload(c, ell_enc, &P.dev.ell_enc)) != SCN_OK) return st;
     if ((st = upload(c, ell_v, &P.dev.ell_v)) != SCN_OK) return st;
     if ((st = upload(c, self_slot, &P.dev.self_slot)) != SCN_OK) return st;
+    {   // the packed records of the visiting backwards' unit top, from the arrays above (which stay: every other kernel reads them)
+        std::vector<BlockRec> rec(bid);
+        if (!pack_block_records(bid, blk_row0.data(), blk_rows.data(), src_ptr.data(), ell_ptr.data(), width.data(), tile_w.data(), tile_wu.data(),
+                                rec.data()))
+            return SCN_ERR_INTERNAL;
+        if ((st = upload(c, rec, &P.blk_rec)) != SCN_OK) return st;   // (hipMalloc: 256-byte aligned)
+    }
     P.mean_src_per_row = (double)total_src / std::max(1, n_rows);
     P.gather_positions = sim_positions;
     P.gather_cycles = sim_cycles;

@@ -34,6 +34,7 @@ namespace scn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- diagnostic build only (-DSCN_STAMPS): per-segment cycle sums of fwd_c32, never compiled into the product
 #ifdef SCN_STAMPS
@@ -101,6 +102,16 @@ __device__ unsigned long long g_stamps_wg[STAMP_WG_CAP][8][STAMP_WG_WORDS];
 extern "C" int scn_conv_visit_prefetch(int32_t on) {
     const int was = scn::g_visit_prefetch;
     if (on >= 0) scn::g_visit_prefetch = on != 0;
+    return was;
+}
+
+// The packed block records at the unit's top of the visiting backwards (scn_blk_bwd.inc), in the same way: on != 0 / 0 sets the switch
+// for the launches that follow, a negative value only asks; returns the setting before the call.  It acts where the unit pipeline is
+// on.  Every output bit is the same either way.
+extern "C" int scn_conv_visit_records_cap(void) { return scn::WSCAN_HDR_CAP; }   // live entries per scan whose records the LDS table holds
+extern "C" int scn_conv_visit_records(int32_t on) {
+    const int was = scn::g_visit_records;
+    if (on >= 0) scn::g_visit_records = on != 0;
     return was;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "scone_hip.h"
+#include "scn_blk_record.h"
 
 namespace scn {
 
@@ -209,6 +210,7 @@ struct PlanDev {
     const float2* ell_v;        // (val0, val1) of entry
     const uint8_t* self_slot;   // [n_blocks][BK_R] slot of the row itself (identity shift)
 };
+static_assert(BLK_REC_WAVES == BK_WAVES, "a record carries the tile widths of the 8-wave kernels");
 
 // optional (block, slab) work list of the zero-skipping mode (scn_work_list); block == nullptr: every block, every slab
 struct WorkList {
@@ -247,6 +249,8 @@ struct TermsPlan {
 struct BlockPlan {
     bool built = false;
     PlanDev dev{};
+    const BlockRec* blk_rec = nullptr;   // [n_blocks] the header fields of `dev` and tile_w / tile_wu, packed: 32 bytes per block (scn_blk_record.h);
+                                         // not part of PlanDev: only the visiting backwards read it, as a kernel argument of their own
     double mean_src_per_row = 0.0;
     int64_t gather_positions = 0, gather_cycles = 0;   // simulated lane-group reads of one gather pass and their LDS cycles (scn_blk_layout.inc)
     std::vector<int32_t> h_row0;   // first row of every block (+ n_rows): scn_conv_plan_blocks

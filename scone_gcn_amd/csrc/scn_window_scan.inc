@@ -28,6 +28,14 @@
 // ------------------------------------------------------------------------------------------------
 constexpr int WSCAN_CHUNK = 64, WSCAN_CHUNKS = 4, WSCAN_CAP = WSCAN_CHUNK * WSCAN_CHUNKS;
 constexpr int WSCAN_LDS_BYTES = 16 + WSCAN_CAP * 12;        // [count, 3 pad words][block][window lo][window hi]
+// RECORD TABLE (the visiting backwards with their records switch on; scn_blk_bwd.inc).  A unit's top used to read the block's header
+// from five arrays -- a trip to memory that depends on the table's block index and that everything else of the top depends on.  The
+// scan knows the blocks one trip earlier: with `recs` set, wave 0 also loads the packed records (scn_blk_record.h) of the scan's first
+// WSCAN_HDR_CAP live entries, all loads issued together, into a second LDS table `hdr` (eight words per entry) -- one more round trip
+// per SCAN, none per unit.  An entry past the cap reads its record from global memory at the unit's top (record()).  `recs` is a
+// compile-time null in every other kernel, which then carries none of this.
+constexpr int WSCAN_HDR_CAP = WSCAN_CHUNK, WSCAN_HDR_BYTES = WSCAN_HDR_CAP * 32;
+static_assert(sizeof(BlockRec) == 32, "eight words per record");
 
 // the bits of block b for the 64 slabs from `first` on (bit j = slab first + j), per lane: three loads, no branch (words past the
 // row: no slab)
@@ -53,9 +61,12 @@ struct WindowWalk {
     KeepMask km;
     UnitList ul;
     int n_blocks, slab0, n_it, scans;
+    const BlockRec* recs;                                             // the plan's packed records: the scan fills `hdr` (null: no record table)
+    uint32_t* hdr;                                                    // LDS, WSCAN_HDR_BYTES, 16-byte aligned
     __device__ __forceinline__ WindowWalk(bool on, char* lds, int n_blocks_, const int32_t* assign_, KeepMask km_, int slab0_, int n_it_,
-                                          UnitList ul_ = UnitList{nullptr, nullptr})
-        : tbl((uint32_t*)lds), assign(assign_), km(km_), ul(ul_), n_blocks(on ? n_blocks_ : 0), slab0(slab0_), n_it(n_it_), scans(0) {}
+                                          UnitList ul_ = UnitList{nullptr, nullptr}, const BlockRec* recs_ = nullptr, char* hdr_ = nullptr)
+        : tbl((uint32_t*)lds), assign(assign_), km(km_), ul(ul_), n_blocks(on ? n_blocks_ : 0), slab0(slab0_), n_it(n_it_), scans(0),
+          recs(recs_), hdr((uint32_t*)hdr_) {}
     // wave 0: the WSCAN_CAP units from cu on, compacted into the table.  LIST MODE (ul.units, see below): a unit is an entry of the
     // mask's unit list -- its block comes from the entry, its window is the block's, restricted to the entry's word.
     __device__ __forceinline__ void scan(int cu, int last, int stride) {
@@ -93,6 +104,34 @@ struct WindowWalk {
         if (lane == 0) {
             tbl[0] = (uint32_t)base;
             if (lst) tbl[1] = (uint32_t)last;                         // the list's length, parked for more()
+        }
+        if (recs) {                                                   // the record table: entry `lane` of the compacted table, one lane each
+            static_assert(WSCAN_HDR_CAP == WSCAN_CHUNK, "one lane per entry of the record table");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's table writes have landed (other lanes wrote the entry)
+            if (lane < (base < WSCAN_HDR_CAP ? base : WSCAN_HDR_CAP)) {
+                const u32x4* src = (const u32x4*)(recs + tbl[4 + lane]);
+                const u32x4 lo = src[0], hi = src[1];
+                *(u32x4*)(hdr + lane * 8) = lo;
+                *(u32x4*)(hdr + lane * 8 + 4) = hi;
+            }
+        }
+    }
+    // The record of table entry e (its block: blk), eight words as scn_blk_record.h lays them out, wave-uniform: from the record
+    // table, or for an entry past its cap from global memory as one 32-byte read.  Only with `recs` set.
+    __device__ __forceinline__ void record(int e, int blk, uint32_t (&w)[8]) const {
+        u32x4 lo, hi;
+        if (e < WSCAN_HDR_CAP) {
+            lo = *(const u32x4*)(hdr + e * 8);
+            hi = *(const u32x4*)(hdr + e * 8 + 4);
+        } else {
+            const u32x4* src = (const u32x4*)(recs + blk);
+            lo = src[0];
+            hi = src[1];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            w[i] = __builtin_amdgcn_readfirstlane(lo[i]);
+            w[4 + i] = __builtin_amdgcn_readfirstlane(hi[i]);
         }
     }
     // first unit of the next scan and the range's end and stride.  LIST MODE: workgroup g takes entries g, g + G, g + 2 G, ... of

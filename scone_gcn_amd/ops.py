@@ -119,6 +119,11 @@ CONE_UNIT_LIST = True
 # its last visit stages the next unit's first slab (csrc/scn_blk_bwd.inc, scn_conv_visit_prefetch).  Every output bit is the same.
 # On wherever READOUT_CONE runs; False: every unit starts with its full prologue.
 VISIT_PREFETCH = True
+# With the pipeline on, a unit's top reads its header, tile widths and the next unit's source range from the block's packed 32-byte
+# record -- left in LDS by the workgroup's window scan for its first scn_conv_visit_records_cap() live entries, one 32-byte load past them -- and
+# issues every load of the top under one wait (csrc/scn_blk_record.h, scn_conv_visit_records).  Every output bit is the same.
+# False: the header from the plan's separate arrays, as before.
+VISIT_RECORDS = True
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
@@ -207,6 +212,8 @@ def _visit_prefetch(lib):
     """Hands VISIT_PREFETCH to the library ahead of a visiting backward (a build from before the switch has no unit pipeline)."""
     if hasattr(lib, "scn_conv_visit_prefetch"):
         lib.scn_conv_visit_prefetch(1 if VISIT_PREFETCH else 0)
+    if hasattr(lib, "scn_conv_visit_records"):
+        lib.scn_conv_visit_records(1 if VISIT_RECORDS else 0)
 
 
 class WorkList:
