@@ -80,50 +80,19 @@ def _nbytes(*tensors):
 
 
 # Module switches for tests and same-box A/B runs (set them from Python; the one environment variable read here is SCN_SMALL_STEP, once,
-# at import):
+# at import).  The first six say how a plain scone stack runs.  They are read ONCE per step, in the forward, by stack_route() below --
+# the one place that states where each applies -- and the backward follows the route in the forward's record (TOP_DZ_MASK and
+# FUSE_FIRST, which only the backward acts on, included: a switch flipped between a forward and its backward is not seen).  Every one of
+# them leaves every output bit as it is; DESIGN.md section 3 says what the kernels behind them do.
 FUSE_FIRST = True      # False: separate scn_conv_backward + scn_conv_dw_first instead of the fused-first backward
-# The first layer's output H1 is 128 bytes per point that follow from the 16-byte shifted-input record y and 96 weights: the plain scone
-# stack at hidden 32 never stores it -- layer 1 writes y only, layer 2's forward expands y into its LDS image and the fused-first backward
-# rebuilds its aux values in registers (SconePlan.conv_stack / _backward).  False: H1 is materialised (the path every other shape takes).
-RECOMPUTE_FIRST = True
-# Nothing reads the last layer's output H_L except the readout, and that only on the edges around each trajectory's last node (about
-# 0.1 % of the rows at |E| = 1M): the last layer's forward stores only the (plan block, slab) items holding such a row, by a bit mask
-# built on the device from the last nodes (SconePlan.conv_stack, scn_keep_mask, scn_conv_forward_keep).  At hidden 32 the forward
-# visits only those items -- the others are not staged, gathered or contracted; at hidden 16 (slab pairs) every tile is still computed
-# and the others dropped.  Which items run depends on the last nodes, never on a value: this is not the zero-skipping mode.  False: the
-# whole tensor is stored.
-KEEP_LAST = True
-# The mirror on the backward side: the readout's gradient dZ_L is non-zero only on those same rows, yet the top layer's backward staged
-# and gathered all of it -- zeros -- to find its zero-tile early-out.  With the keep mask hopped once over the block adjacency
-# (scn_mask_hop) the top layer's backward stages dZ_L only where a source block holds a row the readout wrote; elsewhere it writes its
-# zero tile without staging, gathering or reading aux (SconePlan._top_dz_mask, scn_conv_backward_dzmask).  Every (block, slab) item is
-# still visited and dX is written in full: this is not the zero-skipping mode.  False: the plain backward.
-TOP_DZ_MASK = True
-# Neither argument stops at the top layer.  The readout reads H_L on the items M0 (the keep mask); the kept layer-L forward stages H_{L-1}
-# only from M1 = hop(M0); the layer-L backward reads H_{L-1} only there and its dX_L is zero outside M1 whatever the data are -- by
-# induction nothing reads H_l outside M_{L-l} = hop^{L-l}(M0), dZ_l is zero outside it, and y is read only on M_{L-1}.  With the switch
-# on, and where KEEP_LAST and TOP_DZ_MASK are both served on a stack of three or more 32-channel layers (SconePlan._readout_cone),
-# every layer's forward runs kept on its set, every backward VISITS the set one hop out (scn_conv_backward_visit and kin), and the
-# gradients between layers live in pooled all-zero buffers that a masked clear wipes where their producer wrote (scn_clear_mask).
-# Which items run depends on the last nodes, never on a value.  False: every layer below the top runs in full.
-READOUT_CONE = True
-# A masked launch ends with its busiest workgroup, and the static shares of the blocks (XCD eighths, strided) are uneven on a cone: a
-# trajectory's items lie in a few neighbouring blocks.  The three forward-side launches of a cone (y on M_{L-1}, the from-y layer,
-# the kept layers) write items that do not depend on the workgroup computing them, so with the switch on the mask kernels also write
-# each mask's UNIT LIST -- its non-empty words, once each -- and workgroup g of G takes entries g, g + G, ... of it (WindowWalk's list
-# mode, csrc/scn_window_scan.inc).  Every output bit is the static walk's.  The visiting backwards keep their shares: dW is summed in
-# visit order.  On wherever READOUT_CONE runs; False: the static walk everywhere.
-CONE_UNIT_LIST = True
-# On a cone a unit of the visiting backwards has 1.3 visits on average, so nearly every visit paid a unit's whole prologue (four
-# dependent trips to memory) with nothing beside it.  With the switch on, a unit's prologue also fetches the next unit's source rows and
-# its last visit stages the next unit's first slab (csrc/scn_blk_bwd.inc, scn_conv_visit_prefetch).  Every output bit is the same.
-# On wherever READOUT_CONE runs; False: every unit starts with its full prologue.
-VISIT_PREFETCH = True
-# With the pipeline on, a unit's top reads its header, tile widths and the next unit's source range from the block's packed 32-byte
-# record -- left in LDS by the workgroup's window scan for its first scn_conv_visit_records_cap() live entries, one 32-byte load past them -- and
-# issues every load of the top under one wait (csrc/scn_blk_record.h, scn_conv_visit_records).  Every output bit is the same.
-# False: the header from the plan's separate arrays, as before.
-VISIT_RECORDS = True
+RECOMPUTE_FIRST = True  # H1 is never stored: layer 1 writes the shifted input y only, layer 2 and its backward rebuild H1 from y.  False: stored
+KEEP_LAST = True       # the last layer stores only the (plan block, slab) items the readout reads (the keep mask M0).  False: all of H_L
+TOP_DZ_MASK = True     # the top layer's backward stages dZ_L only where hop(M0) is set.  False: the plain backward
+READOUT_CONE = True    # every layer runs on the readout's cone M_k = hop^k(M0): kept forwards, visiting backwards.  False: only the top does
+CONE_UNIT_LIST = True  # the cone's forward launches take their units from the masks' unit lists.  False: the static walk
+# ... and two the library reads at every visiting backward of a cone (_visit_prefetch):
+VISIT_PREFETCH = True  # a unit's prologue also fetches the next unit's source rows and first slab.  False: every unit's full prologue
+VISIT_RECORDS = True   # a unit's top reads the block's packed 32-byte record.  False: the plan's separate arrays
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
@@ -204,6 +173,17 @@ def _served(status, name):
     """False when the library does not take the shape (SCN_ERR_UNSUPPORTED: the caller falls back), any other error raises."""
     if status == _lib.SCN_ERR_UNSUPPORTED:
         return False
+    check(status, name)
+    return True
+
+
+def _launch(key, nbytes, name, entry, *args, may_decline=False):
+    """One launch of a library entry under the timer key `key` with its byte model (None: none stated); `name` is what an error
+    message calls it.  may_decline: False where the library does not take the shape (_served) instead of raising."""
+    with _timed(key, nbytes):
+        status = entry(*args)
+    if may_decline:
+        return _served(status, name)
     check(status, name)
     return True
 
@@ -396,19 +376,16 @@ class ConvOp:
         n = nodes.numel()
         words = (-(-n // ns) + 31) // 32
         mask = torch.empty((tabs.n_blocks, words), device=nodes.device, dtype=torch.int32)
-        with _timed(key, _nbytes(mask, nodes)):
-            check(_lib.load().scn_keep_mask(n, ns, _dev(nodes, torch.int32), n_nodes, _dev(tabs.top_ptr, torch.int32),
-                                            _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32), _stream()),
-                  "scn_keep_mask")
+        _launch(key, _nbytes(mask, nodes), "scn_keep_mask", _lib.load().scn_keep_mask, n, ns, _dev(nodes, torch.int32), n_nodes,
+                _dev(tabs.top_ptr, torch.int32), _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32), _stream())
         return mask
 
     def mask_hop(self, mask, tabs):
         """One hop out from a keep_mask() over the plan's block adjacency (scn_mask_hop): bit (b, s) set iff a block that b's rows
         stage has its bit set in `mask` -- the source mask of the top layer's backward.  A fresh buffer per call, as keep_mask."""
         out = torch.empty_like(mask)
-        with _timed("dz_mask_hop", _nbytes(mask, out)):
-            check(_lib.load().scn_mask_hop(tabs.n_blocks, mask.shape[1], _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32),
-                                           _dev(mask, torch.int32), _dev(out, torch.int32), _stream()), "scn_mask_hop")
+        _launch("dz_mask_hop", _nbytes(mask, out), "scn_mask_hop", _lib.load().scn_mask_hop, tabs.n_blocks, mask.shape[1],
+                _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32), _dev(mask, torch.int32), _dev(out, torch.int32), _stream())
         return out
 
     def keep_mask_units(self, nodes, ns, n_nodes, tabs, key="keep_mask"):
@@ -422,10 +399,9 @@ class ConvOp:
         buf = torch.empty(n_words + UNIT_COUNTERS, device=nodes.device, dtype=torch.int32)
         mask, counters = buf[:n_words].view(tabs.n_blocks, words), buf[n_words:]
         units = torch.empty(n_words, device=nodes.device, dtype=torch.int32)
-        with _timed(key, _nbytes(mask, nodes)):
-            check(_lib.load().scn_keep_mask_units(n, ns, _dev(nodes, torch.int32), n_nodes, _dev(tabs.top_ptr, torch.int32),
-                                                  _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32),
-                                                  _dev(units, torch.int32), units.numel(), _stream()), "scn_keep_mask_units")
+        _launch(key, _nbytes(mask, nodes), "scn_keep_mask_units", _lib.load().scn_keep_mask_units, n, ns, _dev(nodes, torch.int32), n_nodes,
+                _dev(tabs.top_ptr, torch.int32), _dev(tabs.top_blk, torch.int32), tabs.n_blocks, _dev(mask, torch.int32),
+                _dev(units, torch.int32), units.numel(), _stream())
         return mask, UnitList(units, counters[0:1]), counters
 
     def mask_hop_units(self, mask, tabs, counter):
@@ -433,18 +409,15 @@ class ConvOp:
         device word that is zero (keep_mask_units hands them out)."""
         out = torch.empty_like(mask)
         units = torch.empty(mask.numel(), device=mask.device, dtype=torch.int32)
-        with _timed("dz_mask_hop", _nbytes(mask, out)):
-            check(_lib.load().scn_mask_hop_units(tabs.n_blocks, mask.shape[1], _dev(tabs.adj_ptr, torch.int32),
-                                                 _dev(tabs.adj_blk, torch.int32), _dev(mask, torch.int32), _dev(out, torch.int32),
-                                                 _dev(units, torch.int32), _dev(counter, torch.int32), units.numel(), _stream()),
-                  "scn_mask_hop_units")
+        _launch("dz_mask_hop", _nbytes(mask, out), "scn_mask_hop_units", _lib.load().scn_mask_hop_units, tabs.n_blocks, mask.shape[1],
+                _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32), _dev(mask, torch.int32), _dev(out, torch.int32),
+                _dev(units, torch.int32), _dev(counter, torch.int32), units.numel(), _stream())
         return out, UnitList(units, counter)
 
     def clear_mask(self, t, mask):
         """+0 over the (block, slab) items of a [S, rows, ns, C] tensor whose bit is set in `mask` (scn_clear_mask)."""
-        with _timed("clear_mask", None):
-            check(_lib.load().scn_clear_mask(self.handle, t.shape[0], t.shape[2], t.shape[3], _dev(t), _dev(mask, torch.int32), _stream()),
-                  "scn_clear_mask")
+        _launch("clear_mask", None, "scn_clear_mask", _lib.load().scn_clear_mask, self.handle, t.shape[0], t.shape[2], t.shape[3], _dev(t),
+                _dev(mask, torch.int32), _stream())
 
     def forward(self, srcs, Ws, c_out, act, out=None, wl=None, partial=None, keep=None, units=None):
         """wl: WorkList (zero-skipping): only the listed items of `out` are written; `out` must be given, all-zero.
@@ -469,26 +442,22 @@ class ConvOp:
             assert tuple(w.shape) == (c_in[self.slot_group[s]], c_out), "weight shape"
         if out is None:
             out = torch.empty((S, self.n_rows, ns, c_out), device=srcs[0].device, dtype=torch.float32)
+        key = "conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out)
+        head = (self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act])
         if partial is not None:
-            with _timed("conv_fwd c%s->%d + partial" % ("+".join(map(str, c_in)), c_out), _nbytes(out, partial, *srcs) + self.csr_bytes):
-                check(lib.scn_conv_forward_accumulate(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act],
-                                                      _dev(partial), _dev(out), _stream()), "scn_conv_forward_accumulate")
-            return out
-        if keep is not None:
+            _launch(key + " + partial", _nbytes(out, partial, *srcs) + self.csr_bytes, "scn_conv_forward_accumulate",
+                    lib.scn_conv_forward_accumulate, *head, _dev(partial), _dev(out), _stream())
+        elif keep is not None:
             # (the key of the plain forward.  32 channels: no byte model -- the launch moves the staged rows and the stored rows of the
             # KEPT items only, and their count is on the device; pricing it at the input tensor would print a rate above the HBM
             # peak.  16 channels: every tile is still staged, the input tensor is the model)
-            with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if c_in[0] == 32 else _nbytes(*srcs) + self.csr_bytes):
-                if units is not None:
-                    st = lib.scn_conv_forward_keep_units(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act],
-                                                         _dev(out), _dev(keep, torch.int32), *_unit_ptrs(units), _stream())
-                else:
-                    st = lib.scn_conv_forward_keep(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
-                                                   _dev(keep, torch.int32), _stream())
-            return out if _served(st, "scn_conv_forward_keep") else None
-        with _timed("conv_fwd c%s->%d" % ("+".join(map(str, c_in)), c_out), None if wl is not None else _nbytes(out, *srcs) + self.csr_bytes):
-            check(lib.scn_conv_forward_list(self.handle, S, ns, _ptrs(srcs), i32_array(c_in), _ptrs(Ws), c_out, ACT[act], _dev(out),
-                                            wl.ref() if wl is not None else None, _stream()), "scn_conv_forward")
+            if not _launch(key, None if c_in[0] == 32 else _nbytes(*srcs) + self.csr_bytes, "scn_conv_forward_keep",
+                           lib.scn_conv_forward_keep_units, *head, _dev(out), _dev(keep, torch.int32), *_unit_ptrs(units), _stream(),
+                           may_decline=True):
+                return None
+        else:
+            _launch(key, None if wl is not None else _nbytes(out, *srcs) + self.csr_bytes, "scn_conv_forward",
+                    lib.scn_conv_forward_list, *head, _dev(out), wl.ref() if wl is not None else None, _stream())
         return out
 
     def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None, visit=None):
@@ -520,34 +489,27 @@ class ConvOp:
         ws = _workspace(lib.scn_conv_backward_workspace(self.handle, S, ns, cdz, c_aux), aux.device, 256)
         if need_dx and dx is None:
             dx = torch.empty_like(aux)
+        key = "conv_bwd c%s->%d" % ("+".join(map(str, c_dz)), c_aux)
+        head = (self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act])
         if dx_partial is not None:
-            with _timed("conv_bwd c%s->%d + partial" % ("+".join(map(str, c_dz)), c_aux), _nbytes(aux, dx, dx_partial, *dzs) + self.csr_bytes):
-                check(lib.scn_conv_backward_accumulate(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
-                                                       _dev(dx_partial), _dev(dx), _ptrs(dWs), *ws, _stream()),
-                      "scn_conv_backward_accumulate")
+            _launch(key + " + partial", _nbytes(aux, dx, dx_partial, *dzs) + self.csr_bytes, "scn_conv_backward_accumulate",
+                    lib.scn_conv_backward_accumulate, *head, _dev(dx_partial), _dev(dx), _ptrs(dWs), *ws, _stream())
             return dx
-        if dz_mask is not None:
-            # (the key of the plain backward; the staged items are left out of the byte model, as the kept stores of the forward are)
-            with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
-                        _nbytes(dx if need_dx else None) + self.csr_bytes):
-                st = lib.scn_conv_backward_dzmask(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
-                                                  _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _dev(dz_mask, torch.int32), _stream())
-            if not _served(st, "scn_conv_backward_dzmask"):
+        # (the three forms below share the plain backward's key)
+        key += "" if need_dx else " (dW only)"
+        tail = (_dev(dx) if need_dx else None, _ptrs(dWs), *ws)
+        if dz_mask is not None:                       # (the staged items are left out of the byte model, as the kept stores of the forward are)
+            if not _launch(key, _nbytes(dx if need_dx else None) + self.csr_bytes, "scn_conv_backward_dzmask",
+                           lib.scn_conv_backward_dzmask, *head, *tail, _dev(dz_mask, torch.int32), _stream(), may_decline=True):
                 return False
-            return dx if need_dx else None
-        if visit is not None:                         # (the key of the plain backward; no byte model: the visited items' count is on the device)
-            with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"), None):
-                _visit_prefetch(lib)
-                st = lib.scn_conv_backward_visit(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
-                                                 _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _dev(visit, torch.int32), _stream())
-            if not _served(st, "scn_conv_backward_visit"):
+        elif visit is not None:                       # (no byte model: the visited items' count is on the device)
+            _visit_prefetch(lib)
+            if not _launch(key, None, "scn_conv_backward_visit",
+                           lib.scn_conv_backward_visit, *head, *tail, _dev(visit, torch.int32), _stream(), may_decline=True):
                 return False
-            return dx if need_dx else None
-        with _timed("conv_bwd c%s->%d%s" % ("+".join(map(str, c_dz)), c_aux, "" if need_dx else " (dW only)"),
-                    None if wl is not None else _nbytes(aux, dx if need_dx else None, *dzs) + self.csr_bytes):
-            check(lib.scn_conv_backward_list(self.handle, S, ns, _ptrs(dzs), cdz, _ptrs(Ws), _dev(aux), c_aux, ACT[act],
-                                             _dev(dx) if need_dx else None, _ptrs(dWs), *ws, wl.ref() if wl is not None else None,
-                                             _stream()), "scn_conv_backward")
+        else:
+            _launch(key, None if wl is not None else _nbytes(aux, dx if need_dx else None, *dzs) + self.csr_bytes, "scn_conv_backward",
+                    lib.scn_conv_backward_list, *head, *tail, wl.ref() if wl is not None else None, _stream())
         return dx if need_dx else None
 
     def forward_first(self, x, Ws, c_out, act, out=None, y=None, wl=None):
@@ -562,10 +524,10 @@ class ConvOp:
             out = torch.empty((S, self.n_rows, ns, c_out), device=x.device, dtype=torch.float32)
         if y is None:
             y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
-        with _timed("conv_fwd c1->%d" % c_out, None if wl is not None else _nbytes(x, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), _ptrs(Ws), c_out, ACT[act], _dev(out), _dev(y),
-                                            wl.ref() if wl is not None else None, _stream())
-        return (out, y) if _served(st, "scn_conv_forward_first") else None
+        ok = _launch("conv_fwd c1->%d" % c_out, None if wl is not None else _nbytes(x, out) + self.csr_bytes, "scn_conv_forward_first",
+                     lib.scn_conv_forward_first, self.handle, S, ns, _dev(x), _ptrs(Ws), c_out, ACT[act], _dev(out), _dev(y),
+                     wl.ref() if wl is not None else None, _stream(), may_decline=True)
+        return (out, y) if ok else None
 
     def shifted_input(self, x, keep=None, units=None):
         """y = (x, S_lo x, S_up x, 0) per point of a 1-channel input WITHOUT the first layer's output (scn_conv_forward_first with
@@ -577,17 +539,13 @@ class ConvOp:
             return None
         y = torch.empty((S, self.n_rows, ns, Y_STRIDE), device=x.device, dtype=torch.float32)
         if keep is not None:                          # (no byte model, see forward)
-            with _timed("conv_fwd c1->y", None):
-                if units is not None:
-                    st = lib.scn_conv_shifted_input_keep_units(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32),
-                                                               *_unit_ptrs(units), _stream())
-                else:
-                    st = lib.scn_conv_shifted_input_keep(self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32), _stream())
-            return y if _served(st, "scn_conv_shifted_input_keep") else None
-        dummy = _ptrs([x] * 3)                        # (the weights are not read without an output; the call checks them for NULL)
-        with _timed("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes):
-            st = lib.scn_conv_forward_first(self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream())
-        return y if _served(st, "scn_conv_forward_first") else None
+            ok = _launch("conv_fwd c1->y", None, "scn_conv_shifted_input_keep", lib.scn_conv_shifted_input_keep_units,
+                         self.handle, S, ns, _dev(x), _dev(y), _dev(keep, torch.int32), *_unit_ptrs(units), _stream(), may_decline=True)
+        else:
+            dummy = _ptrs([x] * 3)                    # (the weights are not read without an output; the call checks them for NULL)
+            ok = _launch("conv_fwd c1->y", _nbytes(x, y) + self.csr_bytes, "scn_conv_forward_first", lib.scn_conv_forward_first,
+                         self.handle, S, ns, _dev(x), dummy, 32, ACT["none"], None, _dev(y), None, _stream(), may_decline=True)
+        return y if ok else None
 
     def forward_from_y(self, y, Ws_first, Ws, act, keep=None, out=None, units=None):
         """The layer AFTER a 1-channel first layer from that layer's shifted input y and weights Ws_first: act(sum_s (S_s H1) Ws[s]) with
@@ -603,18 +561,15 @@ class ConvOp:
             out = torch.empty((S, self.n_rows, ns, c), device=y.device, dtype=torch.float32)
         # (the key of the plain C -> C forward: the same kernel family, and what callers that look for the fused layer kernels expect;
         # the launch is told apart by its neighbour "conv_fwd c1->y" and by its byte model: y in, not H1)
+        key = "conv_fwd c%d->%d" % (c, c)
+        head = (self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out))
         if keep is not None:                          # (no byte model, see forward)
-            with _timed("conv_fwd c%d->%d" % (c, c), None):
-                if units is not None:
-                    st = lib.scn_conv_forward_from_y_keep_units(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act],
-                                                                _dev(out), _dev(keep, torch.int32), *_unit_ptrs(units), _stream())
-                else:
-                    st = lib.scn_conv_forward_from_y_keep(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out),
-                                                          _dev(keep, torch.int32), _stream())
-            return out if _served(st, "scn_conv_forward_from_y_keep") else None
-        with _timed("conv_fwd c%d->%d" % (c, c), _nbytes(y, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_from_y(self.handle, S, ns, _dev(y), _ptrs(Ws_first), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
-        return out if _served(st, "scn_conv_forward_from_y") else None
+            ok = _launch(key, None, "scn_conv_forward_from_y_keep", lib.scn_conv_forward_from_y_keep_units,
+                         *head, _dev(keep, torch.int32), *_unit_ptrs(units), _stream(), may_decline=True)
+        else:
+            ok = _launch(key, _nbytes(y, out) + self.csr_bytes, "scn_conv_forward_from_y", lib.scn_conv_forward_from_y,
+                         *head, _stream(), may_decline=True)
+        return out if ok else None
 
     def forward_power(self, x0, x, Ws, act):
         """out = act(x0 W0 + x W1 + (S x) W2) for an operator with identity + one value array (scn_conv_forward_power);
@@ -622,9 +577,9 @@ class ConvOp:
         lib = _lib.load()
         S, rows, ns, c = x.shape
         out = torch.empty_like(x)
-        with _timed("conv_fwd_power c%d" % c, _nbytes(x0, x, out) + self.csr_bytes):
-            st = lib.scn_conv_forward_power(self.handle, S, ns, _dev(x0), _dev(x), _ptrs(Ws), c, ACT[act], _dev(out), _stream())
-        return out if _served(st, "scn_conv_forward_power") else None
+        ok = _launch("conv_fwd_power c%d" % c, _nbytes(x0, x, out) + self.csr_bytes, "scn_conv_forward_power", lib.scn_conv_forward_power,
+                     self.handle, S, ns, _dev(x0), _dev(x), _ptrs(Ws), c, ACT[act], _dev(out), _stream(), may_decline=True)
+        return out if ok else None
 
     def backward_power(self, dz, g1, Ws, aux, act, need_dx, dWs):
         """Backward of forward_power given g1 = S^T dz (scn_conv_backward_power); returns (served, dx)."""
@@ -635,9 +590,9 @@ class ConvOp:
             return False, None
         ws = _workspace(nbytes, dz.device)
         dx = torch.empty_like(aux) if need_dx else None
-        with _timed("conv_bwd_power c%d" % c, _nbytes(dz, g1, aux, dx) + self.csr_bytes):
-            check(lib.scn_conv_backward_power(self.handle, S, ns, _dev(dz), _dev(g1), _ptrs(Ws), _dev(aux), c, ACT[act],
-                                              _dev(dx) if need_dx else None, _ptrs(dWs), *ws, _stream()), "scn_conv_backward_power")
+        _launch("conv_bwd_power c%d" % c, _nbytes(dz, g1, aux, dx) + self.csr_bytes, "scn_conv_backward_power", lib.scn_conv_backward_power,
+                self.handle, S, ns, _dev(dz), _dev(g1), _ptrs(Ws), _dev(aux), c, ACT[act], _dev(dx) if need_dx else None, _ptrs(dWs), *ws,
+                _stream())
         return True, dx
 
     def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None, visit=None):
@@ -656,25 +611,21 @@ class ConvOp:
         if nbytes == 0:
             return False
         ws = _workspace(nbytes, dz.device)
+        key = "conv_bwd c%d->%d + dW_first" % (c, c)
+        head = (self.handle, S, ns, _dev(dz), _ptrs(Ws))
+        tail = (c, ACT[act], _dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws)
         if visit is not None:
             if aux is not None or wl is not None:
                 return False
-            with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None):
-                _visit_prefetch(lib)
-                st = lib.scn_conv_backward_fused_first_from_y_visit(self.handle, S, ns, _dev(dz), _ptrs(Ws), _ptrs(Ws_first), c, ACT[act],
-                                                                    _dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws,
-                                                                    _dev(visit, torch.int32), _stream())
-            return _served(st, "scn_conv_backward_fused_first_from_y_visit")
-        tail = (_dev(y), _ptrs(dWs), _ptrs(dWs_first), *ws, wl.ref() if wl is not None else None, _stream())
+            _visit_prefetch(lib)
+            return _launch(key, None, "scn_conv_backward_fused_first_from_y_visit", lib.scn_conv_backward_fused_first_from_y_visit,
+                           *head, _ptrs(Ws_first), *tail, _dev(visit, torch.int32), _stream(), may_decline=True)
+        wl_ref = wl.ref() if wl is not None else None
         if aux is None:
-            with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, y) + self.csr_bytes):
-                check(lib.scn_conv_backward_fused_first_from_y(self.handle, S, ns, _dev(dz), _ptrs(Ws), _ptrs(Ws_first), c, ACT[act], *tail),
-                      "scn_conv_backward_fused_first_from_y")
-            return True
-        with _timed("conv_bwd c%d->%d + dW_first" % (c, c), None if wl is not None else _nbytes(dz, aux, y) + self.csr_bytes):
-            check(lib.scn_conv_backward_fused_first(self.handle, S, ns, _dev(dz), _ptrs(Ws), _dev(aux), c, ACT[act], *tail),
-                  "scn_conv_backward_fused_first")
-        return True
+            return _launch(key, None if wl is not None else _nbytes(dz, y) + self.csr_bytes, "scn_conv_backward_fused_first_from_y",
+                           lib.scn_conv_backward_fused_first_from_y, *head, _ptrs(Ws_first), *tail, wl_ref, _stream())
+        return _launch(key, None if wl is not None else _nbytes(dz, aux, y) + self.csr_bytes, "scn_conv_backward_fused_first",
+                       lib.scn_conv_backward_fused_first, *head, _dev(aux), *tail, wl_ref, _stream())
 
     def clear(self, t, wl):
         """Zero the listed items of a [S, rows, ns, C] tensor (scn_clear_list)."""
@@ -722,11 +673,9 @@ class ConvOp:
         if nbytes == 0:
             return False
         ws = _workspace(nbytes, dz.device)
-        with _timed("conv_dw_first c%d" % c, None if wl is not None else _nbytes(dz) + 4.0 * S * rows * ns + self.csr_bytes):
-            check(lib.scn_conv_dw_first(self.handle, S, ns, _dev(x) if x is not None else None, _dev(y) if y is not None else None,
-                                        _dev(dz), c, _ptrs(dWs), *ws, wl.ref() if wl is not None else None, _stream()),
-                  "scn_conv_dw_first")
-        return True
+        return _launch("conv_dw_first c%d" % c, None if wl is not None else _nbytes(dz) + 4.0 * S * rows * ns + self.csr_bytes,
+                       "scn_conv_dw_first", lib.scn_conv_dw_first, self.handle, S, ns, _dev(x) if x is not None else None,
+                       _dev(y) if y is not None else None, _dev(dz), c, _ptrs(dWs), *ws, wl.ref() if wl is not None else None, _stream())
 
     def spmm_dual(self, x, dual=True):
         lib = _lib.load()
@@ -734,9 +683,8 @@ class ConvOp:
         assert rows == self.group_cols[0]
         ya = torch.empty((S, self.n_rows, k), device=x.device, dtype=torch.float32)
         yb = torch.empty_like(ya) if dual else None
-        with _timed("spmm_dual k%d" % k if dual else "spmm k%d" % k, _nbytes(x, ya, yb) + self.csr_bytes):
-            check(lib.scn_spmm_dual(self.handle, S, k, _dev(x), _dev(ya), _dev(yb) if dual else None, _stream()),
-                  "scn_spmm_dual")
+        _launch("spmm_dual k%d" % k if dual else "spmm k%d" % k, _nbytes(x, ya, yb) + self.csr_bytes, "scn_spmm_dual", lib.scn_spmm_dual,
+                self.handle, S, k, _dev(x), _dev(ya), _dev(yb) if dual else None, _stream())
         return ya, yb
 
 
@@ -1108,6 +1056,7 @@ class SconeState(NamedTuple):
     wide: bool          # hidden widths above 32 ran in 32-channel blocks (_wide_stack / _wide_backward)
     cone: object = None  # ops.READOUT_CONE: the masks [M0 .. M_{L-1}] the forward ran on (layer l kept on M_{L-l}, y0 on M_{L-1}: every
                          # other row of hs[2:] and y0 is uninitialised memory), which the backward visits by; None: the stack ran in full
+    route: object = None  # the StackRoute the forward ran by, which the backward follows; None: wide, PowerPlan
 
 
 class Cone(list):
@@ -1115,6 +1064,53 @@ class Cone(list):
     (ops.CONE_UNIT_LIST), units[k] = the UnitList of M_k (None: M_k has none); None otherwise.  They belong to this forward's record
     as the masks do: fresh buffers, shared with no other forward on the plan."""
     units = None
+
+
+class StackRoute(NamedTuple):
+    """How one step of a plain scone stack runs: filled once per forward by stack_route(), kept in SconeState.route, followed by the
+    backward.  Every route computes the same bits."""
+    first: str            # layers 1 and 2.  "from_y": layer 1 writes the shifted input y only, layer 2 and its backward rebuild H1 from y
+                          # (hs[1] is None); "stored": forward_first stores H1 and y; "plain": an ordinary layer, no y (no 1-channel input)
+    keep_last: bool       # the last layer's forward runs kept on M0, the keep mask of the last nodes
+    cone: bool            # every layer runs on the readout's cone [M0 .. M_{L-1}]: kept forwards, visiting backwards, masked clears
+    units: bool           # ... and the cone's forward launches take their units from the masks' lists
+    top_dz_mask: bool     # off the cone, the top layer's backward stages dZ_L by hop(M0), rebuilt from the last nodes
+    fused_first: bool     # layer 2's backward also sums the first layer's weight gradient from y (always after "from_y")
+
+    def fallback(self):
+        """The route to try where the library declines a launch of this one: the cone gives way to the stack in full, "from_y" to a
+        stored H1.  (A kept last layer that is declined is rerun plainly on the spot: conv_stack.)"""
+        if self.cone:
+            return self._replace(cone=False, units=False)
+        assert self.first == "from_y", "only a cone or a from-y pair can be declined"
+        return self._replace(first="stored")
+
+
+def stack_route(x_shape, w_shapes, *, activity, last_dev, fused_conv, symmetric, blocked, tables, tables_built, capturing,
+                keep_last_min, small_dz, cone_min):
+    """The StackRoute of one forward from plain facts (no tensor is touched, nothing is launched): the shapes of x and of the weights
+    the stack runs on (promoted ones where it is promoted); activity: work lists are given; last_dev: (count, dtype) of the last
+    nodes or None; fused_conv, symmetric (conv_T is conv), blocked: the plan's operator; tables: the plan has field tables (none for
+    a probed closure), tables_built: already, capturing: the stream is under a graph capture; the three SconePlan bounds, each against
+    its own tensor.  The module switches are read here, now."""
+    S, E, ns, c_in = x_shape
+    shapes = [tuple(s) for s in w_shapes]
+    L = (len(shapes) - 1) // 3
+    last = shapes[-2] if L >= 2 else None          # the last layer's weights, where it is not also the first
+    # every form but the stored one: the plain scone plan on its blocked operator, dense launches, slabs of NS trajectories
+    base = bool(fused_conv and blocked and not activity and ns == NS)
+    from_y = (base and RECOMPUTE_FIRST and FUSE_FIRST and c_in == 1 and L >= 2
+              and shapes[:-1] == [(1, 32)] * 3 + [(32, 32)] * (3 * (L - 1)))
+    # M0 can be built: one int32 last node per trajectory, and the node -> blocks table (built on the host at first use: not under a capture)
+    m0 = base and last_dev == (S * ns, torch.int32) and bool(tables) and (tables_built or not capturing)
+    keep_last = m0 and KEEP_LAST and last in ((32, 32), (16, 16)) and S * E * ns * last[1] * 4 > keep_last_min      # H_L at its own width
+    dz32 = S * E * ns * 32 * 4                     # a 32-channel gradient buffer; at or below small_dz the readout's backward zeroes it itself
+    # (symmetric shifts: the plan's block adjacency is the forward operator's)
+    top_dz_mask = m0 and TOP_DZ_MASK and symmetric and L >= 3 and last == (32, 32) and dz32 > small_dz
+    # the cone: where both are served on a stack without a stored H1, at most 64 slabs (every masked launch is served whatever its grid)
+    cone = keep_last and top_dz_mask and from_y and READOUT_CONE and S <= 64 and dz32 > cone_min
+    return StackRoute(first="from_y" if from_y else "stored" if c_in == 1 else "plain", keep_last=keep_last, cone=cone,
+                      units=cone and CONE_UNIT_LIST, top_dz_mask=top_dz_mask, fused_first=FUSE_FIRST and c_in == 1)
 
 
 class BunchState(NamedTuple):
@@ -1191,148 +1187,102 @@ class SconePlan(Plan):
         self.nnz_lower, self.nnz_upper = int(lo.nnz), int(up.nnz)
 
     # -- raw forward/backward over slabs (no autograd): used by the autograd Function and by the trainer
+    # The three bounds of the masked forms, each against its own tensor (stack_route); tests set them to 0 to take the forms on small
+    # complexes.  Up to KEEP_LAST_MIN_BYTES of H_L the last layer stores everything: the mask's two launches cost more than the stores
+    # they save on the graph-replayed steps of small complexes.  SMALL_DZ_BYTES: see _readout_grad.  READOUT_CONE_MIN_BYTES is the same
+    # bound under a name of its own, so that a test that sets the other two to 0 stays off the cone.
+    KEEP_LAST_MIN_BYTES = 8 << 20
+    SMALL_DZ_BYTES = 8 << 20      # below this the readout's backward zeroes the whole buffer itself instead of keeping it all-zero (small complexes)
+    READOUT_CONE_MIN_BYTES = 8 << 20
+
+    def _route(self, x, weights, activity, last_dev):
+        """stack_route() of this forward: the facts it takes, read off the plan and the arguments."""
+        return stack_route(tuple(x.shape), _shapes(weights), activity=activity is not None,
+                           last_dev=None if last_dev is None else (last_dev.numel(), last_dev.dtype), fused_conv=self.fused_conv,
+                           symmetric=self.conv_T is self.conv, blocked=self._blocked(), tables=self._has_field_tables(),
+                           tables_built=self._field is not None, capturing=torch.cuda.is_current_stream_capturing(),
+                           keep_last_min=self.KEEP_LAST_MIN_BYTES, small_dz=self.SMALL_DZ_BYTES, cone_min=self.READOUT_CONE_MIN_BYTES)
+
+    def _masks(self, route, last_dev, L):
+        """The masks a route's forward runs by, as a Cone: [M0] for a kept last layer, [M0 .. M_{L-1}] (M_k one hop out from M_{k-1})
+        for a cone, None without either.  With route.units every mask comes with its unit list (Cone.units): M0's own and
+        UNIT_COUNTERS - 1 hops' share one allocation of counters, a stack deeper than they reach runs its lowest masks without one."""
+        if not route.keep_last:
+            return None
+        tabs = self.field_tables_dev()
+        if route.units:
+            m0, u0, counters = self.conv.keep_mask_units(last_dev, NS, self.n_nodes, tabs)
+        else:
+            m0, u0, counters = self.conv.keep_mask(last_dev, NS, self.n_nodes, tabs), None, ()
+        masks = Cone([m0])
+        masks.units = [u0] if route.units else None
+        for k in range(1, L if route.cone else 1):
+            if k < len(counters):
+                m, u = self.conv.mask_hop_units(masks[-1], tabs, counters[k:k + 1])
+            else:
+                m, u = self.conv.mask_hop(masks[-1], tabs), None
+            masks.append(m)
+            if route.units:
+                masks.units.append(u)
+        return masks
+
     def conv_stack(self, x, weights, activity=None, last_dev=None, out_last=None):
-        """last_dev: the trajectories' last nodes (what the readout of this forward will take).  With them the LAST layer stores only
-        what that readout reads (_keep_last); without them, or where that path is not served, every layer stores its whole output.
+        """One pass over the layers by the route of this forward (stack_route); returns (hs, y0, cone, route), the route being the one
+        that ran: where the library declines a launch of a cone or of a from-y pair the stack starts again on route.fallback().
+        last_dev: the trajectories' last nodes (what the readout of this forward will take), which the masked routes need.
         out_last (dense stacks of two or more layers): the buffer H_L is written into instead of a fresh one -- a test pre-fills it
         to see which rows a forward wrote."""
         n_layers = (len(weights) - 1) / 3
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:141-142
-        hs, y0 = [x], None
-        S, E, ns, _ = x.shape
         L = int(n_layers)
-        # (the masks of a cone that runs on unit lists are built WITH their lists, M0's among them: asked for where the cone's own
-        # conditions hold, ahead of the mask they also need)
-        listed = CONE_UNIT_LIST and self._cone_shape(x, weights, activity)
-        keep = self._keep_last(x, weights, activity, last_dev, units=listed)
-        keep, units0, counters = keep if listed and keep is not None else (keep, None, None)
-        cone = self._readout_cone(x, weights, activity, keep, units0, counters)
-        if cone is not None:                            # every layer on the readout's cone (READOUT_CONE); not served: the stack below, in full
-            ul = cone.units if cone.units is not None else [None] * L
-            y0, h = self.conv.shifted_input(x, keep=cone[L - 1], units=ul[L - 1]), None
-            if y0 is not None:
-                h = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=cone[L - 2], units=ul[L - 2])
-            hs += [None, h]
-            for i in range(2, L):
-                if hs[-1] is not None:
-                    hs.append(self.conv.forward([hs[-1]], weights[3 * i:3 * i + 3], 32, self.act, out=out_last if i == L - 1 else None,
-                                                keep=cone[L - 1 - i], units=ul[L - 1 - i]))
-            if hs[-1] is not None:
-                return hs, y0, cone
-            hs, y0 = [x], None
+        route = self._route(x, weights, activity, last_dev)
+        masks = self._masks(route, last_dev, L)
+        while True:
+            ran = self._layers(route, masks, x, weights, activity, out_last, L)
+            if ran is not None:
+                return ran
+            route = route.fallback()
 
-        def layer(i, src):                              # layer i >= 1 of a dense stack; the last one by the keep mask where there is one
-            w = weights[3 * i:3 * i + 3]
-            buf = out_last if i == L - 1 else None
-            out = self.conv.forward([src], w, w[0].shape[1], self.act, out=buf, keep=keep) if keep is not None and i == L - 1 else None
-            return out if out is not None else self.conv.forward([src], w, w[0].shape[1], self.act, out=buf)
-
-        if self._recompute_first(x, weights, activity):
-            # hidden 32 throughout, 1-channel input, dense: H1 is never stored (hs[1] is None).  Layer 1 writes the shifted input y
-            # only, layer 2 expands it in LDS; the backward sees hs[1] is None and rebuilds its aux values from y (see _backward)
-            y0 = self.conv.shifted_input(x)
-            h2 = None
-            if y0 is not None and keep is not None and L == 2:
-                h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, keep=keep, out=out_last)
-            if y0 is not None and h2 is None:
-                h2 = self.conv.forward_from_y(y0, weights[0:3], weights[3:6], self.act, out=out_last if L == 2 else None)
-            if h2 is not None:
-                hs += [None, h2]
-                for i in range(2, L):
-                    hs.append(layer(i, hs[-1]))
-                return hs, y0, None
-            y0 = None
-        for i in range(int(n_layers)):
+    def _layers(self, route, masks, x, weights, activity, out_last, L):
+        """conv_stack's pass; None where a launch the route cannot do without is declined.  Layer l (1-based) of a cone runs kept on
+        M_{L-l} and y on M_{L-1}; off the cone only the last layer has a mask, and reruns plainly where its kept form is declined."""
+        S, E, ns, _ = x.shape
+        cone = masks if route.cone else None
+        hs, y0 = [x], None
+        for i in range(L):
             w = weights[3 * i:3 * i + 3]
             c_out = w[0].shape[1]
+            k = L - 1 - i
+            keep = masks[k] if cone is not None or (route.keep_last and k == 0) else None
+            units = cone.units[k] if cone is not None and cone.units is not None else None
             wl = activity["fwd"][i] if activity else None
-            out = self._zeros((S, E, ns, c_out)) if activity else None
-            first = None
-            if i == 0:
-                first = self.conv.forward_first(x, w, c_out, self.act, out=out,
-                                                y=self._zeros((S, E, ns, Y_STRIDE)) if activity else None, wl=wl)
+            out = self._zeros((S, E, ns, c_out)) if activity else out_last if (k == 0 and i > 0) else None
+            if i == 0 and route.first == "from_y":      # y only: H1 is never stored (hs[1] is None)
+                y0, h = self.conv.shifted_input(x, keep=keep, units=units), None
+                if y0 is None:
+                    return None
+            elif i == 0:
+                first = None
+                if route.first == "stored":             # 1-channel input: keep the shifted input for the weight gradient
+                    first = self.conv.forward_first(x, w, c_out, self.act, out=out, y=self._zeros((S, E, ns, Y_STRIDE)) if activity else None,
+                                                    wl=wl)
                 assert first is not None or not activity
-            if first is not None:                       # 1-channel input: keep the shifted input for the weight gradient
-                hs.append(first[0])
-                y0 = first[1]
-            elif activity is None and i > 0:
-                hs.append(layer(i, hs[-1]))
+                if first is None:                       # an ordinary layer (also where forward_first is declined): no y, no fused-first backward
+                    route = route._replace(first="plain", fused_first=False)
+                    first = self.conv.forward([x], w, c_out, self.act, out=out, wl=wl), None
+                h, y0 = first
             else:
-                hs.append(self.conv.forward([hs[-1]], w, c_out, self.act, out=out, wl=wl))
-        return hs, y0, None
-
-    # up to this size of H_L the last layer stores everything: the two extra launches of the mask cost more than the stores they save
-    # on the graph-replayed steps of small complexes (the bound of SMALL_DZ_BYTES; tests set 0 to take the path on small complexes)
-    KEEP_LAST_MIN_BYTES = 8 << 20
-
-    def _keep_last(self, x, weights, activity, last_dev, units=False):
-        """The keep mask the last layer of this stack runs with, or None: plain scone plan on its blocked operator, dense launches, a
-        last layer of 32 -> 32 or 16 -> 16 channels (so at least two layers), an H_L above KEEP_LAST_MIN_BYTES, and the plan's
-        node -> blocks table (field_tables_dev: none for a probed closure; it is built on the host at first use, so not under a
-        graph capture).  KEEP_LAST is the tests' and A/B's switch.  units: the mask comes with its unit list, (mask, UnitList, counters)
-        of ConvOp.keep_mask_units."""
-        if not KEEP_LAST or last_dev is None or activity is not None or not self.fused_conv or len(weights) < 7:
-            return None
-        S, E, ns, _ = x.shape
-        sh = tuple(weights[-2].shape)
-        if ns != NS or sh not in ((32, 32), (16, 16)) or last_dev.numel() != S * ns or last_dev.dtype != torch.int32:
-            return None
-        if S * E * ns * sh[1] * 4 <= self.KEEP_LAST_MIN_BYTES or not self._blocked():
-            return None
-        if self._field is None and torch.cuda.is_current_stream_capturing():
-            return None
-        tabs = self.field_tables_dev()
-        if tabs is None:
-            return None
-        return self.conv.keep_mask_units(last_dev, ns, self.n_nodes, tabs) if units else self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs)
-
-    # the bound of KEEP_LAST_MIN_BYTES and SMALL_DZ_BYTES under a name of its own: a test that sets those two to 0 to take their paths on a
-    # small complex stays on those paths; the tests of this one set all three
-    READOUT_CONE_MIN_BYTES = 8 << 20
-
-    def _cone_shape(self, x, weights, activity):
-        """The conditions of _readout_cone that do not need the keep mask."""
-        L = (len(weights) - 1) // 3
-        if not READOUT_CONE or not TOP_DZ_MASK or L < 3 or self.conv_T is not self.conv:
-            return False
-        S, E, ns, _ = x.shape
-        nbytes = S * E * ns * 32 * 4
-        return not (S > 64 or nbytes <= self.SMALL_DZ_BYTES or nbytes <= self.READOUT_CONE_MIN_BYTES
-                    or not self._recompute_first(x, weights, activity))
-
-    def _readout_cone(self, x, weights, activity, keep, units0=None, counters=None):
-        """The masks [M0 .. M_{L-1}] of the readout's cone (M0 = keep, M_k = one hop out from M_{k-1}), or None: exactly where _keep_last
-        and _top_dz_mask are both served -- their switches on, `keep` built (plain scone plan on its blocked operator, dense launches,
-        the sizes and the tables of _keep_last), symmetric shifts, the gradient buffers above SMALL_DZ_BYTES -- on a stack of three or
-        more layers that runs without a stored H1 (1-channel input, hidden 32 throughout: _recompute_first), and at most 64 slabs,
-        where every masked launch is served whatever its grid.  READOUT_CONE is the tests' and A/B's switch.
-        units0, counters (ops.CONE_UNIT_LIST): M0's UnitList and the zeroed counter words of ConvOp.keep_mask_units -- every hop then
-        writes its mask's list too (Cone.units; a stack deeper than the counters reach runs its lowest masks without one)."""
-        L = (len(weights) - 1) // 3
-        if keep is None or not self._cone_shape(x, weights, activity):
-            return None
-        tabs = self.field_tables_dev()
-        cone = Cone([keep])
-        if units0 is not None:
-            cone.units = [units0]
-        for k in range(1, L):
-            if cone.units is not None and k < counters.numel():
-                m, u = self.conv.mask_hop_units(cone[-1], tabs, counters[k:k + 1])
-                cone.units.append(u)
-            else:
-                m = self.conv.mask_hop(cone[-1], tabs)
-                if cone.units is not None:
-                    cone.units.append(None)
-            cone.append(m)
-        return cone
-
-    def _recompute_first(self, x, weights, activity):
-        """Whether this stack runs without a stored H1: plain scone plan, 1-channel input, every hidden width 32 (no promotion), at
-        least two layers, dense launches, symmetric or not.  All observed, not chosen; RECOMPUTE_FIRST is the tests' and A/B's switch."""
-        L = (len(weights) - 1) // 3
-        return (RECOMPUTE_FIRST and FUSE_FIRST and self.fused_conv and activity is None and x.shape[3] == 1 and L >= 2
-                and x.shape[2] == NS and self._blocked()
-                and [tuple(w.shape) for w in weights[:-1]] == [(1, 32)] * 3 + [(32, 32)] * (3 * (L - 1)))
+                if i == 1 and route.first == "from_y":  # layer 2 expands y in LDS
+                    call = lambda **kept: self.conv.forward_from_y(y0, weights[0:3], w, self.act, out=out, **kept)
+                else:
+                    call = lambda **kept: self.conv.forward([hs[-1]], w, c_out, self.act, out=out, wl=wl, **kept)
+                h = call(keep=keep, units=units) if keep is not None else None
+                if h is None and cone is None:
+                    h = call()
+                if h is None:
+                    return None
+            hs.append(h)
+        return hs, y0, cone, route
 
     # -- zero-skipping mode ---------------------------------------------------------------------------------
     def _block_graph(self):
@@ -1434,11 +1384,14 @@ class SconePlan(Plan):
         return {"fwd": fwd, "bwd": bwd, "mode": mode,
                 "active_fraction": {"fwd": [w.items / total for w in fwd], "bwd": [w.items / total for w in bwd[1:]]}}
 
+    def _has_field_tables(self):
+        return self.conv is not None and self.conv.plan_info()[0] > 0 and not self._probed
+
     def field_tables_dev(self):
         """FieldTables of this plan (built and uploaded once; dropped with the readout tables), or None where activity() serves
         nothing either: no blocked plan, a probed Bcond_func closure.  The pattern is the one `conv` stores (union_pattern of the two
         shifts, explicit zeros included): what a block's rows stage, and for non-symmetric shifts nothing more."""
-        if self.conv is None or not self.conv.plan_info()[0] or self._probed:
+        if not self._has_field_tables():
             return None
         if self._field is None:
             rowptr, cols, _ = union_pattern([s.device_csr() for s in self._shift_pair])
@@ -1551,9 +1504,12 @@ class SconePlan(Plan):
             check(_lib.load().scn_logits_sum_log_softmax(logp.shape[0], self.max_deg, len(parts), _ptrs(parts),
                                                          _dev(parts[0]), _dev(logp), _stream()), "scn_logits_sum_log_softmax")
             return logp, SconeState(hs, bhs, y0, None, wp, wide=True)
-        hs, y0, cone = self.conv_stack(x, w, activity, last_dev, out_last)
+        if not self.fused_conv:                         # (PowerPlan: every layer stores its whole output, no route)
+            (hs, y0), cone, route = self.conv_stack(x, w), None, None
+        else:
+            hs, y0, cone, route = self.conv_stack(x, w, activity, last_dev, out_last)
         logp, bh, _ = self.readout(hs[-1], w[-1], last_dev)
-        return logp, SconeState(hs, bh, y0, activity, wp, wide=False, cone=cone)
+        return logp, SconeState(hs, bh, y0, activity, wp, wide=False, cone=cone, route=route)
 
     # -- hidden widths above 32 (TE:103-110 accepts any): every activation is P / 32 separate 32-channel tensors and a layer is
     # its (input block i, output block j) pairs on the fused C = 32 kernels -- act(sum_i sum_s (S_s H_i) W_s[i, j]) (TE:143-149):
@@ -1642,8 +1598,6 @@ class SconePlan(Plan):
                                        _dev(grads[-1]), _stream()), "scn_readout_backward")
         return dz_top, key
 
-    SMALL_DZ_BYTES = 8 << 20      # below this the readout's backward zeroes the whole buffer itself instead of keeping it all-zero (small complexes)
-
     def _release_top(self, dz_top, key, last_dev):
         S, E, ns, C = key
         if dz_top.numel() * 4 <= self.SMALL_DZ_BYTES:
@@ -1653,97 +1607,54 @@ class SconePlan(Plan):
                                                _dev(dz_top), _stream()), "scn_readout_clear_dz")
         self._dz_zero.setdefault(key, []).append(dz_top)
 
-    def _top_dz_mask(self, dz_top, aux, activity, last_dev):
-        """The source mask the top layer's backward stages the readout gradient by, or None: plain scone plan on its blocked operator
-        with symmetric shifts (conv_T is conv: the plan's block adjacency is the forward operator's), dense launches, 32 -> 32
-        channels, the pooled all-zero buffer (above SMALL_DZ_BYTES; below it dz_top is zeroed by the readout's launch and the plain
-        call is cheaper than two mask launches) and the plan's tables (field_tables_dev; not built under a graph capture).  Built
-        from the last nodes the readout's backward got, for this call alone: nothing is kept on the plan.  TOP_DZ_MASK is the tests'
-        and A/B's switch."""
-        if not TOP_DZ_MASK or last_dev is None or activity is not None or not self.fused_conv or self.conv_T is not self.conv:
-            return None
-        S, E, ns, C = dz_top.shape
-        if ns != NS or C != 32 or aux.shape[3] != 32 or last_dev.numel() != S * ns or last_dev.dtype != torch.int32:
-            return None
-        if dz_top.numel() * 4 <= self.SMALL_DZ_BYTES or not self._blocked():
-            return None
-        if self._field is None and torch.cuda.is_current_stream_capturing():
-            return None
-        tabs = self.field_tables_dev()
-        if tabs is None:
-            return None
-        return self.conv.mask_hop(self.conv.keep_mask(last_dev, ns, self.n_nodes, tabs, key="dz_mask"), tabs)
-
-    def _cone_backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        """The backward of a forward that ran on the readout's cone (saved.cone = [M0 .. M_{L-1}]): layer l visits M_{L-l+1}, one hop
-        out from the set its dZ_l was written on.  dX_l goes into a pooled all-zero buffer (the readout gradient's pool: same shape,
-        same all-zero state) on the visited items only; once its consumer has run, the masked clear wipes exactly those items."""
-        hs, y0, cone = saved.hs, saved.y0, saved.cone
-        L = len(hs) - 1
-        dz, key = self._readout_grad(hs[-1], saved.bh, logp, d_logp, last_dev, weights, grads)
-        wrote = None                                    # the mask dz was written on (None: the readout's rows, wiped by _release_top)
-        for i in reversed(range(1, L)):
-            w, g, visit = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3], cone[L - i]
-            if i == 1:                                  # H1 was never stored: aux from y0, dW_first in the same launch, no dx
-                assert self.conv.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit), \
-                    "visiting fused-first backward not served"
-                dx = None
-            else:
-                pool = self._dz_zero.get(key)
-                dx = pool.pop() if pool else torch.zeros_like(dz)
-                assert self.conv.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit) is not False, "visiting backward not served"
-            if wrote is None:
-                self._release_top(dz, key, last_dev)
-            else:
-                self.conv.clear_mask(dz, wrote)
-                self._dz_zero.setdefault(key, []).append(dz)
-            dz, wrote = dx, visit
-        return grads
-
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
+        """One loop down the layers by the route the forward ran (saved.route).  On a cone (saved.cone = [M0 .. M_{L-1}]) layer l visits
+        M_{L-l+1}, one hop out from the set its dZ_l was written on, and dX_l goes into a pooled all-zero buffer (the readout
+        gradient's pool: same shape, same all-zero state) on the visited items only; once its consumer has run, the masked clear wipes
+        exactly those items.  Off the cone the top layer stages dZ_L by hop(M0) where the route says so: the mask is built from the
+        last nodes the readout's backward got, for this call alone."""
         if saved.wide:
             return self._wide_backward(saved, logp, d_logp, last_dev, weights, grads)
-        if saved.cone is not None:
-            return self._cone_backward(saved, logp, d_logp, last_dev, weights, grads)
-        hs, bh, y0, activity = saved.hs, saved.bh, saved.y0, saved.activity
-        dz_top, key = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
-        S, E, ns, C = hs[-1].shape
+        hs, y0, activity, cone, route = saved.hs, saved.y0, saved.activity, saved.cone, saved.route
         L = len(hs) - 1
-        dz = dz_top
-        fused_first = False
+        dz, key = self._readout_grad(hs[-1], saved.bh, logp, d_logp, last_dev, weights, grads)
         for i in reversed(range(L)):
-            if i == 0 and fused_first:
-                break                                   # the first layer's weight gradient came out of layer 1's backward
+            w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
             wl_out = activity["bwd"][i] if (activity and i > 0) else None      # items of this layer's input gradient
             wl_in = activity["bwd"][i + 1] if activity else None                # support of dz
-            dz_in = dz
-            if i == 1 and hs[1] is None:                # the forward ran without a stored H1 (conv_stack): aux is rebuilt from y0
-                assert self.conv_T.backward_fused_first(dz, weights[3:6], None, self.act, y0, grads[3:6], grads[0:3],
-                                                        Ws_first=weights[0:3]), "aux-free fused-first backward not served"
-                fused_first = True
-                dz = None
-            elif i == 1 and hs[0].shape[3] == 1 and y0 is not None and FUSE_FIRST and \
-                    self.conv_T.backward_fused_first(dz, weights[3:6], hs[1], self.act, y0, grads[3:6], grads[0:3], wl=wl_out):
-                fused_first = True                      # dx of this layer only feeds dW_first: contracted in registers, never written
-                dz = None
-            elif i == 0 and hs[0].shape[3] == 1 and self.conv.dw_first(hs[0], y0, dz, grads[0:3], wl=wl_in):
-                dz = None                               # first layer: shifted 1-channel input x one stream over dz
+            visit = cone[L - i] if cone is not None else None
+            first_done = i == 0                         # the first layer's weight gradient is out: nothing is left below
+            if i == 1 and route.first == "from_y":      # H1 was never stored: aux is rebuilt from y0, dW_first in the same launch, no dx
+                assert self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit), \
+                    "aux-free fused-first backward not served"
+                first_done, dx = True, None
+            elif i == 1 and route.fused_first and self.conv_T.backward_fused_first(dz, w, hs[1], self.act, y0, g, grads[0:3], wl=wl_out):
+                first_done, dx = True, None             # dx of this layer only feeds dW_first: contracted in registers, never written
+            elif i == 0 and hs[0].shape[3] == 1 and self.conv.dw_first(hs[0], y0, dz, g, wl=wl_in):
+                dx = None                               # first layer: shifted 1-channel input x one stream over dz
+            elif cone is not None:
+                pool = self._dz_zero.get(key)
+                dx = pool.pop() if pool else torch.zeros_like(dz)
+                assert self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit) is not False, "visiting backward not served"
             else:
                 assert not activity or i > 0, "zero-skipping needs the first-layer fast path"
-                dx = self._zeros(hs[i].shape) if activity else None
-                src_mask = self._top_dz_mask(dz_top, hs[i], activity, last_dev) if i == L - 1 and i >= 2 else None
-                dz_in_grad = False                      # the top layer: dz staged only where the readout wrote it (False: not served)
-                if src_mask is not None:
-                    dz_in_grad = self.conv_T.backward([dz], weights[3 * i:3 * i + 3], hs[i], self.act, True, grads[3 * i:3 * i + 3],
-                                                      dz_mask=src_mask)
-                if dz_in_grad is False:
-                    dz_in_grad = self.conv_T.backward([dz], weights[3 * i:3 * i + 3], hs[i], self.act, i > 0, grads[3 * i:3 * i + 3],
-                                                      dx=dx, wl=wl_out)
-                dz = dz_in_grad
+                dx = False                              # the top layer: dz staged only where the readout wrote it (False: not served)
+                if i == L - 1 and route.top_dz_mask:
+                    tabs = self.field_tables_dev()
+                    m1 = self.conv.mask_hop(self.conv.keep_mask(last_dev, NS, self.n_nodes, tabs, key="dz_mask"), tabs)
+                    dx = self.conv_T.backward([dz], w, hs[i], self.act, True, g, dz_mask=m1)
+                if dx is False:
+                    dx = self.conv_T.backward([dz], w, hs[i], self.act, i > 0, g, dx=self._zeros(hs[i].shape) if activity else None, wl=wl_out)
             if i == L - 1:                              # the top layer is done with the readout gradient: wipe and keep it
-                self._release_top(dz_top, key, last_dev)
+                self._release_top(dz, key, last_dev)
+            elif cone is not None:                      # wipe what the layer above wrote, on the mask it visited
+                self.conv.clear_mask(dz, cone[L - 1 - i])
+                self._dz_zero.setdefault(key, []).append(dz)
             elif activity:
-                self._give_back(dz_in, wl_in)
+                self._give_back(dz, wl_in)
+            if first_done:
+                break
+            dz = dx
         if activity:                                    # the forward's buffers go back to the pool, all-zero again
             self._give_back_forward(saved)
         return grads
@@ -1777,7 +1688,7 @@ class PowerPlan(SconePlan):
     def field_tables_dev(self):
         return None
 
-    def conv_stack(self, x, weights, activity=None, last_dev=None, out_last=None):   # (neither is used: every layer stores its whole output)
+    def conv_stack(self, x, weights):
         n_layers = (len(weights) - 1) / 3
         assert n_layers % 1 == 0, "wrong number of weights"                    # TE:159-160
         hs, y0 = [x], None
@@ -1791,7 +1702,7 @@ class PowerPlan(SconePlan):
                 if i == 0 and x.shape[3] == 1:
                     y0 = torch.cat([x, g1, g2, torch.zeros_like(x)], dim=3)  # the shifted input per point, for the first layer's weight gradient
             hs.append(out)
-        return hs, y0, None
+        return hs, y0
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         hs, bh, y0 = saved.hs, saved.bh, saved.y0
