@@ -883,6 +883,53 @@ int scn_sssp_paths(int32_t n_nodes, const int32_t* adj_ptr, const int32_t* adj, 
 int scn_walk_assemble(int32_t n, const int32_t* path, const int32_t* path_len, int32_t path_cap, int32_t* walk, int32_t* walk_len,
                       int32_t walk_cap, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Teacher-forced scoring of node paths (Scone_GCN.path_step_log_probs): the steps around the batched forwards that give the model's
+ * log-probability of every node of a path given the nodes before it.  Paths are ragged like the Markov calls: path_ptr[n_paths + 1]
+ * and path_nodes[path_ptr[n_paths]], int32, on the device; position t is a flat index into path_nodes.  The step tables are those of
+ * the multi-hop calls above ([n_nodes][d]: step_node, step_edge = the DEVICE row, step_sign; deg[n_nodes]); the host builds them by its
+ * rule "flow": slots as the readout numbers them, the edge of the sorted pair, +1 where v < u (times the readout's flips).
+ * All three calls: every launch on `stream`, nothing allocated, nothing synchronises, no float atomics (the same inputs give the same
+ * bytes), n == 0 returns SCN_OK without a launch, SCN_ERR_BAD_SHAPE / SCN_ERR_BAD_ARG for a shape or pointer that cannot be served,
+ * before any launch.  Paths may have any length.
+ *
+ * scn_path_steps: once per call, one wave per path.  A position t whose successor t + 1 lies in the same path is the step
+ *   v = nodes[t] -> u = nodes[t + 1]; the outputs are flat arrays parallel to path_nodes:
+ *     slot[t]      the first j < deg[v] with step_node[v][j] == u;
+ *     row[t]       step_edge[v][slot[t]];
+ *     run[t]       the sum of step_sign over the steps t' <= t of the same path with row[t'] == row[t], added in step order: the value
+ *                  that edge's flow has after step t (repeated edges accumulate, like path_to_flow's +=, SDG:327-344);
+ *     next_same[t] the smallest t' > t of the same path with row[t'] == row[t], else INT32_MAX.
+ *   The last position of every path (no step) gets slot = row = -1, run = 0, next_same = INT32_MAX.  An id outside [0, n_nodes), a pair
+ *   that is no neighbour or a row outside [0, n_rows) lowers err[0] to t (atomicMin: the caller initialises it to INT32_MAX); nothing is
+ *   read through the bad id and the step gets slot = row = -1, run = 0, next_same = INT32_MAX.  A path of length 0 writes nothing.
+ * scn_path_slabs: one chunk of items.  Item i < n_items is (item_path[i], item_len[i] = k >= 1): the first k nodes of that path.  x
+ *   [n_slabs][n_rows][4][1] (16-byte aligned, n_items <= 4 n_slabs, ns must be 4: SCN_ERR_UNSUPPORTED otherwise): column i = the flow
+ *   of that prefix, columns at or past n_items zero.  x is zero except where a step t of the prefix (path_ptr[p] <= t < path_ptr[p] + k
+ *   - 1) with row[t] >= 0 is the last one of the prefix on its row -- next_same[t] >= path_ptr[p] + k - 1 -- which SETS
+ *   x[i / 4][row[t]][i % 4] = run[t] (an explicit 0 where the steps cancelled).  No two writers touch one word.  Two launches: the
+ *   zero fill, then one wave per item.  An item with a path outside [0, n_paths) or k outside [1, length] is a caller's error that
+ *   is only guarded against: its column stays zero.  n_items == 0 writes nothing.
+ * scn_path_score: the same chunk behind the forward, logp [n_items][d].  With t = path_ptr[p] + k - 1 the position of the prefix's
+ *   last node v, j* = slot[t] and lim = deg[v] (clamped to [0, d]):
+ *     step_logp[i] = logp[i][j*] (the bits);
+ *     step_rank[i] = the number of slots j < lim that come before j* in the order of scn_beam_step / scn_hop_select: a NaN before every
+ *                    number, then the higher value, then the lower slot -- 0 exactly when scn_hop_select with limit deg[v] chooses j*;
+ *     step_mass[i] = log sum_{j < lim} exp(logp[i][j]), the mass the model leaves on real neighbours (the padded slots keep logit 0
+ *                    inside its logsumexp, TE:288), as m + logf(sum_j expf(logp_j - m)) with m the first slot of that order, one fp32
+ *                    subtract per slot and an fp32 running sum in slot order; m itself when it is a NaN or +-inf.
+ *   An item with j* < 0 (the prefix ends its path, or a bad step), or guarded against as above, gets NaN / -1 / NaN.  One thread per
+ *   item.  SCN_ERR_UNSUPPORTED when n_items * d reaches 2^31 - 1. */
+int scn_path_steps(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t n_nodes, int32_t d, const int32_t* deg,
+                   const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows, int32_t* slot,
+                   int32_t* row, float* run, int32_t* next_same, int32_t* err, void* stream);
+int scn_path_slabs(int32_t n_items, int32_t n_slabs, const int32_t* item_path, const int32_t* item_len, int32_t n_paths,
+                   const int32_t* path_ptr, const int32_t* row, const float* run, const int32_t* next_same, int32_t n_rows, int32_t ns,
+                   float* x, void* stream);
+int scn_path_score(int32_t n_items, int32_t d, const int32_t* item_path, const int32_t* item_len, int32_t n_paths,
+                   const int32_t* path_ptr, const int32_t* path_nodes, const int32_t* slot, const int32_t* deg, int32_t n_nodes,
+                   const float* logp, float* step_logp, int32_t* step_rank, float* step_mass, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,9 +26,11 @@ class StepTables:
     the tables' device pointers as the launches take them (p_deg, p_node, p_edge, p_sign).
     rule "binary" (STM:139-147): slot j of nbrhoods[v] as it is; +1 on E_lookup[(v, u)] if that key exists, else -1 on
     E_lookup[(u, v)].  rule "dist" (STM:160, 176-187): the real neighbours of v left-aligned (the -1 padding dropped), -1 / +1 on
-    E_lookup[sorted(v, u)] by whether v > u."""
+    E_lookup[sorted(v, u)] by whether v > u.  rule "flow" (path_scores.py; path_to_flow, SDG:327-344): slot j as the readout numbers
+    it -- this project's left-aligned table, interior padding is refused --, +1 / -1 on E_lookup[sorted(v, u)] by whether v < u, times
+    flips[that edge] (the Bconds flips, caller's edge order) where there are any: the value a step adds to the flow the model reads."""
 
-    def __init__(self, nbrhoods, E_lookup, edge_perm, rule, device):
+    def __init__(self, nbrhoods, E_lookup, edge_perm, rule, device, flips=None):
         nb = np.asarray(nbrhoods, np.int64)
         if nb.ndim != 2:
             raise ValueError("nbrhoods must be a (V, D) table padded with -1")
@@ -37,8 +39,11 @@ class StepTables:
             real = nb >= 0
             order = np.argsort(~real, axis=1, kind="stable")
             nb = np.where(np.take_along_axis(real, order, 1), np.take_along_axis(nb, order, 1), -1)
+        elif rule == "flow":
+            if np.any((nb >= 0) != (np.arange(D)[None, :] < (nb >= 0).sum(axis=1)[:, None])):
+                raise ValueError("rule 'flow' needs a left-aligned nbrhoods table (the -1 padding behind a node's neighbours)")
         elif rule != "binary":
-            raise ValueError("rule must be 'binary' or 'dist'")
+            raise ValueError("rule must be 'binary', 'dist' or 'flow'")
         n = len(E_lookup)
         keys = np.fromiter((c for k in E_lookup.keys() for c in k), np.int64, 2 * n).reshape(n, 2)
         vals = np.fromiter(E_lookup.values(), np.int64, n)
@@ -66,6 +71,8 @@ class StepTables:
         E = len(edge_perm)
         if np.any(edge >= E):
             raise ValueError("E_lookup holds an edge index outside the complex's %d edges" % E)
+        if rule == "flow" and flips is not None:
+            sign = sign * np.asarray(flips, np.float64).reshape(-1)[np.maximum(edge, 0)]
         row = np.where(edge >= 0, np.asarray(edge_perm)[np.maximum(edge, 0)], -1)
         self.rule, self.n_nodes, self.width = rule, V, D
         self.h_node, self.h_edge = nb, row
@@ -84,7 +91,8 @@ def step_tables(plan, nbrhoods, E_lookup, rule):
     hit = _STEP_TABLES.get(key)
     if hit is not None and hit[0] is nbrhoods and hit[1] is E_lookup and hit[2] is plan:
         return hit[3]
-    tab = StepTables(nbrhoods, E_lookup, plan.layout.perm[1], rule, plan.device)
+    flips = getattr(getattr(plan, "bconds", None), "flips", None) if rule == "flow" else None      # (the plan's readout operand owns them)
+    tab = StepTables(nbrhoods, E_lookup, plan.layout.perm[1], rule, plan.device, flips)
     if tab.width != plan.max_deg:
         raise ValueError("nbrhoods has %d slots, the model's readout %d" % (tab.width, plan.max_deg))
     if len(_STEP_TABLES) >= 8:

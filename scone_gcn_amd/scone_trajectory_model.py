@@ -18,7 +18,7 @@ import gc
 import numpy as np
 import torch
 
-from . import _lib, multihop, ops
+from . import _lib, multihop, ops, path_scores
 from . import distributed as dp
 from .synthetic_data_gen import SparseFlows
 from .trajectory_experiments import MODEL_ACT, MODEL_FUNCS, resolve_operands
@@ -450,6 +450,30 @@ class Scone_GCN():
         tree identifiers can collide -- not reproduced).  hops < 1 raises ValueError."""
         tp = self.multi_hop_target_probs(inputs, target_nodes, nbrhoods, E_lookup, last_nodes, hops)
         return [float(np.average(tp[np.asarray(m) == 1])) for m in masks]
+
+    # ------------------------------------------------------------------ scoring observed paths: path_scores.py
+    def path_step_log_probs(self, inputs, paths, min_prefix=2, normalise=False):
+        """Teacher-forced log-likelihood of node paths, step by step: for every path p (a sequence of node ids in the caller's
+        numbering) and every k = max(min_prefix, 1) .. len(p) - 1 the model's log-probability of p[k] given the flow of p[:k] and
+        the last node p[k - 1] -- what _predict gives on paths_to_flows of every prefix (times the -flip_edges flips), without
+        building those sum(len^2) flow entries.  Returns PathScores(ptr, logp, rank, mass, prefix_len) (path_scores.PathScores):
+        per item, path-major with k ascending, logp and mass float64, rank int64 (0: the model's own choice among the real
+        neighbours; the order rule is scn_beam_step's, include/scone_hip.h), mass = log of the probability left on real neighbours;
+        normalise: logp - mass, the log-probability among the real neighbours alone.  A path shorter than that has no items.  Of
+        `inputs` only the readout operand is used (the Bconds object, for bunch the nbrhoods table); the caller's flows are neither
+        read nor written.  A step between two nodes that are no neighbours raises KeyError((a, b)) before any forward.  Chunks of
+        multi_hop_micro_batch (default: ops.forward_micro_batch) items per forward; multi_hop_skip is ignored (x is dense)."""
+        return path_scores.step_log_probs(self, inputs, paths, min_prefix, normalise)
+
+    def path_log_likelihood(self, inputs, paths, min_prefix=2, normalise=False):
+        """(ll [P] float64, n_steps [P] int64): every path's summed step log-probabilities (path_step_log_probs; added on the host
+        in fp64) and the number of steps behind the sum; a path without items has (0, 0)."""
+        return path_scores.log_likelihood(self, inputs, paths, min_prefix, normalise)
+
+    def score_paths(self, inputs, paths, mask=None, min_prefix=2, normalise=False):
+        """Held-out scores over the steps of the paths of mask (all when None): {"mean_step_logp", "perplexity" = exp(-mean),
+        "accuracy" = the share of steps with rank 0, "n_steps"}; NaN where there is no step."""
+        return path_scores.score_paths(self, inputs, paths, mask, min_prefix, normalise)
 
     # ------------------------------------------------------------------ gradient step (STM:306-310)
     def stage(self, inputs, y, idx, skip=None):

@@ -37,6 +37,7 @@ def hyperparams(args=None):
           'multi_hop_samples': 0,        # S > 0 with -multi_hop 1: also the mean 2-hop target probability estimated from S sampled paths
           'markov_order': 1,             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
           'projection': 0,               # 1: the harmonic projection baseline's experiments first (the reference's projection_model.py)
+          'path_likelihood': 0,          # not in the reference: 1 = after training, the teacher-forced scores of prefix + [target] (score_paths)
           'n_points': 400, 'n_walks': 1000,   # not in the reference (hard-coded, TE:224): the size of the -load_data 0 data set
           'walks': 'host',               # host | device: device = generate_random_walks_batched (fresh waypoints per walk on the GPU)
           'walk_metric': 'hops'}         # hops | euclid: the shortest-path metric of the generated walks
@@ -320,7 +321,9 @@ def train_model(hp=None):
     (-markov_order K, default 1) runs its five experiments first (TE:327-432) and its accuracies go to
     experiment_results["markov"].  The reference then stops (`raise Exception`, TE:433); this driver does not: it goes on to
     train the model.  With -projection 1 the harmonic projection baseline runs next (projection_experiments) and its results go to
-    experiment_results["projection"]; training follows as well."""
+    experiment_results["projection"]; training follows as well.  With -path_likelihood 1 the trained model scores every path
+    prefixes[i] + [target_nodes_all[0][i]] step by step (Scone_GCN.score_paths) over the train and the test mask:
+    experiment_results["path_likelihood"] = {"train": ..., "test": ...}."""
     from .scone_trajectory_model import Scone_GCN
     hp = hyperparams() if hp is None else hp
     inputs_all, y_all, train_mask, test_mask, shifts, G_undir, E_lookup, nbrhoods, n_nbrs, target_nodes_all, prefixes = \
@@ -390,6 +393,12 @@ def train_model(hp=None):
             tp = scone.multi_hop_target_probs_sampled(inputs_1hop, target_nodes_all[1], 2, int(hp['multi_hop_samples']))
             results["multi_hop_sampled"] = [float(np.average(tp[np.asarray(m) == 1])) for m in (train_mask, test_mask)]
             print('Multi hop sampled target probs (%d samples):' % int(hp['multi_hop_samples']), results["multi_hop_sampled"])
+    if hp.get('path_likelihood', 0) == 1:                                  # not in the reference: how likely are the observed paths, step by step
+        paths = [[int(v) for v in pre] + [int(t)] for pre, t in zip(prefixes, target_nodes_all[0])]
+        results["path_likelihood"] = {name: scone.score_paths(inputs_1hop, paths, m) for name, m in (("train", train_mask), ("test", test_mask))}
+        for name, r in results["path_likelihood"].items():
+            print('Path likelihood ({}): mean step log-prob {:.6f} -- perplexity {:.4f} -- step acc {:.3f} -- steps {}'.format(
+                name, r["mean_step_logp"], r["perplexity"], r["accuracy"], r["n_steps"]))
     if markov_results is not None:
         results["markov"] = markov_results
     if projection_results is not None:
