@@ -554,6 +554,18 @@ int scn_plan_gather_stats(int32_t n, const int32_t* rowptr, const int32_t* col, 
  * it has the device to itself for its ~60 us (all workgroups resident together); scn_small_step_pairing(1) turns the form off
  * process-wide (0: back on, the default).  The workspace size covers both forms. */
 int scn_small_step_pairing(int32_t mode);
+/* The form a scn_small_step launch of n_traj (= n_slabs * ns) trajectories on this pair of handles takes, from the host function the
+ * launch itself selects its kernel instance and LDS layout with.  out[0 .. SCN_SMALL_LAYOUT_FIELDS) (n_out >= that; all zero when
+ * out[0] is):
+ *   [0] supported (operator and size only; n_layers, hidden, max_deg, max_items are scn_small_step_supported's)
+ *   [1] waves per workgroup (12 up to 24 row tiles, else 8)   [2] 16-row tiles per wave   [3] instance: tiles a wave keeps resident
+ *   [4] paired (scn_small_step_pairing and the device's CU count included)
+ *   [5] n_ovf, [6] n_ovf_t: operator entries past a row's twelfth, of conv and conv_t
+ *   [7] ovf_lds: the layout has room for the longer list   [8] y_lds: and for the first layer's shifted input
+ *   [9] ovf_in_kernel: the instance reads the tails from the list in LDS (else from memory)
+ *   [10] same_t: conv_t is conv   [11] lds_bytes of the launch */
+#define SCN_SMALL_LAYOUT_FIELDS 12
+int scn_small_step_layout(scn_conv_t conv, scn_conv_t conv_t, int32_t n_traj, int32_t* out, int32_t n_out);
 int scn_small_step_supported(scn_conv_t conv, int32_t n_layers, int32_t hidden, int32_t max_deg, int32_t max_items);
 size_t scn_small_step_workspace(int32_t n_edges, int32_t n_traj, int32_t n_layers);
 int scn_small_step(scn_conv_t conv, scn_conv_t conv_t, int32_t n_slabs, int32_t ns, int32_t n_layers, int32_t hidden,

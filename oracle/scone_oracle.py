@@ -44,7 +44,7 @@ def leaky_relu(x):
     return np.where(x >= 0, x, 0.01 * x)          # TE:133-134
 
 
-ACTIVATIONS = {"tanh": tanh, "relu": relu, "leaky_relu": leaky_relu}
+ACTIVATIONS = {"tanh": tanh, "relu": relu, "leaky_relu": leaky_relu, "none": lambda x: x}    # none: the kernels' SCN_ACT_NONE
 
 
 def act_grad(name, z):
@@ -61,6 +61,8 @@ def act_grad(name, z):
         return np.where(z > 0, 1.0, np.where(z == 0, 0.5, 0.0))
     if name == "leaky_relu":
         return np.where(z >= 0, 1.0, 0.01)
+    if name == "none":
+        return np.ones_like(z)
     raise ValueError(name)
 
 

@@ -91,6 +91,8 @@ struct SmallLds {
     size_t off_w, off_misc, off_x, off_red, off_y, off_ovf, total;
 };
 __host__ __device__ static inline int small_waves(int n_edges) { return ((n_edges + 15) >> 4) <= 24 ? 12 : 8; }
+// Which instances can read a row's entries past the twelfth from the list in LDS at all (small_step_kernel's OVF; small_form)
+__host__ __device__ constexpr bool small_ovf_instance(int maxt, int waves, bool paired) { return waves == 8 && (paired || maxt <= 8); }
 __host__ __device__ static inline SmallLds small_lds(int n_edges, int n_ovf) {
     const int waves = small_waves(n_edges);
     SmallLds L;
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_step_kernel(SmallArgs a) {
     float* const ovf_l = (float*)(smem + lay.off_ovf);          // [n_ovf][3] the operator's overflow list, when there is room (lay.ovf_lds)
     // (the twelve-wave kernels of |E| <= 384 have no register to spare for it and measured no gain, small_lds; the nine-tile instance
     //  of |E| > 1024 has neither the registers nor the LDS)
-    constexpr bool OVF = WAVES == 8 && (PAIRED || MAXT <= 8);
+    constexpr bool OVF = small_ovf_instance(MAXT, WAVES, PAIRED);
     const float* const ovf = OVF && lay.ovf_lds ? ovf_l : nullptr;
     const int half = PAIRED ? (blockIdx.x >> 3) & 1 : 0;
     const int n = PAIRED ? (blockIdx.x >> 4) * 8 + (blockIdx.x & 7) : blockIdx.x;
@@ -900,6 +902,46 @@ static bool small_paired(int n_edges, int n_traj) {
     return g_small_pairing.load() == 0 && small_waves(n_edges) == 8 && small_blocks(n_edges) >= 2 && 2 * n_traj <= small_cus();
 }
 
+// The form a launch takes -- kernel instance and LDS layout -- from the complex's size, the longer of the two overflow lists and
+// whether two workgroups share a trajectory.  ONE function for the launch (small_step_impl), the LDS limits raised at create time
+// (small_prepare) and the query (scn_small_step_layout).  Eight waves run from 25 tiles up, four tiles per wave at least: the
+// unpaired instances are 1 / 2 (twelve waves) and 6 / 8 / 9.
+struct SmallForm {
+    int waves, tiles_per_wave, instance;              // instance: small_step_kernel's MAXT
+    bool paired, ovf_in_kernel;                       // ovf_in_kernel: the tails past a row's twelfth entry are read from the list in LDS
+    SmallLds lay;
+};
+static SmallForm small_form(int n_edges, int n_ovf, bool paired) {
+    SmallForm f;
+    f.lay = small_lds(n_edges, n_ovf);
+    f.waves = small_waves(n_edges);
+    f.tiles_per_wave = ((f.lay.epad >> 4) + f.waves - 1) / f.waves;
+    f.paired = paired;
+    if (paired) f.instance = std::min(std::max((small_blocks(n_edges) + 1) / 2, 2), 5);
+    else if (f.waves == 12) f.instance = f.tiles_per_wave <= 1 ? 1 : 2;
+    else f.instance = f.tiles_per_wave <= 6 ? 6 : f.tiles_per_wave <= 8 ? 8 : SM_MAXT;
+    f.ovf_in_kernel = small_ovf_instance(f.instance, f.waves, paired) && f.lay.ovf_lds;
+    return f;
+}
+// fn(MAXT, WAVES, PAIRED as integral constants) of the form's instance; every instance the library has is named here
+template <typename F>
+static int small_with_instance(const SmallForm& f, F&& fn) {
+#define SCN_SMALL_INSTANCE(T, WV, P) \
+    if (f.instance == T && f.waves == WV && f.paired == P) \
+        return fn(std::integral_constant<int, T>{}, std::integral_constant<int, WV>{}, std::integral_constant<bool, P>{})
+    SCN_SMALL_INSTANCE(1, 12, false);
+    SCN_SMALL_INSTANCE(2, 12, false);
+    SCN_SMALL_INSTANCE(6, 8, false);
+    SCN_SMALL_INSTANCE(8, 8, false);
+    SCN_SMALL_INSTANCE(SM_MAXT, 8, false);
+    SCN_SMALL_INSTANCE(2, 8, true);
+    SCN_SMALL_INSTANCE(3, 8, true);
+    SCN_SMALL_INSTANCE(4, 8, true);
+    SCN_SMALL_INSTANCE(5, 8, true);
+#undef SCN_SMALL_INSTANCE
+    return SCN_ERR_UNSUPPORTED;
+}
+
 // Called by scn_conv_create* (scn_conv.hip) on every new handle: an operator scn_small_step can serve gets its entry pack
 // (col, val_lower, val_upper, 0) on the device HERE, at create time, and the kernel instance of its size gets its LDS limit raised --
 // so that scn_small_step itself neither allocates nor copies nor synchronises, like every other launch of the library (its first call
@@ -959,25 +1001,13 @@ int small_prepare(scn_conv_s* c) {
     c->plan.allocs.push_back(dv);
     if (!ov.empty()) SCN_HIP_TRY(hipMemcpy(dv, ov.data(), ov.size() * sizeof(float4), hipMemcpyHostToDevice));
     c->small_ovf = dv;
-    {                                                           // (the kernels' LDS limit: whatever a launch's layout comes to, overflow list included)
-        const int waves = small_waves(c->n_rows);
-        const int tiles_per_wave = ((lay.epad >> 4) + waves - 1) / waves;
-        int st;
-        if (waves == 12) st = tiles_per_wave <= 1 ? small_raise_lds<1, 12>((size_t)160 * 1024) : small_raise_lds<2, 12>((size_t)160 * 1024);
-        else if (tiles_per_wave <= 3) st = small_raise_lds<3, 8>((size_t)160 * 1024);
-        else if (tiles_per_wave <= 6) st = small_raise_lds<6, 8>((size_t)160 * 1024);
-        else if (tiles_per_wave <= 8) st = small_raise_lds<8, 8>((size_t)160 * 1024);
-        else st = small_raise_lds<SM_MAXT, 8>((size_t)160 * 1024);
+    // the kernels' LDS limit: whatever a launch's layout comes to, overflow list included; both forms, the pairing is a launch's choice
+    auto raise = [](auto t, auto wv, auto p) { return small_raise_lds<decltype(t)::value, decltype(wv)::value, decltype(p)::value>((size_t)160 * 1024); };
+    int st = small_with_instance(small_form(c->n_rows, 0, false), raise);
+    if (st != SCN_OK) return st;
+    if (small_waves(c->n_rows) == 8 && small_blocks(c->n_rows) >= 2) {
+        st = small_with_instance(small_form(c->n_rows, 0, true), raise);
         if (st != SCN_OK) return st;
-        if (waves == 8 && small_blocks(c->n_rows) >= 2) {
-            switch ((small_blocks(c->n_rows) + 1) / 2) {
-                case 2: st = small_raise_lds<2, 8, true>((size_t)160 * 1024); break;
-                case 3: st = small_raise_lds<3, 8, true>((size_t)160 * 1024); break;
-                case 4: st = small_raise_lds<4, 8, true>((size_t)160 * 1024); break;
-                default: st = small_raise_lds<5, 8, true>((size_t)160 * 1024); break;
-            }
-            if (st != SCN_OK) return st;
-        }
     }
     return SCN_OK;
 }
@@ -1012,6 +1042,23 @@ size_t scn_small_step_workspace(int32_t n_edges, int32_t n_traj, int32_t n_layer
     const size_t part = ((size_t)2 * n_traj * small_pw(n_layers) * 4 + 15) / 16 * 16;     // (sized for the paired form: 2 N partials,
     const size_t flags = (size_t)n_traj * 4 * SM_MAX_LAYERS * 4;                          //  hand-over buffers of the size of hs, flags)
     return hs + ys + part + (size_t)2 * n_traj * 8 + hs + flags + 256;
+}
+
+int scn_small_step_layout(scn_conv_t conv, scn_conv_t conv_t, int32_t n_traj, int32_t* out, int32_t n_out) {
+    if (!conv || !conv_t || !out || n_out < SCN_SMALL_LAYOUT_FIELDS || n_traj <= 0) return SCN_ERR_BAD_ARG;
+    for (int k = 0; k < n_out; ++k) out[k] = 0;
+    if (!small_shape(conv) || !small_shape(conv_t) || conv_t->n_rows != conv->n_rows) return SCN_OK;
+    if (conv->n_rows > 16 * 8 * SM_MAXT || !conv->small_pack || !conv_t->small_pack) return SCN_OK;
+    if (small_lds(conv->n_rows, 0).total > 160 * 1024) return SCN_OK;
+    const int E = conv->n_rows;
+    const SmallForm f = small_form(E, std::max(conv->small_n_ovf, conv_t->small_n_ovf), small_paired(E, n_traj));
+    out[0] = 1;
+    out[1] = f.waves; out[2] = f.tiles_per_wave; out[3] = f.instance; out[4] = f.paired ? 1 : 0;
+    out[5] = conv->small_n_ovf; out[6] = conv_t->small_n_ovf;
+    out[7] = f.lay.ovf_lds ? 1 : 0; out[8] = f.lay.y_lds ? 1 : 0; out[9] = f.ovf_in_kernel ? 1 : 0;
+    out[10] = conv_t == conv ? 1 : 0;
+    out[11] = (int32_t)f.lay.total;
+    return SCN_OK;
 }
 
 int scn_small_step_pairing(int32_t mode) {
@@ -1079,24 +1126,16 @@ static int small_step_impl(scn_conv_t conv, scn_conv_t conv_t, int32_t n_slabs, 
         // launch's tag in the very cell a workgroup polls is a 2^-32 event per cell.
         a.tag = (int32_t)(((uint32_t)(g_small_tag.fetch_add(1) + 1) * 2654435761u) | 1u);
     }
-    const SmallLds lay = small_lds(E, std::max(a.n_ovf, a.n_ovf_t));
+    const SmallForm form = small_form(E, std::max(a.n_ovf, a.n_ovf_t), paired);
     hipStream_t s = (hipStream_t)stream;
-    const int waves = small_waves(E);
-    const int tiles_per_wave = ((lay.epad >> 4) + waves - 1) / waves;
-#define SCN_LAUNCH_SMALL(T, WV) hipLaunchKernelGGL((small_step_kernel<T, WV, false>), dim3(N), dim3(64 * WV), lay.total, s, a)
-#define SCN_LAUNCH_PAIRED(T) hipLaunchKernelGGL((small_step_kernel<T, 8, true>), dim3(16 * ((N + 7) / 8)), dim3(512), lay.total, s, a)
-    if (paired) {
-        switch ((small_blocks(E) + 1) / 2) {
-            case 2: SCN_LAUNCH_PAIRED(2); break;
-            case 3: SCN_LAUNCH_PAIRED(3); break;
-            case 4: SCN_LAUNCH_PAIRED(4); break;
-            default: SCN_LAUNCH_PAIRED(5); break;
-        }
-    } else if (waves == 12) { if (tiles_per_wave <= 1) SCN_LAUNCH_SMALL(1, 12); else SCN_LAUNCH_SMALL(2, 12); }
-    else if (tiles_per_wave <= 3) SCN_LAUNCH_SMALL(3, 8);
-    else if (tiles_per_wave <= 6) SCN_LAUNCH_SMALL(6, 8);
-    else if (tiles_per_wave <= 8) SCN_LAUNCH_SMALL(8, 8);
-    else SCN_LAUNCH_SMALL(SM_MAXT, 8);
+    const int st = small_with_instance(form, [&](auto t, auto wv, auto p) {
+        constexpr int T = decltype(t)::value, WV = decltype(wv)::value;
+        constexpr bool P = decltype(p)::value;
+        const dim3 grid(P ? 16 * ((N + 7) / 8) : N);
+        hipLaunchKernelGGL((small_step_kernel<T, WV, P>), grid, dim3(64 * WV), form.lay.total, s, a);
+        return (int)SCN_OK;
+    });
+    if (st != SCN_OK) return st;
     SCN_LAUNCH_CHECK();
     SmallReduce r{};
     r.n_traj = paired ? 2 * N : N; r.pw = pw;

@@ -288,8 +288,9 @@ def test_small_step_refuses_what_it_does_not_serve(cfg1, sc1):
 
 @pytest.mark.parametrize("n_pts,n_traj", [(130, 37), (250, 12), (80, 5), (440, 9), (200, 11), (330, 100), (250, 160)])
 def test_small_step_on_other_complex_sizes_against_the_layer_by_layer_kernels(n_pts, n_traj):
-    """The kernel's instances by row tiles per wave: |E| ~ 320 (three, the drifter complex's size), ~ 620 (six), ~ 190 (two for
-    some waves, one for others) and ~ 1100 (nine: the largest complex whose two activation buffers fit the LDS).  Above 384 edges
+    """The kernel's instances by row tiles per wave: |E| ~ 320 and ~ 190 (twelve waves with two tiles or one each: up to 384 edges
+    no wave has more; ~ 320 is the drifter complex's size), ~ 620 (six) and ~ 1100 (nine: the largest complex whose two
+    activation buffers fit the LDS).  Above 384 edges
     and up to 128 trajectories two workgroups share a trajectory (alternating blocks of eight row tiles: two blocks each at
     |E| ~ 500, three at ~ 620, four at ~ 820 with a whole batch of 100 -- 200 workgroups resident together --, five at ~ 1100);
     160 trajectories at |E| ~ 620 are past that form's limit and run one workgroup each."""
@@ -373,3 +374,100 @@ def test_host_batches_through_the_replayed_graph_take_the_one_launch_step():
         gmax = np.abs(gb).max()
         assert gmax > 1e-5
         assert abs(la - lb) <= 1e-6 * max(1.0, abs(lb)) and np.abs(ga - gb).max() <= 2e-6 * max(gmax, 1.0) and np.abs(wa - wb).max() <= 5e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the real drifter complex (bench.py's configs[2]: tests/golden/buoy.npz, 133 nodes / 320 edges, 160 training trajectories)
+# ------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def buoy():
+    import os
+    from scone_gcn_amd import buoy_data as bd
+    from scone_gcn_amd import synthetic_data_gen as g
+    from scone_gcn_amd.complex import SimplicialComplex
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    gld = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "buoy.npz"))
+    trajs = [gld["traj_nodes"][gld["traj_ptr"][i]:gld["traj_ptr"][i + 1]].astype(int).tolist() for i in range(len(gld["traj_ptr"]) - 1)]
+    cx, paths, flows, choice, last, tnodes, train_mask, test_mask = bd.buoy_dataset(
+        gld["elist"].astype(np.int64), gld["tlist"].astype(np.int64), gld["coords"], trajs)
+    sc = SimplicialComplex(cx)
+    B1, B2 = (m.toarray() for m in g.incidence_matrices(cx))
+    nb, _ = so.neighborhoods(cx.edges, cx.n_nodes)
+    return dict(cx=cx, sc=sc, flows=flows, X=flows.todense().astype(np.float64), last=last, y=so.onehot_targets(choice, sc.max_degree),
+                train_mask=np.asarray(train_mask).astype(int), B1=B1, B2=B2, Bc=so.make_Bconds(B1, nb))
+
+
+def _buoy_net(b, model, scale, graph, weight_decay):
+    from scone_gcn_amd import scone_trajectory_model as stm
+    from scone_gcn_amd import trajectory_experiments as te
+    shifts, readout, _ = te.setup_from_complex(b["sc"], model)
+    inputs = [readout, b["last"], b["flows"]]
+    stm.reseed(1030)
+    net = stm.Scone_GCN(1, 1e-3, 160, weight_decay, verbose=False)
+    net.use_graph = graph
+    net.setup(te.MODEL_FUNCS[model], [(3, 16)] * 3, shifts, inputs, b["y"], None, b["train_mask"], model_type=model)
+    with torch.no_grad():
+        for w in net.weights:
+            w.mul_(scale)
+    return net, inputs
+
+
+def _split(flat, like):
+    out, off = [], 0
+    for g in like:
+        out.append(flat[off:off + g.size].reshape(g.shape))
+        off += g.size
+    return out
+
+
+@pytest.mark.parametrize("graph", [True, False])
+def test_drifter_complex_three_adam_steps_against_the_oracle(buoy, graph):
+    """Scone_GCN.grad_step_staged on the drifter complex with its 160 training trajectories as one batch, weight decay 5e-5: the
+    one-launch step (|E| = 320: a twelve-wave kernel), graph-replayed with the optimiser step inside the summing launch and eager,
+    against oracle.scone_loss_and_grad + oracle.Adam step by step -- loss and every gradient tensor within 1e-5, the weights
+    within 1e-5 after each of three steps."""
+    from scone_gcn_amd import ops
+    b, wd = buoy, 5e-5
+    idx = np.nonzero(b["train_mask"])[0]
+    assert len(idx) == 160 and b["cx"].n_edges == 320
+    net, inputs = _buoy_net(b, "scone", 30.0, graph, wd)             # 0.3 randn: the scale of test_gpu_parity._rand_weights
+    L_lo, L_up = so.scone_shifts(b["B1"], b["B2"])
+    adam = so.Adam([w.detach().cpu().numpy().astype(np.float64) for w in net.weights], 1e-3)
+    staged = net.stage(inputs, b["y"], idx)
+    for i in range(3):
+        ref_loss, ref_g = so.scone_loss_and_grad(adam.x, L_lo, L_up, b["Bc"], b["last"], b["X"], b["y"], b["train_mask"], wd)
+        data_g = [g - 2 * wd * w for g, w in zip(ref_g, adam.x)]     # the ridge term joins the gradient in the optimiser launch
+        loss = float(net.grad_step_staged(inputs, staged, 160)) + wd * so.ridge(adam.x)
+        got = _split(net._flat_g.cpu().numpy().astype(np.float64), ref_g)
+        worst = max(_maxdiff(a, r) for a, r in zip(got, data_g))
+        adam.update(i, ref_g)
+        w_err = max(_maxdiff(a.detach().cpu().numpy(), r) for a, r in zip(net.weights, adam.x))
+        print("drifter step %d (graph %s): loss %.3g, gradients %.3g, weights %.3g" % (i, graph, abs(loss - ref_loss) / max(1.0, abs(ref_loss)), worst, w_err))
+        assert min(float(np.abs(g).max()) for g in data_g) >= 0.1
+        assert abs(loss - ref_loss) <= TOL * max(1.0, abs(ref_loss)), i
+        assert worst <= TOL and w_err <= 1e-5, i
+    assert (len(net._graphs) > 0) == graph
+    _, _, table = _step(net, inputs, b["y"], idx)
+    assert any(k.startswith("small_step") for k in table) and not any(k.startswith("conv_") for k in table), list(table)
+
+
+def test_drifter_complex_with_the_ebli_pair(buoy):
+    """One gradient step with (L1, L1^2) on the drifter complex: rows of L1^2 -- several dozen entries -- in a twelve-wave kernel,
+    their tails read from memory."""
+    from scone_gcn_amd import ops
+    b = buoy
+    idx = np.nonzero(b["train_mask"])[0]
+    net, inputs = _buoy_net(b, "ebli", 3.0, False, 0.0)
+    plan = net._plan(inputs)
+    assert type(plan) is ops.SconePlan and int(np.diff(plan._pattern.indptr).max()) > 24
+    loss, g, table = _step(net, inputs, b["y"], idx)
+    assert any(k.startswith("small_step") for k in table) and not any(k.startswith("conv_") for k in table), list(table)
+    w = [a.detach().cpu().numpy().astype(np.float64) for a in net.weights]
+    S1, S2 = so.ebli_shifts(b["B1"], b["B2"])
+    ref_loss, ref_g = so.scone_loss_and_grad(w, S1, S2, b["Bc"], b["last"], b["X"], b["y"], b["train_mask"], 0.0, "leaky_relu")
+    worst = max(_maxdiff(a, r) for a, r in zip(_split(g.astype(np.float64), ref_g), ref_g))
+    print("drifter ebli: loss %.3g, gradients %.3g" % (abs(loss - ref_loss) / max(1.0, abs(ref_loss)), worst))
+    assert abs(loss - ref_loss) <= TOL * max(1.0, abs(ref_loss)) and worst <= TOL
