@@ -603,6 +603,73 @@ int scn_masked_ce(int64_t n, const float* logp, const float* y, float scale, flo
 int scn_masked_ce_begin(int64_t n, const float* logp, const float* y, float scale, float* d_logp, double* loss,
                         int32_t overwrite, float* zero_buf, int64_t zero_n, void* stream);
 
+/* The tail of a micro-batch in two launches instead of nine (csrc/scn_readout.hip, csrc/scn_step_epilogue.inc).
+ *
+ * scn_readout_step = scn_readout_forward, the scaling d_logp = y * scale of scn_masked_ce_begin and scn_readout_backward's d_logits
+ *   and dz in ONE launch, one wave per trajectory; every output has the separate launches' bits.  dz must be a buffer that is
+ *   all-zero (dz_is_zero = 1; every other value is SCN_ERR_UNSUPPORTED, as are max_deg > 64 and c > 64: the caller runs the separate
+ *   launches).  zero_buf / zero_n as in scn_masked_ce_begin: zeroed by workgroup 0; nothing else in the launch touches it.  NOT done
+ *   here: the loss sum and the readout's weight gradient -- they are jobs of scn_step_epilogue.
+ *
+ * scn_step_epilogue runs everything a micro-batch deferred, each job the body of its stand-alone kernel on the workgroups that launch
+ *   had (a workgroup finds its job by its index, csrc/scn_step_ranges.h; no workgroup waits for another), each result its bits:
+ *     loss         loss[0] = overwrite ? s : loss[0] + s, s summed as scn_masked_ce does (loss = NULL: absent)
+ *     readout_dw   d_w_last += sum dl x bh as scn_readout_backward's second launch (rd_d_w = NULL: absent)
+ *     reduce[k]    the weight-gradient reduce of a backward that left its partials in its workspace (the _partial entries below)
+ *     first        the first layer's reduce of scn_conv_backward_fused_first_from_y_visit_partial (first_form: 0 absent, 1: 32 channels)
+ *     rc_*         scn_readout_clear_dz (rc_dz = NULL: absent; max_deg <= 64)
+ *     clear[k]     scn_clear_mask of one tensor
+ *   More than SCN_EPI_MAX_REDUCES / SCN_EPI_MAX_CLEARS jobs, or a job no stand-alone launch would take: an error before any launch.
+ *   conv: the operator whose plan the masked clears walk (may be NULL without a masked clear).
+ *
+ * scn_conv_backward_visit_partial / scn_conv_backward_fused_first_from_y_visit_partial = the entries without the suffix, less their
+ *   reduce launches: the workspace keeps the partial sums ([n_wg][c_aux][3 c_dz] at its head; the fused-first form [n_wg][96] behind
+ *   [n_wg][3 ch ch]) until a scn_step_epilogue on the same stream has run, and *n_wg_out is the launch's workgroup count. */
+#define SCN_EPI_MAX_REDUCES 4
+#define SCN_EPI_MAX_CLEARS 4
+typedef struct {
+    const float* partial;           /* [n_wg][c_aux][3 * c_dz] */
+    int32_t n_wg, c_aux, c_dz;
+    float* dW[3];
+} scn_epi_reduce;
+typedef struct {
+    float* tensor;                  /* [n_slabs][n_rows][ns][channels], 16-byte aligned */
+    const uint32_t* mask;
+    int32_t n_slabs, ns, channels;
+} scn_epi_clear;
+typedef struct {
+    /* loss */
+    int64_t loss_n; const float* logp; const float* y; float scale; double* loss; int32_t overwrite;
+    /* readout_dw */
+    int32_t rd_nd, rd_c; const float* rd_dl; const float* rd_bh; float* rd_d_w;
+    /* reduces */
+    int32_t n_reduce; scn_epi_reduce reduce[SCN_EPI_MAX_REDUCES];
+    int32_t first_form; const float* first_partial; int32_t first_n_wg; float* first_dW[3];
+    /* the readout gradient's clear */
+    int32_t rc_n_slabs, rc_ns, rc_n_edges, rc_c, rc_max_deg; const int32_t* rc_nbr; const int32_t* rc_last_nodes;
+    const int32_t* rc_inc_ptr; const int32_t* rc_inc_edge; const int32_t* rc_edge_nodes; float* rc_dz;
+    /* masked clears */
+    int32_t n_clear; scn_epi_clear clear[SCN_EPI_MAX_CLEARS];
+} scn_step_epilogue_desc;
+int scn_readout_step(int32_t n_slabs, int32_t ns, int32_t n_edges, int32_t c, const float* H, const float* w_last, const int32_t* nbr,
+                     int32_t n_nodes, int32_t max_deg, const int32_t* last_nodes, const int32_t* inc_ptr, const int32_t* inc_edge,
+                     const float* inc_sign, const int32_t* edge_nodes, const float* y, float scale, int32_t act, float* bh,
+                     float* logits, float* logp, float* d_logp, float* d_logits, float* dz, int32_t dz_is_zero, float* zero_buf,
+                     int64_t zero_n, void* stream);
+int scn_step_epilogue(scn_conv_t conv, const scn_step_epilogue_desc* desc, void* stream);
+/* The two reduces a backward runs behind its kernel, as launches of their own (what the epilogue's jobs are tested against):
+ * dW[slot][ca][cc] += sum over n_wg partials [c_aux][3 * c_dz] (a NULL slot is skipped), and the first layer's dW[slot][cc] += sum over
+ * n_wg partials [96] (form 1: 32 channels; 2: the slab-pair form, 16). */
+int scn_dw_reduce(const float* partial, int32_t n_wg, int32_t c_aux, int32_t c_dz, float* const* dW, void* stream);
+int scn_dw_first_reduce(const float* partial, int32_t n_wg, int32_t form, float* const* dW, void* stream);
+int scn_conv_backward_visit_partial(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                                    const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, void* workspace,
+                                    size_t workspace_bytes, const uint32_t* visit, int32_t* n_wg_out, void* stream);
+int scn_conv_backward_fused_first_from_y_visit_partial(scn_conv_t conv_t, int32_t n_slabs, int32_t ns, const float* dz,
+                                                       const float* const* W, const float* const* W_first, int32_t channels,
+                                                       int32_t act, const float* y, void* workspace, size_t workspace_bytes,
+                                                       const uint32_t* visit, int32_t* n_wg_out, void* stream);
+
 /* Fused Adam + ridge step on the flat parameter buffer (jax.experimental.optimizers.adam as driven by
  * STM:300-326; ridge term of STM:54-56):   g' = g * g_scale + 2*weight_decay*w ; m,v EMA ;
  *   w -= lr * (m / (1 - b1^(i+1))) / (sqrt(v / (1 - b2^(i+1))) + eps)                                */

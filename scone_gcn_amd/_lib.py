@@ -41,6 +41,29 @@ class GroupDesc(ctypes.Structure):
                 ("nnz", c_i64), ("rowptr", c_void_p), ("col", c_void_p), ("val0", c_void_p), ("val1", c_void_p)]
 
 
+SCN_EPI_MAX_REDUCES = 4           # jobs of each kind one scn_step_epilogue takes
+SCN_EPI_MAX_CLEARS = 4
+
+
+class EpiReduce(ctypes.Structure):             # scn_epi_reduce
+    _fields_ = [("partial", c_void_p), ("n_wg", c_i32), ("c_aux", c_i32), ("c_dz", c_i32), ("dW", c_void_p * 3)]
+
+
+class EpiClear(ctypes.Structure):              # scn_epi_clear
+    _fields_ = [("tensor", c_void_p), ("mask", c_void_p), ("n_slabs", c_i32), ("ns", c_i32), ("channels", c_i32)]
+
+
+class StepEpilogueDesc(ctypes.Structure):      # scn_step_epilogue_desc (device pointers; zero-initialised = every job absent)
+    _fields_ = [("loss_n", c_i64), ("logp", c_void_p), ("y", c_void_p), ("scale", c_f32), ("loss", c_void_p), ("overwrite", c_i32),
+                ("rd_nd", c_i32), ("rd_c", c_i32), ("rd_dl", c_void_p), ("rd_bh", c_void_p), ("rd_d_w", c_void_p),
+                ("n_reduce", c_i32), ("reduce", EpiReduce * SCN_EPI_MAX_REDUCES),
+                ("first_form", c_i32), ("first_partial", c_void_p), ("first_n_wg", c_i32), ("first_dW", c_void_p * 3),
+                ("rc_n_slabs", c_i32), ("rc_ns", c_i32), ("rc_n_edges", c_i32), ("rc_c", c_i32), ("rc_max_deg", c_i32),
+                ("rc_nbr", c_void_p), ("rc_last_nodes", c_void_p), ("rc_inc_ptr", c_void_p), ("rc_inc_edge", c_void_p),
+                ("rc_edge_nodes", c_void_p), ("rc_dz", c_void_p),
+                ("n_clear", c_i32), ("clear", EpiClear * SCN_EPI_MAX_CLEARS)]
+
+
 # name -> (restype, argtypes); every name here must be exported by the library and declared in the header
 SIGNATURES = {
     "scn_version": (ctypes.c_int, []),
@@ -233,6 +256,17 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_void_p]),
     "scn_masked_ce_begin": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_f32, c_void_p, c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+    "scn_readout_step": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_f32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
+    "scn_step_epilogue": (ctypes.c_int, [c_void_p, ctypes.POINTER(StepEpilogueDesc), c_void_p]),
+    "scn_dw_reduce": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, ctypes.POINTER(c_void_p), c_void_p]),
+    "scn_dw_first_reduce": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), c_void_p]),
+    "scn_conv_backward_visit_partial": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
+                                                       c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_size_t, c_void_p, P_i32, c_void_p]),
+    "scn_conv_backward_fused_first_from_y_visit_partial": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),
+                                                                          ctypes.POINTER(c_void_p), c_i32, c_i32, c_void_p, c_void_p,
+                                                                          c_size_t, c_void_p, P_i32, c_void_p]),
     "scn_adam_step": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,
                                      c_i32, c_f32, c_f32, c_void_p]),
     "scn_adam_step_dev": (ctypes.c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_f32, c_f32, c_f32,

@@ -257,7 +257,12 @@ int blocked_backward(scn_conv_s* c, const BwdLaunch& a) {
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.dx_partial, W[0], W[1], W[2], a.aux, a.dx, partial, L.nr, L.nc,
                               n_slabs, wl, nullptr, NO_FIRSTW, NO_KEEP, 0, nullptr);
     });
-    return st_k != SCN_OK ? st_k : reduce_dw(partial, L.n_wg(), c_aux, cd, a.dW, a.st);
+    if (st_k != SCN_OK) return st_k;
+    if (a.defer_n_wg) {
+        *a.defer_n_wg = L.n_wg();
+        return SCN_OK;
+    }
+    return reduce_dw(partial, L.n_wg(), c_aux, cd, a.dW, a.st);
 }
 
 // Backward of the layer that follows the first one, fused with the first layer's weight gradient (bwd_c32_first and its kin).
@@ -272,10 +277,9 @@ size_t blocked_backward_first_workspace(const scn_conv_s* c, int n_slabs, int ns
 }
 
 // dW_first[slot][cc] of the slab-pair form: partial [b][slot * 32 + 16 s + cc], the two slabs s folded here (fixed order)
-__global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* __restrict__ partial, int n_partials,
-                                                                  float* __restrict__ dW0, float* __restrict__ dW1,
-                                                                  float* __restrict__ dW2) {
-    const int o = blockIdx.x, lane = threadIdx.x;                 // o = slot * 16 + cc
+__device__ __forceinline__ void dw_first_reduce_pair_body(int o, int lane, const float* __restrict__ partial, int n_partials,
+                                                          float* __restrict__ dW0, float* __restrict__ dW1, float* __restrict__ dW2) {
+    // o = slot * 16 + cc
     const int slot = o >> 4, cc = o & 15;
     float s = 0.f;
     for (int b = lane; b < n_partials; b += 64) s += partial[(size_t)b * 96 + slot * 32 + cc] + partial[(size_t)b * 96 + slot * 32 + 16 + cc];
@@ -285,6 +289,11 @@ __global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* _
         float* d = slot == 0 ? dW0 : (slot == 1 ? dW1 : dW2);
         d[cc] += s;
     }
+}
+__global__ __launch_bounds__(64) void dw_first_reduce_pair_kernel(const float* __restrict__ partial, int n_partials,
+                                                                  float* __restrict__ dW0, float* __restrict__ dW1,
+                                                                  float* __restrict__ dW2) {
+    dw_first_reduce_pair_body(blockIdx.x, threadIdx.x, partial, n_partials, dW0, dW1, dW2);
 }
 
 int blocked_backward_first(scn_conv_s* c, const BwdFirstLaunch& a) {
@@ -308,6 +317,10 @@ int blocked_backward_first(scn_conv_s* c, const BwdFirstLaunch& a) {
         return launch_checked(k, L.grid, dim3(BK_THREADS), lds, a.st, L.P, a.dz, a.y, W[0], W[1], W[2], a.W_first ? nullptr : a.aux, nullptr, partial,
                               L.nr, L.nc, n_slabs, wl, partial_first, fw, NO_KEEP, 0, nullptr);
     });
+    if (st_k == SCN_OK && a.defer_n_wg) {
+        *a.defer_n_wg = n_wg;
+        return SCN_OK;
+    }
     if (st_k == SCN_OK) st_k = reduce_dw(partial, n_wg, ch, ch, a.dW, a.st);
     if (st_k != SCN_OK) return st_k;
     if (ch == 32)

@@ -180,14 +180,15 @@ __global__ __launch_bounds__(256) void clear_list_kernel(PlanDev P, WorkList wl,
 // past n_slabs names no slab).  Plain 16-byte vector stores, no atomics; a workgroup walks a listed block's words with scalar loads.
 // The workgroup's blocks b = blockIdx.x + k * gridDim.x are tested FIRST, one per thread with all loads in flight together (256 per
 // pass), and the non-empty ones listed in LDS; only those are then walked (a zero store is the same in any order).
-__global__ __launch_bounds__(256) void clear_mask_kernel(PlanDev P, KeepMask km, float* __restrict__ T, int n_rows, int n_slabs,
-                                                         int row_floats) {
+// (the body: workgroup `bid` of `grid`, its first 256 threads -- the kernel below, and a role of the step epilogue)
+__device__ __forceinline__ void clear_mask_body(int bid, int grid, const PlanDev& P, KeepMask km, float* __restrict__ T, int n_rows,
+                                                int n_slabs, int row_floats) {
     __shared__ int32_t live[256];
     __shared__ int32_t n_live;
-    for (int64_t b0 = blockIdx.x; b0 < P.n_blocks; b0 += (int64_t)gridDim.x * 256) {
+    for (int64_t b0 = bid; b0 < P.n_blocks; b0 += (int64_t)grid * 256) {
         if (threadIdx.x == 0) n_live = 0;
         __syncthreads();
-        const int64_t bt = b0 + (int64_t)threadIdx.x * gridDim.x;
+        const int64_t bt = b0 + (int64_t)threadIdx.x * grid;
         if (bt < P.n_blocks) {
             const uint32_t* tw = km.bits + (size_t)bt * km.words;
             uint32_t any = 0;
@@ -212,13 +213,16 @@ __global__ __launch_bounds__(256) void clear_mask_kernel(PlanDev P, KeepMask km,
         __syncthreads();                                          // (the list is rewritten by the next pass)
     }
 }
+__global__ __launch_bounds__(256) void clear_mask_kernel(PlanDev P, KeepMask km, float* __restrict__ T, int n_rows, int n_slabs,
+                                                         int row_floats) {
+    clear_mask_body(blockIdx.x, gridDim.x, P, km, T, n_rows, n_slabs, row_floats);
+}
 
 // dW_slot[0][cc] += sum over the stream kernel's partials: one wave per output element, lane l adds partials l, l+64, ...
 // and the 64 lane sums are folded in a fixed butterfly order (deterministic).
-__global__ __launch_bounds__(64) void dw_first_reduce_kernel(const float* __restrict__ partial, int n_partials, int c,
-                                                             float* __restrict__ dW0, float* __restrict__ dW1,
-                                                             float* __restrict__ dW2) {
-    const int o = blockIdx.x, lane = threadIdx.x;                 // o = slot * c + cc
+__device__ __forceinline__ void dw_first_reduce_body(int o, int lane, const float* __restrict__ partial, int n_partials, int c,
+                                                     float* __restrict__ dW0, float* __restrict__ dW1, float* __restrict__ dW2) {
+    // o = slot * c + cc
     float s = 0.f;
     for (int b = lane; b < n_partials; b += 64) s += partial[(size_t)b * (3 * c) + o];
 #pragma unroll
@@ -229,16 +233,21 @@ __global__ __launch_bounds__(64) void dw_first_reduce_kernel(const float* __rest
         d[cc] += s;
     }
 }
+__global__ __launch_bounds__(64) void dw_first_reduce_kernel(const float* __restrict__ partial, int n_partials, int c,
+                                                             float* __restrict__ dW0, float* __restrict__ dW1,
+                                                             float* __restrict__ dW2) {
+    dw_first_reduce_body(blockIdx.x, threadIdx.x, partial, n_partials, c, dW0, dW1, dW2);
+}
 
 // dW_slot[i] += sum over partials.  layout: partial[b][ca*3c + slot*c + cc].  One workgroup per 64 outputs: wave w adds the
 // partials w, w + 16, ... (lanes = outputs: coalesced rows), the sixteen wave sums are combined in a fixed order -- deterministic,
 // and a handful of independent loads per thread instead of one thread walking all partials (60 us per launch on a small complex,
 // where the grid splits blocks x slabs into several hundred partials: the dearest kernel of that step).
-__global__ __launch_bounds__(1024) void blocked_dw_reduce(const float* __restrict__ partial, int n_partials, int c_aux, int c,
-                                                          float* __restrict__ dW0, float* __restrict__ dW1, float* __restrict__ dW2) {
+__device__ __forceinline__ void blocked_dw_reduce_body(int bid, const float* __restrict__ partial, int n_partials, int c_aux, int c,
+                                                       float* __restrict__ dW0, float* __restrict__ dW1, float* __restrict__ dW2) {
     __shared__ float part[16][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane;
+    const int i = bid * 64 + lane;
     const int per = c_aux * 3 * c;
     float s = 0.f;
     if (i < per) {
@@ -260,4 +269,8 @@ __global__ __launch_bounds__(1024) void blocked_dw_reduce(const float* __restric
         float* d = slot == 0 ? dW0 : (slot == 1 ? dW1 : dW2);
         if (d) d[ca * c + cc] += t;
     }
+}
+__global__ __launch_bounds__(1024) void blocked_dw_reduce(const float* __restrict__ partial, int n_partials, int c_aux, int c,
+                                                          float* __restrict__ dW0, float* __restrict__ dW1, float* __restrict__ dW2) {
+    blocked_dw_reduce_body(blockIdx.x, partial, n_partials, c_aux, c, dW0, dW1, dW2);
 }

@@ -18,7 +18,8 @@
 //               that were just issued.
 // Parts (one translation unit): scn_blk_layout.inc + scn_blk_plan.inc (host: block plan), scn_blk_common.inc (LDS layout, gather, pipeline helpers),
 // scn_window_scan.inc (batched window scan of the masked kernels), scn_blk_spmm.inc (dual SpMM), scn_blk_fwd.inc / scn_blk_bwd.inc (fused layer kernels), scn_blk_first.inc (first-layer
-// gradient streams, reductions), scn_blk_dispatch.inc (host dispatch), scn_terms.inc (fused Bunch layer).
+// gradient streams, reductions), scn_blk_dispatch.inc (host dispatch), scn_step_epilogue.inc (the deferred jobs of a step in one launch, with
+// the readout bodies of scn_readout_dev.inc), scn_terms.inc (fused Bunch layer).
 #include <algorithm>
 #include <array>
 #include <cstdlib>
@@ -29,6 +30,7 @@
 
 #include "scn_internal.h"
 #include "scn_keep_bits.h"
+#include "scn_step_ranges.h"
 
 namespace scn {
 
@@ -93,6 +95,8 @@ __device__ unsigned long long g_stamps_wg[STAMP_WG_CAP][8][STAMP_WG_WORDS];
 #include "scn_blk_bwd.inc"
 #include "scn_blk_first.inc"
 #include "scn_blk_dispatch.inc"
+#include "scn_readout_dev.inc"
+#include "scn_step_epilogue.inc"
 #include "scn_terms.inc"
 
 }  // namespace scn

@@ -706,6 +706,54 @@ int scn_conv_backward_fused_first_from_y_visit(scn_conv_t c, int32_t n_slabs, in
     return blocked_backward_first(c, L);
 }
 
+// The two visiting backwards less their reduce launches: the partial sums stay in the workspace for scn_step_epilogue.
+int scn_conv_backward_visit_partial(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* const* dz, const int32_t* c_dz,
+                                    const float* const* W, const float* aux, int32_t c_aux, int32_t act, float* dx, void* workspace,
+                                    size_t workspace_bytes, const uint32_t* visit, int32_t* n_wg_out, void* stream) {
+    if (!c || !dz || !c_dz || !W || !aux || !workspace || !visit || !n_wg_out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || ns <= 0 || c_aux <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS) return SCN_ERR_UNSUPPORTED;
+    if (!dz[0] || c_dz[0] <= 0 || !per_slot(c, W)) return SCN_ERR_BAD_ARG;
+    if (c->n_groups != 1 || c_dz[0] != 32 || c_aux != 32 || !blocked_backward_supported(c, ns, c_dz, c_aux)) return SCN_ERR_UNSUPPORTED;
+    if (ws_short(workspace_bytes, scn_conv_backward_workspace(c, n_slabs, ns, c_dz, c_aux))) return SCN_ERR_WORKSPACE;
+    BwdLaunch L{n_slabs, dz[0], c_dz[0], W, aux, c_aux, act, dx, nullptr, workspace, (hipStream_t)stream};
+    L.visit = visit;
+    L.defer_n_wg = n_wg_out;
+    return blocked_backward(c, L);
+}
+
+int scn_conv_backward_fused_first_from_y_visit_partial(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* dz, const float* const* W,
+                                                       const float* const* W_first, int32_t channels, int32_t act, const float* y,
+                                                       void* workspace, size_t workspace_bytes, const uint32_t* visit,
+                                                       int32_t* n_wg_out, void* stream) {
+    if (!c || !dz || !all3(W) || !all3(W_first) || !y || !workspace || !visit || !n_wg_out) return SCN_ERR_BAD_ARG;
+    if (n_slabs <= 0 || !act_ok(act)) return SCN_ERR_BAD_SHAPE;
+    if (n_slabs > MAX_SLABS || channels != 32 || !blocked_backward_first_supported(c, ns, channels)) return SCN_ERR_UNSUPPORTED;
+    if (ws_short(workspace_bytes, blocked_backward_first_workspace(c, n_slabs, ns, channels))) return SCN_ERR_WORKSPACE;
+    BwdFirstLaunch L{n_slabs, dz, W, channels, act, y, nullptr, nullptr, workspace, (hipStream_t)stream};
+    L.W_first = W_first;
+    L.visit = visit;
+    L.defer_n_wg = n_wg_out;
+    return blocked_backward_first(c, L);
+}
+
+int scn_dw_reduce(const float* partial, int32_t n_wg, int32_t c_aux, int32_t c_dz, float* const* dW, void* stream) {
+    if (!partial || !dW) return SCN_ERR_BAD_ARG;
+    if (n_wg <= 0 || c_aux <= 0 || c_dz <= 0) return SCN_ERR_BAD_SHAPE;
+    return blocked_dw_reduce_alone(partial, n_wg, c_aux, c_dz, dW, (hipStream_t)stream);
+}
+
+int scn_dw_first_reduce(const float* partial, int32_t n_wg, int32_t form, float* const* dW, void* stream) {
+    if (!partial || !all3(dW)) return SCN_ERR_BAD_ARG;
+    if (n_wg <= 0 || (form != 1 && form != 2)) return SCN_ERR_BAD_SHAPE;
+    return blocked_dw_first_reduce_alone(partial, n_wg, form, dW, (hipStream_t)stream);
+}
+
+int scn_step_epilogue(scn_conv_t c, const scn_step_epilogue_desc* desc, void* stream) {
+    if (!desc) return SCN_ERR_BAD_ARG;
+    return blocked_step_epilogue(c, *desc, (hipStream_t)stream);
+}
+
 int scn_conv_forward_power(scn_conv_t c, int32_t n_slabs, int32_t ns, const float* x0, const float* x,
                            const float* const* W, int32_t channels, int32_t act, float* out, void* stream) {
     if (!c || !x0 || !x || !all3(W) || !out) return SCN_ERR_BAD_ARG;

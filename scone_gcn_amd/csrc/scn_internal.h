@@ -326,6 +326,8 @@ struct BwdLaunch {                          // blocked_backward
     const float* dx_partial = nullptr;      // 32 -> 32: dx = dx_partial + (...) act', see bwd_c32_bf16_kernel
     const uint32_t* dzmask = nullptr;       // 32 -> 32, dense, no partial: dz is staged by the source mask, see there
     const uint32_t* visit = nullptr;        // the same shapes, no dzmask: only the mask's items are visited, see there
+    int32_t* defer_n_wg = nullptr;          // given: no reduce launch -- the partials [n_wg][c_aux][3 c_dz] stay at the head of ws for the step
+                                            // epilogue (scn_step_epilogue), and n_wg is written here
 };
 struct BwdFirstLaunch {                     // blocked_backward_first: the layer behind the first one, fused with dW_first
     int n_slabs;
@@ -341,6 +343,7 @@ struct BwdFirstLaunch {                     // blocked_backward_first: the layer
     const float* const* W_first = nullptr;  // 32 channels: aux is rebuilt from y, not read
     WorkList wl = NO_LIST;
     const uint32_t* visit = nullptr;        // with W_first, dense: only the mask's items are visited
+    int32_t* defer_n_wg = nullptr;          // given: neither reduce is launched -- ws keeps [n_wg][3 ch ch] and behind it [n_wg][96], n_wg is written here
 };
 
 int build_block_plan(scn_conv_s* c);
@@ -368,6 +371,9 @@ int blocked_dw_first(scn_conv_s* c, int n_slabs, const float* x, const float* y,
                      float* const* dW, void* ws, const WorkList* wl, hipStream_t st);
 int blocked_clear_list(scn_conv_s* c, int ns, int ch, float* t, const WorkList* wl, hipStream_t st);
 int blocked_clear_mask(scn_conv_s* c, int n_slabs, int ns, int ch, float* t, const uint32_t* mask, hipStream_t st);
+int blocked_step_epilogue(scn_conv_s* c, const scn_step_epilogue_desc& d, hipStream_t st);
+int blocked_dw_reduce_alone(const float* partial, int n_wg, int c_aux, int cd, float* const* dW, hipStream_t st);
+int blocked_dw_first_reduce_alone(const float* partial, int n_wg, int form, float* const* dW, hipStream_t st);
 bool blocked_spmm_supported(const scn_conv_s* c, int k);
 int blocked_spmm(scn_conv_s* c, int n_slabs, int k, const float* x, float* ya, float* yb, hipStream_t st);
 int blocked_window_scan_probe(scn_conv_s* c, int n_slabs, const uint32_t* mask, int gx, int slab0, int n_it, int cap, int32_t* out_block,

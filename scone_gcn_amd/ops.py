@@ -93,6 +93,8 @@ CONE_UNIT_LIST = True  # the cone's forward launches take their units from the m
 # ... and two the library reads at every visiting backward of a cone (_visit_prefetch):
 VISIT_PREFETCH = True  # a unit's prologue also fetches the next unit's source rows and first slab.  False: every unit's full prologue
 VISIT_RECORDS = True   # a unit's top reads the block's packed 32-byte record.  False: the plan's separate arrays
+# ... and one the trainer's micro-batch loop reads (SconePlan.step):
+STEP_TAIL = True       # a cone step's readout chain is one launch, and its loss sum, dW reduces and clears one more.  False: nine launches
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
@@ -460,7 +462,7 @@ class ConvOp:
                     lib.scn_conv_forward_list, *head, _dev(out), wl.ref() if wl is not None else None, _stream())
         return out
 
-    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None, visit=None):
+    def backward(self, dzs, Ws, aux, act, need_dx, dWs, dx=None, wl=None, dx_partial=None, dz_mask=None, visit=None, defer=None):
         """dWs: list of tensors ACCUMULATED into.  Returns dx or None.  wl: WorkList (zero-skipping): only the listed
         items of `dx` are written (it must be given, all-zero) and only they contribute to dWs.
         dx_partial: tensor of dx's shape ADDED to the input gradient (scn_conv_backward_accumulate; dx defaults to it, in place).
@@ -469,7 +471,9 @@ class ConvOp:
         (scn_conv_backward_dzmask).
         visit: a mask V one hop out from a mask outside whose items dzs[0] is all-zero: only V's items are visited, with the plain
         call's dWs and its dx on V; `dx` must be given and every other row of it is left as it is; False when not served
-        (scn_conv_backward_visit)."""
+        (scn_conv_backward_visit).
+        defer (with visit): a list -- the launch leaves its weight-gradient partials in its workspace and appends the reduce job
+        ("reduce", workspace, n_wg, c_aux, c_dz, dWs) for the step epilogue (scn_conv_backward_visit_partial, step_epilogue)."""
         lib = _lib.load()
         assert wl is None or (dx is not None or not need_dx)
         assert dz_mask is None or (wl is None and dx_partial is None)
@@ -502,6 +506,13 @@ class ConvOp:
             if not _launch(key, _nbytes(dx if need_dx else None) + self.csr_bytes, "scn_conv_backward_dzmask",
                            lib.scn_conv_backward_dzmask, *head, *tail, _dev(dz_mask, torch.int32), _stream(), may_decline=True):
                 return False
+        elif visit is not None and defer is not None:
+            _visit_prefetch(lib)
+            n_wg = ctypes.c_int32(0)
+            if not _launch(key, None, "scn_conv_backward_visit_partial", lib.scn_conv_backward_visit_partial, *head,
+                           _dev(dx) if need_dx else None, *ws, _dev(visit, torch.int32), ctypes.byref(n_wg), _stream(), may_decline=True):
+                return False
+            defer.append(("reduce", ws, n_wg.value, c_aux, c_dz[0], dWs))
         elif visit is not None:                       # (no byte model: the visited items' count is on the device)
             _visit_prefetch(lib)
             if not _launch(key, None, "scn_conv_backward_visit",
@@ -595,12 +606,13 @@ class ConvOp:
                 _stream())
         return True, dx
 
-    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None, visit=None):
+    def backward_fused_first(self, dz, Ws, aux, act, y, dWs, dWs_first, wl=None, Ws_first=None, visit=None, defer=None):
         """Backward of the layer after the first one, fused with the first layer's weight gradient: dWs (this layer) and
         dWs_first are accumulated, the input gradient is never written (scn_conv_backward_fused_first).  False when the shape
         is not served.  aux = None with Ws_first (the first layer's weights): the first layer's output is rebuilt from y
         inside the kernel instead of being read (scn_conv_backward_fused_first_from_y, 32 channels).  visit (with Ws_first, dense): as
-        in backward (scn_conv_backward_fused_first_from_y_visit)."""
+        in backward (scn_conv_backward_fused_first_from_y_visit).  defer (with visit): a list that takes the launch's two reduce jobs,
+        as in backward (scn_conv_backward_fused_first_from_y_visit_partial)."""
         lib = _lib.load()
         S, rows, ns, c = dz.shape
         if (aux is not None and tuple(aux.shape) != (S, rows, ns, c)) or tuple(y.shape) != (S, rows, ns, Y_STRIDE) or self.n_groups != 1:
@@ -618,6 +630,15 @@ class ConvOp:
             if aux is not None or wl is not None:
                 return False
             _visit_prefetch(lib)
+            if defer is not None:
+                n_wg = ctypes.c_int32(0)
+                if not _launch(key, None, "scn_conv_backward_fused_first_from_y_visit_partial",
+                               lib.scn_conv_backward_fused_first_from_y_visit_partial, *head, _ptrs(Ws_first), c, ACT[act], _dev(y), *ws,
+                               _dev(visit, torch.int32), ctypes.byref(n_wg), _stream(), may_decline=True):
+                    return False
+                defer.append(("reduce", ws, n_wg.value, c, c, dWs))
+                defer.append(("first", ws, n_wg.value, c, dWs_first))
+                return True
             return _launch(key, None, "scn_conv_backward_fused_first_from_y_visit", lib.scn_conv_backward_fused_first_from_y_visit,
                            *head, _ptrs(Ws_first), *tail, _dev(visit, torch.int32), _stream(), may_decline=True)
         wl_ref = wl.ref() if wl is not None else None
@@ -1476,6 +1497,103 @@ class SconePlan(Plan):
                 flat_w, m, v, lr, wd, step_dev = adam
                 check(lib.scn_small_step_adam(*args, *ws, _dev(flat_w), _dev(m), _dev(v), float(lr), 0.9, 0.999, 1e-8,
                                               ctypes.c_void_p(step_dev.data_ptr()), float(wd), _stream()), "scn_small_step_adam")
+        return True
+
+    # -- the cone route: a micro-batch whose tail is two launches (scn_readout_step, scn_step_epilogue; STEP_TAIL)
+    def step(self, x, last_dev, yt, scale, weights, grads, part, overwrite=False, zero_buf=None):
+        """grads[k] += d/dW[k] of scale * sum_n <logp_n, yt_n> and part[0] += that sum (overwrite: part[0] = ...), as forward /
+        scn_masked_ce_begin / backward compute them bit for bit, on the cone route of a plain stack at hidden 32: the forward stack,
+        ONE readout launch (forward, d_logp = yt * scale, backward; it also zeroes zero_buf -- the flat gradient buffer of a fresh
+        step, or None), the visiting backwards with their reduces left undone, and ONE epilogue launch for everything nothing waits
+        for before the micro-batch ends: the loss sum, the readout's weight gradient, every dW reduce and the clears of the pooled
+        gradient buffers.  False (nothing launched that changes grads, part or a pooled buffer) where the route or shape is not served:
+        the caller runs the separate calls.
+        A clear is deferred only where no layer further down takes a pooled buffer again, so the pool's peak is the separate calls'."""
+        lib = _lib.load()
+        if not STEP_TAIL or not self.fused_conv or self.conv is None or last_dev is None or self.max_deg > 64:
+            return False
+        if len(weights) < 7 or (len(weights) - 1) % 3 or self.promotion(weights):
+            return False
+        L = (len(weights) - 1) // 3
+        S, E, ns, _ = x.shape
+        N = S * ns
+        if tuple(yt.shape) != (N, self.max_deg) or L - 1 > _lib.SCN_EPI_MAX_REDUCES:
+            return False
+        route = self._route(x, weights, None, last_dev)
+        if not (route.cone and route.first == "from_y"):
+            return False
+        ran = self._layers(route, self._masks(route, last_dev, L), x, weights, None, None, L)
+        if ran is None:
+            return False
+        hs, y0, cone, route = ran
+        H = hs[-1]
+        C = H.shape[3]
+        key = (S, E, ns, C)
+        assert cone is not None and H.numel() * 4 > self.SMALL_DZ_BYTES      # (what makes a cone: the gradient buffers are kept all-zero)
+        bh = torch.empty((N, self.max_deg, C), device=H.device, dtype=torch.float32)
+        logits, logp, d_logp, d_logits = (torch.empty((N, self.max_deg), device=H.device, dtype=torch.float32) for _ in range(4))
+        take = lambda: self._dz_zero[key].pop() if self._dz_zero.get(key) else torch.zeros_like(H)
+        give = lambda t: self._dz_zero.setdefault(key, []).append(t)
+        dz = take()
+        if not _served(lib.scn_readout_step(S, ns, E, C, _dev(H), _dev(weights[-1]), *self._readout_args(last_dev, edge_nodes=True), _dev(yt),
+                                            float(scale), ACT[self.act], _dev(bh), _dev(logits), _dev(logp), _dev(d_logp), _dev(d_logits),
+                                            _dev(dz), 1, _dev(zero_buf) if zero_buf is not None else None,
+                                            zero_buf.numel() if zero_buf is not None else 0, _stream()), "scn_readout_step"):
+            give(dz)                                     # (declined before any launch: still all-zero)
+            return False
+        jobs, top, clears = [], None, []
+        for i in reversed(range(1, L)):
+            w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
+            visit = cone[L - i]
+            if i == 1:                                  # H1 is rebuilt from y0, dW_first in the same launch, no dx
+                assert self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit,
+                                                        defer=jobs), "aux-free fused-first backward not served"
+                dx = None
+            else:
+                dx = take()
+                assert self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit, defer=jobs) is not False, \
+                    "visiting backward not served"
+            taken_again = i - 1 >= 2                    # the layer below pops a pooled buffer: this one has to be back, all-zero, by then
+            if i == L - 1 and taken_again:
+                self._release_top(dz, key, last_dev)
+            elif i == L - 1:
+                top = dz
+            elif taken_again:
+                self.conv.clear_mask(dz, cone[L - 1 - i])
+                give(dz)
+            else:
+                clears.append((dz, cone[L - 1 - i]))
+            dz = dx
+        d = _lib.StepEpilogueDesc()
+        ptr = lambda t, dtype=torch.float32: _dev(t, dtype).value
+        d.loss_n, d.logp, d.y, d.scale, d.loss, d.overwrite = logp.numel(), ptr(logp), ptr(yt), float(scale), part.data_ptr(), 1 if overwrite else 0
+        d.rd_nd, d.rd_c, d.rd_dl, d.rd_bh, d.rd_d_w = N * self.max_deg, C, ptr(d_logits), ptr(bh), ptr(grads[-1])
+        for job in jobs:
+            if job[0] == "reduce":
+                _, ws, n_wg, c_aux, c_dz, dWs = job
+                q = d.reduce[d.n_reduce]
+                q.partial, q.n_wg, q.c_aux, q.c_dz = ws[0].value, n_wg, c_aux, c_dz
+                for k in range(3):
+                    q.dW[k] = ptr(dWs[k])
+                d.n_reduce += 1
+            else:                                       # the first layer's partials lie behind the layer's own in the same workspace
+                _, ws, n_wg, c, dWs = job
+                d.first_form, d.first_partial, d.first_n_wg = 1, ws[0].value + 4 * n_wg * 3 * c * c, n_wg
+                for k in range(3):
+                    d.first_dW[k] = ptr(dWs[k])
+        if top is not None:
+            i32 = torch.int32
+            d.rc_n_slabs, d.rc_ns, d.rc_n_edges, d.rc_c, d.rc_max_deg = S, ns, E, C, self.max_deg
+            d.rc_nbr, d.rc_last_nodes, d.rc_inc_ptr, d.rc_inc_edge = ptr(self.nbr, i32), ptr(last_dev, i32), ptr(self.inc_ptr, i32), ptr(self.inc_edge, i32)
+            d.rc_edge_nodes, d.rc_dz = ptr(self.edge_nodes, i32), ptr(top)
+        for t, mask in clears:
+            q = d.clear[d.n_clear]
+            q.tensor, q.mask, q.n_slabs, q.ns, q.channels = ptr(t), ptr(mask, torch.int32), t.shape[0], t.shape[2], t.shape[3]
+            d.n_clear += 1
+        # (under the masked clear's key: it is the launch that does that clear; no byte model, as there)
+        _launch("clear_mask", None, "scn_step_epilogue", lib.scn_step_epilogue, self.conv.handle, ctypes.byref(d), _stream())
+        for t in ([top] if top is not None else []) + [t for t, _ in clears]:
+            give(t)
         return True
 
     def promotion(self, weights):

@@ -531,6 +531,11 @@ class Scone_GCN():
                     part_set, zero_g = True, False
                     self._adam_applied = fuse
                     continue
+                # the cone route of a large complex: readout chain and deferred tail in two launches (ops.STEP_TAIL)
+                if plan.step(x, last_dev, yt, -1.0 / total, self.weights, self._grads, part, overwrite=not part_set,
+                             zero_buf=self._flat_g if zero_g else None):
+                    part_set, zero_g = True, False
+                    continue
             logp, saved = plan.forward(x, last_dev, self.weights, activity) if activity else plan.forward(x, last_dev, self.weights)
             d_logp = torch.empty_like(logp)
             _lib.check(lib.scn_masked_ce_begin(logp.numel(), ops._dev(logp), ops._dev(yt), -1.0 / total, ops._dev(d_logp),
