@@ -442,6 +442,35 @@ int scn_conv_forward_from_y_keep_units(scn_conv_t conv, int32_t n_slabs, int32_t
 int scn_conv_shifted_input_keep_units(scn_conv_t conv, int32_t n_slabs, int32_t ns, const float* x, float* y_out, const uint32_t* keep,
                                       const uint32_t* units /* NULL: static shares */, const uint32_t* unit_count, void* stream);
 
+/* The masks of a whole step in one launch.  The chain above -- scn_keep_mask_units, then L - 1 scn_mask_hop_units -- depends only on a
+ * micro-batch's last nodes, and every micro-batch's last nodes are on the device when a step begins.
+ * scn_cone_masks builds that chain for n_mb micro-batches at once, one workgroup each, the mask being read in LDS.  For micro-batch i
+ *   (mb[i], a HOST array of device pointers; n > 0 leaves, slab i / ns as in scn_keep_mask, words_i = ceil(ceil(n / ns) / 32),
+ *   n_words_i = n_blocks * words_i):
+ *     masks    [L][stride]      M0 = scn_keep_mask's mask of (node, n), M_k = scn_mask_hop(M_{k-1}) with the `adj` table, bit for bit;
+ *     units    [L][stride]      the unit list of M_k in its first counters[k] entries, ASCENDING; entries at or past the count are not
+ *                               written; of a mask only its n_words_i words are;
+ *     counters [SCN_UNIT_COUNTERS]   counters[k] = the number of non-zero words of M_k for k < L, 0 for k >= L.
+ *   Every word of every mask and every counter is written whatever the buffers held: no memset, no global atomic, no allocation, no
+ *   synchronisation, no host read; the launch can be captured.  The guards of scn_keep_mask and scn_mask_hop hold (a node outside
+ *   [0, n_nodes), a block outside [0, n_blocks) in either table: nothing is read or written through it).  More than
+ *   SCN_CONE_MASKS_MAX_MB micro-batches go out as several launches.
+ *   SCN_ERR_UNSUPPORTED, before anything is launched or written, for L > SCN_UNIT_COUNTERS and where some n_words_i exceeds
+ *   SCN_CONE_MASKS_MAX_WORDS (one mask has to fit a workgroup's LDS; also what scn_cone_masks_max_words() returns) or 2^31 - 1. */
+#define SCN_CONE_MASKS_MAX_WORDS 39936   /* 39 x 1024: 156 KB of a compute unit's 160 */
+#define SCN_CONE_MASKS_MAX_MB 64         /* micro-batches per launch (the table travels in the kernel's arguments) */
+typedef struct {
+    const int32_t* node;     /* device: the micro-batch's last nodes */
+    int32_t n;               /* ... and their number */
+    int32_t stride;          /* words from one mask (and list) to the next, at least n_words_i: SCN_ERR_WORKSPACE below, L > 1 */
+    uint32_t* masks;         /* device, the three outputs */
+    uint32_t* units;
+    uint32_t* counters;
+} scn_cone_mb;
+int scn_cone_masks(int32_t n_mb, const scn_cone_mb* mb, int32_t ns, int32_t n_nodes, int32_t n_blocks, const int32_t* top_ptr,
+                   const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L, void* stream);
+int64_t scn_cone_masks_max_words(void);
+
 /* Diagnostic, like scn_conv_plan_blocks; no step uses it.  The masked launches above do not walk a workgroup's units one at a time:
  * ahead of the block loop a workgroup fetches the blocks and the mask windows of its units in batches and keeps, in order, the units
  * whose window is non-zero.  scn_window_scan_probe runs that same device helper on grid_x workgroups (a multiple of 8, at least 8)

@@ -64,6 +64,10 @@ class StepEpilogueDesc(ctypes.Structure):      # scn_step_epilogue_desc (device 
                 ("n_clear", c_i32), ("clear", EpiClear * SCN_EPI_MAX_CLEARS)]
 
 
+class ConeMb(ctypes.Structure):                # scn_cone_mb (device pointers)
+    _fields_ = [("node", c_void_p), ("n", c_i32), ("stride", c_i32), ("masks", c_void_p), ("units", c_void_p), ("counters", c_void_p)]
+
+
 # name -> (restype, argtypes); every name here must be exported by the library and declared in the header
 SIGNATURES = {
     "scn_version": (ctypes.c_int, []),
@@ -162,6 +166,9 @@ SIGNATURES = {
     "scn_clear_mask": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "scn_keep_mask_units": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p]),
     "scn_mask_hop_units": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "scn_cone_masks": (ctypes.c_int, [c_i32, ctypes.POINTER(ConeMb), c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                      c_void_p]),
+    "scn_cone_masks_max_words": (c_i64, []),
     "scn_conv_forward_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
                                                    c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_conv_forward_from_y_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),

@@ -165,6 +165,271 @@ __global__ __launch_bounds__(256) void mask_hop_kernel(int n_blocks, int words, 
     }
 }
 
+// The masks of a whole step in ONE launch (scn_cone_masks): workgroup g builds, for micro-batch g, the chain the three kernels above
+// build in 2 + L launches -- M0 = keep mask of its last nodes, M_k = hop(M_{k-1}), every mask's unit list and count -- with the mask
+// being read in LDS.  Thread t owns the words t, t + CM_THREADS, ... of every mask (at most MAXT of them: the trip count is a
+// compile-time bound, so a hop's results stay in registers until everybody has read the image they replace: ONE LDS image).
+//   M0:   the image is zeroed, the leaves OR their bits in with LDS atomics (CM_LEAF_LANES threads stride over a leaf's T(v)), the image
+//         goes out to global in 16-byte stores (words before the first and after the last 16-byte boundary of the destination singly);
+//   hop:  the pull form of mask_hop_kernel, `in` from LDS, the adjacency from global in aligned 16-byte loads, one plain store per word.  The
+//         trips are a pipeline (a trip's row and first entries are fetched while the trips before it gather), and the first hop's
+//         way into it does not depend on the mask: it is issued before the keep phase, whose chain of loads it overlaps;
+//   list: pass j of the owned words covers [j * CM_THREADS, (j + 1) * CM_THREADS) in thread order, so (pass, wave) cells in order are
+//         the words in order: a ballot per cell, one workgroup prefix over the cells' counts in LDS, and every live lane knows its
+//         position.  No global atomic anywhere; entries ascend; nothing is written at or past the count; the L counts and the zeros
+//         behind them are stored once, at the end.
+// Every word of every mask is written, so the buffers may hold anything on entry: no memset.  Workgroups share nothing.  The guards
+// of the kernels above hold: a node outside [0, n_nodes) or a block outside [0, n_blocks) contributes nothing and nothing is read or
+// written through it.
+constexpr int CM_THREADS = 1024, CM_WAVES = CM_THREADS / 64, CM_LEAF_LANES = 8;
+static_assert(SCN_CONE_MASKS_MAX_WORDS % CM_THREADS == 0 && SCN_CONE_MASKS_MAX_WORDS * 4 + 4096 <= 160 * 1024,
+              "the image and the list's cells fit a workgroup's LDS");
+struct ConeMasksArgs { scn_cone_mb mb[SCN_CONE_MASKS_MAX_MB]; };
+// words of one mask of a micro-batch of n leaves: n_blocks * ceil(ceil(n / ns) / 32), n > 0 (the host's checks, in 64 bits)
+static inline int64_t cone_masks_words(int32_t n, int32_t ns, int32_t n_blocks) {
+    const int64_t n_slabs = ((int64_t)n - 1) / ns + 1;
+    return (int64_t)n_blocks * ((n_slabs + 31) / 32);
+}
+
+// exclusive prefix of v over the workgroup's threads in thread order (wave_sums: CM_WAVES words of LDS, free on entry); total = the sum
+__device__ __forceinline__ uint32_t cm_exclusive_scan(uint32_t v, uint32_t* wave_sums, uint32_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wave_sums[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < CM_WAVES; ++i) {
+        const uint32_t x = wave_sums[i];
+        base += i < wave ? x : 0u;
+        total += x;
+    }
+    return base + incl - v;
+}
+
+// the unit list of the mask whose owned words are acc[0 .. MAXT): returns its count (the same in every thread).  Two barriers inside,
+// one behind: cells and wave_sums are free again on return.
+template <int MAXT>
+__device__ __forceinline__ uint32_t cm_list(const uint32_t (&acc)[MAXT], int n_words, uint32_t* cells, uint32_t* wave_sums,
+                                            uint32_t* __restrict__ units) {
+    static_assert(MAXT * CM_WAVES <= CM_THREADS, "one thread per (pass, wave) cell");
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+        const uint64_t live = __builtin_amdgcn_ballot_w64(acc[j] != 0);
+        if (lane == 0) cells[j * CM_WAVES + wave] = (uint32_t)__builtin_popcountll(live);
+    }
+    __syncthreads();
+    uint32_t total;
+    const uint32_t first = cm_exclusive_scan(t < MAXT * CM_WAVES ? cells[t] : 0u, wave_sums, total);
+    __syncthreads();                                   // (every thread has read its cell's count)
+    if (t < MAXT * CM_WAVES) cells[t] = first;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+        const uint64_t live = __builtin_amdgcn_ballot_w64(acc[j] != 0);
+        const uint32_t rank =__builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
+        const int idx = t + j * CM_THREADS;
+        if (acc[j] != 0 && idx < n_words) units[cells[j * CM_WAVES + wave] + rank] = (uint32_t)idx;
+    }
+    __syncthreads();
+    return total;
+}
+
+// A hop's view of the adjacency.  The row of the word owned in trip j is the range [lo, hi) of adj_blk (empty past the mask's end).  A
+// CmBatch is CM_BATCH consecutive entries of the table from cm_first(q) on -- q itself, or, where the table lies on a 16-byte boundary
+// (wide), the boundary at or before it, so that the entries come in aligned 16-byte loads (what they bring from outside the row is not
+// used); at the table's end, and for a table that does not lie so, single guarded loads.  A part wholly beyond the row is not loaded.
+constexpr int CM_BATCH = 16;
+struct CmRows {
+    const int32_t* __restrict__ adj_ptr;
+    const int32_t* __restrict__ adj_blk;
+    int nnz, n_words, words;
+    bool wide;
+};
+struct CmRange { int lo, hi; };
+struct CmBatch { int4 q[CM_BATCH / 4]; };
+
+__device__ __forceinline__ CmRange cm_range(const CmRows& R, int idx) {
+    CmRange r{0, 0};
+    if (idx < R.n_words) {
+        const int b = R.words == 1 ? idx : idx / R.words;
+        r.lo = R.adj_ptr[b];
+        r.hi = R.adj_ptr[b + 1];
+    }
+    return r;
+}
+__device__ __forceinline__ int cm_first(const CmRows& R, int q) { return R.wide ? q & ~3 : q; }
+__device__ __forceinline__ CmBatch cm_batch(const CmRows& R, int q, int hi) {
+    CmBatch B;
+    const int p0 = cm_first(R, q);
+#pragma unroll
+    for (int c = 0; c < CM_BATCH / 4; ++c) {
+        const int p = p0 + 4 * c;
+        B.q[c] = make_int4(-1, -1, -1, -1);
+        if (p < hi) {
+            if (R.wide && p + 4 <= R.nnz) {
+                B.q[c] = *reinterpret_cast<const int4*>(R.adj_blk + p);
+            } else {
+                if (p >= q && p < hi) B.q[c].x = R.adj_blk[p];
+                if (p + 1 >= q && p + 1 < hi) B.q[c].y = R.adj_blk[p + 1];
+                if (p + 2 >= q && p + 2 < hi) B.q[c].z = R.adj_blk[p + 2];
+                if (p + 3 >= q && p + 3 < hi) B.q[c].w = R.adj_blk[p + 3];
+            }
+        }
+    }
+    return B;
+}
+// OR of img[b' * words + w] over the batch's entries b' that lie in the row's part [q, hi) and in [0, n_blocks).  Every other entry
+// reads the zero word the image keeps at `zero_at`: sixteen independent LDS reads under one wait, no branch per entry.
+__device__ __forceinline__ uint32_t cm_gather(const CmRows& R, const CmBatch& B, int q, int hi, const uint32_t* img, int n_blocks, int w,
+                                              int zero_at) {
+    uint32_t a = 0;
+    const int p0 = cm_first(R, q);
+#pragma unroll
+    for (int c = 0; c < CM_BATCH / 4; ++c) {
+        const int v[4] = {B.q[c].x, B.q[c].y, B.q[c].z, B.q[c].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int p = p0 + 4 * c + e;
+            a |= img[p >= q && p < hi && v[e] >= 0 && v[e] < n_blocks ? v[e] * R.words + w : zero_at];
+        }
+    }
+    return a;
+}
+
+template <int MAXT>
+__global__ __launch_bounds__(CM_THREADS) void cone_masks_kernel(ConeMasksArgs A, int ns, int n_nodes, int n_blocks,
+                                                                const int32_t* __restrict__ top_ptr, const int32_t* __restrict__ top_blk,
+                                                                const int32_t* __restrict__ adj_ptr, const int32_t* __restrict__ adj_blk,
+                                                                int L) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t cm_img[];           // the mask being read: n_words, rounded up to four, + four
+    __shared__ uint32_t cells[MAXT * CM_WAVES], wave_sums[CM_WAVES];
+    const scn_cone_mb& mb = A.mb[blockIdx.x];
+    const int t = threadIdx.x;
+    const int n = mb.n;
+    const int32_t* __restrict__ node = mb.node;
+    const int n_slabs = (n - 1) / ns + 1, words = (n_slabs + 31) / 32;           // (n > 0)
+    const int n_words = n_blocks * words;                                       // (<= MAXT * CM_THREADS: the host's check)
+    uint32_t* __restrict__ mask = mb.masks;
+    uint32_t* __restrict__ units = mb.units;
+
+    // the first hop's way in -- the rows of trips 0 and 1 and the first batch of trip 0 -- does not depend on the mask: its two
+    // dependent trips to memory are issued here, ahead of the keep phase, and overlap the leaves' node -> top_ptr -> top_blk chain
+    const CmRows R{adj_ptr, adj_blk, L > 1 ? adj_ptr[n_blocks] : 0, n_words, words, ((uintptr_t)adj_blk & 15u) == 0};
+    CmRange r0{0, 0}, r1{0, 0};
+    CmBatch b0 = cm_batch(R, 0, 0);
+    if (L > 1) {
+        r0 = cm_range(R, t);
+        r1 = cm_range(R, t + CM_THREADS);
+        b0 = cm_batch(R, r0.lo, r0.hi);
+    }
+
+    // M0 into the LDS image
+    const int zero_at = (n_words + 3) & ~3;            // four words behind the image that stay zero: what a hop reads for an entry it passes over
+    for (int i = t * 4; i < zero_at + 4; i += CM_THREADS * 4) *reinterpret_cast<uint4*>(cm_img + i) = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    for (int i = t / CM_LEAF_LANES; i < n; i += CM_THREADS / CM_LEAF_LANES) {
+        const int v = node[i];
+        if (v < 0 || v >= n_nodes) continue;
+        const int s = i / ns;
+        const uint32_t bit = 1u << (s & 31);
+        const int q1 = top_ptr[v + 1];
+        for (int q = top_ptr[v] + t % CM_LEAF_LANES; q < q1; q += CM_LEAF_LANES) {
+            const int b = top_blk[q];
+            if (b >= 0 && b < n_blocks) atomicOr(&cm_img[b * words + (s >> 5)], bit);
+        }
+    }
+    __syncthreads();
+    {
+        // 16-byte stores between the destination's first and last 16-byte boundary, single words outside them
+        const int head = min(n_words, (int)(((16u - (uint32_t)((uintptr_t)mask & 15u)) & 15u) >> 2));
+        const int body = (n_words - head) & ~3;
+        if (t < head) mask[t] = cm_img[t];
+        for (int i = head + t * 4; i < head + body; i += CM_THREADS * 4)
+            *reinterpret_cast<uint4*>(mask + i) = make_uint4(cm_img[i], cm_img[i + 1], cm_img[i + 2], cm_img[i + 3]);
+        if (t < n_words - head - body) mask[head + body + t] = cm_img[head + body + t];
+    }
+    uint32_t acc[MAXT];
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+        const int idx = t + j * CM_THREADS;
+        acc[j] = idx < n_words ? cm_img[idx] : 0u;
+    }
+    uint32_t counts[SCN_UNIT_COUNTERS] = {};
+    counts[0] = cm_list<MAXT>(acc, n_words, cells, wave_sums, units);
+
+#pragma unroll 1
+    for (int k = 1; k < L; ++k) {
+        mask += mb.stride;
+        units += mb.stride;
+        if (k > 1) {
+            r0 = cm_range(R, t);
+            r1 = cm_range(R, t + CM_THREADS);
+            b0 = cm_batch(R, r0.lo, r0.hi);
+        }
+        // a pipeline over the trips: while trip j gathers from the image, the first batch of trip j + 1 and the row of trip j + 2 are
+        // under way (a row longer than a batch fetches the rest of it in place)
+#pragma unroll
+        for (int j = 0; j < MAXT; ++j) {
+            const CmRange r2 = j + 2 < MAXT ? cm_range(R, t + (j + 2) * CM_THREADS) : CmRange{0, 0};
+            const CmBatch b1 = cm_batch(R, r1.lo, r1.hi);
+            const int idx = t + j * CM_THREADS;
+            const int w = words == 1 ? 0 : idx % words;
+            uint32_t a = cm_gather(R, b0, r0.lo, r0.hi, cm_img, n_blocks, w, zero_at);
+            for (int q = cm_first(R, r0.lo) + CM_BATCH; q < r0.hi; q += CM_BATCH)
+                a |= cm_gather(R, cm_batch(R, q, r0.hi), q, r0.hi, cm_img, n_blocks, w, zero_at);
+            acc[j] = a;
+            if (idx < n_words) mask[idx] = a;
+            r0 = r1;
+            r1 = r2;
+            b0 = b1;
+        }
+        __syncthreads();                               // everybody has read M_{k-1}: the image becomes M_k
+#pragma unroll
+        for (int j = 0; j < MAXT; ++j) {
+            const int idx = t + j * CM_THREADS;
+            if (idx < n_words) cm_img[idx] = acc[j];
+        }
+        __syncthreads();
+        const uint32_t c = cm_list<MAXT>(acc, n_words, cells, wave_sums, units);
+#pragma unroll
+        for (int i = 1; i < SCN_UNIT_COUNTERS; ++i)
+            if (i == k) counts[i] = c;
+    }
+    if (t < SCN_UNIT_COUNTERS) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < SCN_UNIT_COUNTERS; ++i)
+            if (i == t) c = counts[i];
+        mb.counters[t] = c;
+    }
+}
+
+// one instantiation's launch; its dynamic-LDS attribute is set once per device, at the instantiation's full size, not per call
+template <int MAXT>
+static int cone_masks_launch(const ConeMasksArgs& A, int n_mb, size_t lds, hipStream_t st, int ns, int n_nodes, int n_blocks,
+                             const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int L) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    SCN_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        SCN_HIP_TRY(hipFuncSetAttribute((const void*)cone_masks_kernel<MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        MAXT * CM_THREADS * 4 + 16));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(cone_masks_kernel<MAXT>, dim3(n_mb), dim3(CM_THREADS), lds, st, A, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr,
+                       adj_blk, L);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
 __global__ __launch_bounds__(64) void node_readout_fwd_kernel(int ns, int n_nodes, const float* __restrict__ X,
                                                               const int32_t* __restrict__ nbr, int max_deg,
                                                               const int32_t* __restrict__ last_nodes,
@@ -578,6 +843,42 @@ int scn_mask_hop_units(int32_t n_blocks, int32_t words, const int32_t* adj_ptr, 
     hipLaunchKernelGGL(mask_hop_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_blocks, words,
                        adj_ptr, adj_blk, in, out, units, unit_count, (uint32_t)std::min<int64_t>(capacity, INT32_MAX));
     SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int64_t scn_cone_masks_max_words(void) { return SCN_CONE_MASKS_MAX_WORDS; }
+
+int scn_cone_masks(int32_t n_mb, const scn_cone_mb* mb, int32_t ns, int32_t n_nodes, int32_t n_blocks, const int32_t* top_ptr,
+                   const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L, void* stream) {
+    if (!mb || !top_ptr || !top_blk || !adj_ptr || !adj_blk) return SCN_ERR_BAD_ARG;
+    if (n_mb <= 0 || ns <= 0 || n_nodes <= 0 || n_blocks <= 0 || L <= 0) return SCN_ERR_BAD_SHAPE;
+    if (L > SCN_UNIT_COUNTERS) return SCN_ERR_UNSUPPORTED;
+    // everything is checked before the first launch: a declined call has launched and written nothing
+    int64_t widest = 0;
+    for (int i = 0; i < n_mb; ++i) {
+        if (!mb[i].node || !mb[i].masks || !mb[i].units || !mb[i].counters) return SCN_ERR_BAD_ARG;
+        if (mb[i].n <= 0) return SCN_ERR_BAD_SHAPE;
+        const int64_t n_words = cone_masks_words(mb[i].n, ns, n_blocks);
+        if (L > 1 && mb[i].stride < n_words) return SCN_ERR_WORKSPACE;
+        widest = std::max(widest, n_words);
+    }
+    if (widest > INT32_MAX || widest > SCN_CONE_MASKS_MAX_WORDS) return SCN_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)((widest + 3) / 4 * 4 + 4) * sizeof(uint32_t);         // (the image and its four zero words)
+    const int trips = (int)((widest + CM_THREADS - 1) / CM_THREADS);
+    for (int i0 = 0; i0 < n_mb; i0 += SCN_CONE_MASKS_MAX_MB) {
+        const int m = std::min<int>(SCN_CONE_MASKS_MAX_MB, n_mb - i0);
+        ConeMasksArgs A{};
+        std::memcpy(A.mb, mb + i0, sizeof(scn_cone_mb) * (size_t)m);
+        int rc;
+        if (trips <= 4)
+            rc = cone_masks_launch<4>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
+        else if (trips <= 20)
+            rc = cone_masks_launch<20>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
+        else
+            rc = cone_masks_launch<SCN_CONE_MASKS_MAX_WORDS / CM_THREADS>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr,
+                                                                          top_blk, adj_ptr, adj_blk, L);
+        if (rc != SCN_OK) return rc;
+    }
     return SCN_OK;
 }
 

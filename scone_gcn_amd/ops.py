@@ -95,6 +95,7 @@ VISIT_PREFETCH = True  # a unit's prologue also fetches the next unit's source r
 VISIT_RECORDS = True   # a unit's top reads the block's packed 32-byte record.  False: the plan's separate arrays
 # ... and one the trainer's micro-batch loop reads (SconePlan.step):
 STEP_TAIL = True       # a cone step's readout chain is one launch, and its loss sum, dW reduces and clears one more.  False: nine launches
+STEP_MASKS = True      # the cone masks of all of a step's micro-batches come from one launch ahead of the first.  False: five launches each
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser
@@ -267,14 +268,16 @@ def field_tables(row0, pattern_csr, nbr, inc_ptr, inc_edge):
 
 def keep_mask_host(nodes, ns, top_ptr, top_blk, n_blocks):
     """NumPy restatement of scn_keep_mask (include/scone_hip.h): uint32 [n_blocks][ceil(n_slabs / 32)], bit s & 31 of word
-    [b][s >> 5] set iff a leaf i of slab s = i // ns has block b in T(nodes[i]).  A node outside the table contributes nothing."""
+    [b][s >> 5] set iff a leaf i of slab s = i // ns has block b in T(nodes[i]).  A node outside the table contributes nothing, nor
+    does a block outside [0, n_blocks)."""
     nodes = np.asarray(nodes, np.int64)
     n_slabs = -(-len(nodes) // ns)
     mask = np.zeros((n_blocks, (n_slabs + 31) // 32), np.uint32)
     for i, v in enumerate(nodes):
         if 0 <= v < len(top_ptr) - 1:
             s = i // ns
-            mask[np.asarray(top_blk[top_ptr[v]:top_ptr[v + 1]], np.int64), s >> 5] |= np.uint32(1 << (s & 31))
+            blk = np.asarray(top_blk[top_ptr[v]:top_ptr[v + 1]], np.int64)
+            mask[blk[(blk >= 0) & (blk < n_blocks)], s >> 5] |= np.uint32(1 << (s & 31))
     return mask
 
 
@@ -289,6 +292,28 @@ def mask_hop_host(mask, adj_ptr, adj_blk):
         if len(src):
             out[b] = np.bitwise_or.reduce(mask[src], axis=0)
     return out
+
+
+def cone_masks_host(nodes_list, ns, top_ptr, top_blk, adj_ptr, adj_blk, n_blocks, L):
+    """NumPy restatement of scn_cone_masks (include/scone_hip.h): for every micro-batch's last nodes in nodes_list the tuple
+    (masks, lists, counters) -- masks[k] = M_k, M0 = keep_mask_host, M_k = mask_hop_host(M_{k-1}); lists[k] = the indices b * words + w
+    of the non-zero words of M_k, ascending; counters = their lengths for k < L and 0 behind, UNIT_COUNTERS words."""
+    assert 1 <= L <= UNIT_COUNTERS
+    out = []
+    for nodes in nodes_list:
+        masks = [keep_mask_host(nodes, ns, top_ptr, top_blk, n_blocks)]
+        for _ in range(1, L):
+            masks.append(mask_hop_host(masks[-1], adj_ptr, adj_blk))
+        lists = [np.flatnonzero(m.reshape(-1)).astype(np.uint32) for m in masks]
+        counters = np.zeros(UNIT_COUNTERS, np.uint32)
+        counters[:L] = [len(u) for u in lists]
+        out.append((masks, lists, counters))
+    return out
+
+
+def cone_masks_limit():
+    """Words of one mask scn_cone_masks takes at most (the library's SCN_CONE_MASKS_MAX_WORDS: one mask in a workgroup's LDS)."""
+    return int(_lib.load().scn_cone_masks_max_words())
 
 
 class UnitList(NamedTuple):
@@ -415,6 +440,45 @@ class ConvOp:
                 _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32), _dev(mask, torch.int32), _dev(out, torch.int32),
                 _dev(units, torch.int32), _dev(counter, torch.int32), units.numel(), _stream())
         return out, UnitList(units, counter)
+
+    def cone_masks(self, last_devs, ns, n_nodes, tabs, L):
+        """The cones of several micro-batches in ONE launch (scn_cone_masks): for every int32 device tensor of last nodes in last_devs a
+        Cone [M0 .. M_{L-1}] with every mask's UnitList, as keep_mask_units() and L - 1 mask_hop_units() build them (the lists
+        ascending).  Masks, entries and counters are views into three fresh allocations of this call, none of them filled: the launch
+        writes every mask word and every counter.  No memset, no host read.  None where the library declines (L above UNIT_COUNTERS, a
+        mask above cone_masks_limit() words): nothing was launched."""
+        n_mb = len(last_devs)
+        words = [(-(-t.numel() // ns) + 31) // 32 for t in last_devs]
+        n_words = [tabs.n_blocks * w for w in words]
+        stride = -(-max(n_words) // 128) * 128                  # (every mask and list starts on 512 bytes, as an allocation of its own does)
+        dev = last_devs[0].device
+        masks = torch.empty((n_mb * L, stride), device=dev, dtype=torch.int32)
+        units = torch.empty((n_mb * L, stride), device=dev, dtype=torch.int32)
+        counters = torch.empty((n_mb * UNIT_COUNTERS, 1), device=dev, dtype=torch.int32)
+        desc = (_lib.ConeMb * n_mb)()
+        m0, u0, c0 = masks.data_ptr(), units.data_ptr(), counters.data_ptr()
+        for i, t in enumerate(last_devs):
+            d = desc[i]
+            d.node, d.n, d.stride = _dev(t, torch.int32).value, t.numel(), stride
+            d.masks, d.units, d.counters = m0 + 4 * i * L * stride, u0 + 4 * i * L * stride, c0 + 4 * UNIT_COUNTERS * i
+        # bytes: every mask and counter written, the last nodes read, and per micro-batch the block adjacency once for each hop
+        nb = 4.0 * L * sum(n_words) + _nbytes(counters, *last_devs) + n_mb * (L - 1) * _nbytes(tabs.adj_ptr, tabs.adj_blk)
+        if not _launch("cone_masks", nb, "scn_cone_masks", _lib.load().scn_cone_masks, n_mb, desc, ns, n_nodes, tabs.n_blocks,
+                       _dev(tabs.top_ptr, torch.int32), _dev(tabs.top_blk, torch.int32), _dev(tabs.adj_ptr, torch.int32),
+                       _dev(tabs.adj_blk, torch.int32), L, _stream(), may_decline=True):
+            return None
+        # the views, a few tensor calls for all of them (host time ahead of a step's first launch): row i * L + k of the buffers is
+        # mask / list k of micro-batch i
+        rows = {w: (masks[:, :tabs.n_blocks * w].unflatten(1, (tabs.n_blocks, w)).unbind(0), units[:, :tabs.n_blocks * w].unbind(0))
+                for w in set(words)}
+        count = counters.unbind(0)
+        cones = []
+        for i in range(n_mb):
+            m, u = rows[words[i]]
+            cone = Cone(m[i * L:(i + 1) * L])
+            cone.units = [UnitList(u[i * L + k], count[i * UNIT_COUNTERS + k]) for k in range(L)]
+            cones.append(cone)
+        return cones
 
     def clear_mask(self, t, mask):
         """+0 over the (block, slab) items of a [S, rows, ns, C] tensor whose bit is set in `mask` (scn_clear_mask)."""
@@ -1500,7 +1564,43 @@ class SconePlan(Plan):
         return True
 
     # -- the cone route: a micro-batch whose tail is two launches (scn_readout_step, scn_step_epilogue; STEP_TAIL)
-    def step(self, x, last_dev, yt, scale, weights, grads, part, overwrite=False, zero_buf=None):
+    def _step_route(self, x, last_dev, yt, weights):
+        """The route of a micro-batch that step() serves, or None: the facts step() declines on before it launches anything."""
+        if not STEP_TAIL or not self.fused_conv or self.conv is None or last_dev is None or self.max_deg > 64:
+            return None
+        if len(weights) < 7 or (len(weights) - 1) % 3 or self.promotion(weights):
+            return None
+        L = (len(weights) - 1) // 3
+        S, E, ns, _ = x.shape
+        if tuple(yt.shape) != (S * ns, self.max_deg) or L - 1 > _lib.SCN_EPI_MAX_REDUCES:
+            return None
+        route = self._route(x, weights, None, last_dev)
+        return route if route.cone and route.first == "from_y" else None
+
+    def step_cones(self, staged_micro_batches, weights):
+        """The cones of every micro-batch of a step -- staged_micro_batches: (x, last_dev, yt, activity) each -- from ONE launch
+        (ConvOp.cone_masks; STEP_MASKS), to hand to step(cone=...) one by one.  None (nothing launched) where the switch is off, some
+        micro-batch is not one step() serves on a cone with unit lists, or the library declines: step() then builds each micro-batch's
+        masks itself.  Nothing is kept: the masks are built inside the step that uses them, from the batch staged for it."""
+        if not STEP_MASKS or not staged_micro_batches:
+            return None
+        L = (len(weights) - 1) // 3
+        served = {}                                     # (one look per shape: host time ahead of a step's first launch)
+        for x, last_dev, yt, activity in staged_micro_batches:
+            if activity is not None or last_dev is None:
+                return None
+            key = (tuple(x.shape), last_dev.numel(), last_dev.dtype, tuple(yt.shape))
+            if key not in served:
+                route = self._step_route(x, last_dev, yt, weights)
+                served[key] = route is not None and route.units and x.shape[2] == NS
+            if not served[key]:
+                return None
+        tabs = self.field_tables_dev()
+        if L > UNIT_COUNTERS or max(tabs.n_blocks * ((m[0].shape[0] + 31) // 32) for m in staged_micro_batches) > cone_masks_limit():
+            return None
+        return self.conv.cone_masks([m[1] for m in staged_micro_batches], NS, self.n_nodes, tabs, L)
+
+    def step(self, x, last_dev, yt, scale, weights, grads, part, overwrite=False, zero_buf=None, cone=None):
         """grads[k] += d/dW[k] of scale * sum_n <logp_n, yt_n> and part[0] += that sum (overwrite: part[0] = ...), as forward /
         scn_masked_ce_begin / backward compute them bit for bit, on the cone route of a plain stack at hidden 32: the forward stack,
         ONE readout launch (forward, d_logp = yt * scale, backward; it also zeroes zero_buf -- the flat gradient buffer of a fresh
@@ -1508,21 +1608,16 @@ class SconePlan(Plan):
         for before the micro-batch ends: the loss sum, the readout's weight gradient, every dW reduce and the clears of the pooled
         gradient buffers.  False (nothing launched that changes grads, part or a pooled buffer) where the route or shape is not served:
         the caller runs the separate calls.
+        cone: this micro-batch's Cone from step_cones() -- its masks are not built here then; None: they are, in five launches.
         A clear is deferred only where no layer further down takes a pooled buffer again, so the pool's peak is the separate calls'."""
         lib = _lib.load()
-        if not STEP_TAIL or not self.fused_conv or self.conv is None or last_dev is None or self.max_deg > 64:
-            return False
-        if len(weights) < 7 or (len(weights) - 1) % 3 or self.promotion(weights):
+        route = self._step_route(x, last_dev, yt, weights)
+        if route is None:
             return False
         L = (len(weights) - 1) // 3
         S, E, ns, _ = x.shape
         N = S * ns
-        if tuple(yt.shape) != (N, self.max_deg) or L - 1 > _lib.SCN_EPI_MAX_REDUCES:
-            return False
-        route = self._route(x, weights, None, last_dev)
-        if not (route.cone and route.first == "from_y"):
-            return False
-        ran = self._layers(route, self._masks(route, last_dev, L), x, weights, None, None, L)
+        ran = self._layers(route, cone if cone is not None else self._masks(route, last_dev, L), x, weights, None, None, L)
         if ran is None:
             return False
         hs, y0, cone, route = ran

@@ -519,7 +519,11 @@ class Scone_GCN():
         # on the reference's own sizes a step is ~15 launches of 5-15 us each.
         part = torch.empty((1,), device=self._flat_w.device, dtype=torch.float64)
         part_set, zero_g = False, bool(fresh)
-        for x, last_dev, yt, activity in staged:
+        # The cone masks depend on the last nodes alone, and every micro-batch's are on the device already: ONE launch builds them for
+        # the whole step (ops.STEP_MASKS), asked for once, ahead of the first micro-batch the one-launch step does not take.  Built here,
+        # in the step, from the batch staged for it -- never kept from one call to the next.
+        cones, cones_asked = None, not (type(plan) is ops.SconePlan and all(m[3] is None for m in staged))
+        for i, (x, last_dev, yt, activity) in enumerate(staged):
             if activity is None and type(plan) is ops.SconePlan:
                 if not part_set and not zero_g:
                     part.zero_()                                  # (accumulating call whose first micro-batch takes the one-launch step)
@@ -532,8 +536,10 @@ class Scone_GCN():
                     self._adam_applied = fuse
                     continue
                 # the cone route of a large complex: readout chain and deferred tail in two launches (ops.STEP_TAIL)
+                if not cones_asked:
+                    cones, cones_asked = plan.step_cones(staged, self.weights), True
                 if plan.step(x, last_dev, yt, -1.0 / total, self.weights, self._grads, part, overwrite=not part_set,
-                             zero_buf=self._flat_g if zero_g else None):
+                             zero_buf=self._flat_g if zero_g else None, cone=cones[i] if cones is not None else None):
                     part_set, zero_g = True, False
                     continue
             logp, saved = plan.forward(x, last_dev, self.weights, activity) if activity else plan.forward(x, last_dev, self.weights)
