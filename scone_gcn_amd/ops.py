@@ -322,6 +322,34 @@ class UnitList(NamedTuple):
     count: object       # int32 [1] device: the number of entries
 
 
+# The reduces a visiting backward leaves to ConvOp.step_epilogue (defer=): its layer's and, fused-first, the first layer's.  partial: device
+# address of the per-workgroup partials; dWs: the three gradients summed into; ws: the launch's workspace, which keeps the partials alive.
+ReduceJob = NamedTuple("ReduceJob", [("partial", int), ("n_wg", int), ("c_aux", int), ("c_dz", int), ("dWs", list), ("ws", object)])
+FirstReduceJob = NamedTuple("FirstReduceJob", [("partial", int), ("n_wg", int), ("dWs", list), ("ws", object)])
+
+
+class ZeroPool(dict):
+    """{shape: [fp32 buffers]} of a plan.  A buffer in the pool is all-zero: whoever gives one back has wiped what was written into it
+    (ConvOp.clear, clear_mask, scn_readout_clear_dz, the step epilogue), so a taker writes only the rows it needs.  The one exception: a
+    readout gradient of at most SconePlan.SMALL_DZ_BYTES goes back as it is, and _readout_grad, its only taker, has it zeroed in the launch."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def take(self, like, zeroed=True):
+        shape = tuple(getattr(like, "shape", like))     # (a shape or a tensor; zeroed=False: a fresh buffer is left uninitialised)
+        return self[shape].pop() if self.get(shape) else (torch.zeros if zeroed else torch.empty)(shape, device=self.device, dtype=torch.float32)
+
+    def give(self, t):
+        self.setdefault(tuple(t.shape), []).append(t)
+
+
+def deferred_clears(L):
+    """Layers of an L-layer cone whose gradient buffer a step leaves for its epilogue to wipe: those with no layer below that takes a pooled
+    buffer again -- layer j >= 2 takes one for its dx, layer 1 writes none: layers 2 and 1 -- so the pool's peak stays the separate calls'."""
+    return set(range(1, min(L, 3)))
+
+
 def _unit_ptrs(units):
     return (_dev(units.units, torch.int32), _dev(units.count, torch.int32)) if units is not None else (None, None)
 
@@ -536,8 +564,8 @@ class ConvOp:
         visit: a mask V one hop out from a mask outside whose items dzs[0] is all-zero: only V's items are visited, with the plain
         call's dWs and its dx on V; `dx` must be given and every other row of it is left as it is; False when not served
         (scn_conv_backward_visit).
-        defer (with visit): a list -- the launch leaves its weight-gradient partials in its workspace and appends the reduce job
-        ("reduce", workspace, n_wg, c_aux, c_dz, dWs) for the step epilogue (scn_conv_backward_visit_partial, step_epilogue)."""
+        defer (with visit): a list -- the launch leaves its weight-gradient partials in its workspace and appends their ReduceJob
+        for step_epilogue (scn_conv_backward_visit_partial)."""
         lib = _lib.load()
         assert wl is None or (dx is not None or not need_dx)
         assert dz_mask is None or (wl is None and dx_partial is None)
@@ -576,7 +604,7 @@ class ConvOp:
             if not _launch(key, None, "scn_conv_backward_visit_partial", lib.scn_conv_backward_visit_partial, *head,
                            _dev(dx) if need_dx else None, *ws, _dev(visit, torch.int32), ctypes.byref(n_wg), _stream(), may_decline=True):
                 return False
-            defer.append(("reduce", ws, n_wg.value, c_aux, c_dz[0], dWs))
+            defer.append(ReduceJob(ws[0].value, n_wg.value, c_aux, c_dz[0], dWs, ws))
         elif visit is not None:                       # (no byte model: the visited items' count is on the device)
             _visit_prefetch(lib)
             if not _launch(key, None, "scn_conv_backward_visit",
@@ -675,8 +703,8 @@ class ConvOp:
         dWs_first are accumulated, the input gradient is never written (scn_conv_backward_fused_first).  False when the shape
         is not served.  aux = None with Ws_first (the first layer's weights): the first layer's output is rebuilt from y
         inside the kernel instead of being read (scn_conv_backward_fused_first_from_y, 32 channels).  visit (with Ws_first, dense): as
-        in backward (scn_conv_backward_fused_first_from_y_visit).  defer (with visit): a list that takes the launch's two reduce jobs,
-        as in backward (scn_conv_backward_fused_first_from_y_visit_partial)."""
+        in backward (scn_conv_backward_fused_first_from_y_visit).  defer (with visit): a list that takes the launch's ReduceJob and
+        FirstReduceJob, as in backward (scn_conv_backward_fused_first_from_y_visit_partial)."""
         lib = _lib.load()
         S, rows, ns, c = dz.shape
         if (aux is not None and tuple(aux.shape) != (S, rows, ns, c)) or tuple(y.shape) != (S, rows, ns, Y_STRIDE) or self.n_groups != 1:
@@ -700,8 +728,8 @@ class ConvOp:
                                lib.scn_conv_backward_fused_first_from_y_visit_partial, *head, _ptrs(Ws_first), c, ACT[act], _dev(y), *ws,
                                _dev(visit, torch.int32), ctypes.byref(n_wg), _stream(), may_decline=True):
                     return False
-                defer.append(("reduce", ws, n_wg.value, c, c, dWs))
-                defer.append(("first", ws, n_wg.value, c, dWs_first))
+                defer.append(ReduceJob(ws[0].value, n_wg.value, c, c, dWs, ws))
+                defer.append(FirstReduceJob(ws[0].value + 4 * n_wg.value * 3 * c * c, n_wg.value, dWs_first, ws))   # (behind n_wg x 3 x c x c floats)
                 return True
             return _launch(key, None, "scn_conv_backward_fused_first_from_y_visit", lib.scn_conv_backward_fused_first_from_y_visit,
                            *head, _ptrs(Ws_first), *tail, _dev(visit, torch.int32), _stream(), may_decline=True)
@@ -711,6 +739,35 @@ class ConvOp:
                            lib.scn_conv_backward_fused_first_from_y, *head, _ptrs(Ws_first), *tail, wl_ref, _stream())
         return _launch(key, None if wl is not None else _nbytes(dz, aux, y) + self.csr_bytes, "scn_conv_backward_fused_first",
                        lib.scn_conv_backward_fused_first, *head, _dev(aux), *tail, wl_ref, _stream())
+
+    def step_epilogue(self, loss, readout_dw, jobs, clears, readout_args):
+        """All of a cone step that nothing waits for before the micro-batch ends, in ONE launch (scn_step_epilogue; under the masked clear's
+        timer key, which it does, with no byte model as there).  loss = (logp, y, scale, out, overwrite): out[0] (fp64) += scale * <logp, y>,
+        or = with overwrite; readout_dw = (d_logits, bh, dW): the readout's weight gradient, added to dW; jobs: what the deferred backwards
+        left; clears: (tensor, mask) pairs, each wiped as clear_mask does -- mask None: a readout gradient, wiped as scn_readout_clear_dz
+        does by readout_args = SconePlan._readout_args(last nodes, sign=False, edge_nodes=True), which is not looked at without one."""
+        d = _lib.StepEpilogueDesc()
+        ptr = lambda t, dtype=torch.float32: _dev(t, dtype).value
+        logp, y, scale, out, overwrite = loss
+        d.loss_n, d.logp, d.y, d.scale, d.loss, d.overwrite = logp.numel(), ptr(logp), ptr(y), float(scale), out.data_ptr(), 1 if overwrite else 0
+        d_logits, bh, dW = readout_dw
+        d.rd_nd, d.rd_c, d.rd_dl, d.rd_bh, d.rd_d_w = d_logits.numel(), bh.shape[2], ptr(d_logits), ptr(bh), ptr(dW)
+        for job in jobs:
+            if isinstance(job, ReduceJob):
+                q = d.reduce[d.n_reduce]
+                q.partial, q.n_wg, q.c_aux, q.c_dz, q.dW[:] = job.partial, job.n_wg, job.c_aux, job.c_dz, [ptr(t) for t in job.dWs]
+                d.n_reduce += 1
+            else:
+                d.first_form, d.first_partial, d.first_n_wg, d.first_dW[:] = 1, job.partial, job.n_wg, [ptr(t) for t in job.dWs]
+        for t, mask in clears:
+            if mask is None:
+                nbr, _, d.rc_max_deg, last, inc_ptr, inc_edge, nodes = readout_args
+                d.rc_dz, (d.rc_n_slabs, d.rc_n_edges, d.rc_ns, d.rc_c) = ptr(t), t.shape
+                d.rc_nbr, d.rc_last_nodes, d.rc_inc_ptr, d.rc_inc_edge, d.rc_edge_nodes = (p.value for p in (nbr, last, inc_ptr, inc_edge, nodes))
+            else:
+                d.clear[d.n_clear] = _lib.EpiClear(ptr(t), ptr(mask, torch.int32), t.shape[0], t.shape[2], t.shape[3])
+                d.n_clear += 1
+        _launch("clear_mask", None, "scn_step_epilogue", _lib.load().scn_step_epilogue, self.handle, ctypes.byref(d), _stream())
 
     def clear(self, t, wl):
         """Zero the listed items of a [S, rows, ns, C] tensor (scn_clear_list)."""
@@ -1226,8 +1283,7 @@ class SconePlan(Plan):
         self.n_edges = self.n_rows = E
         self._init_operators(S_lower, S_upper)
         self.bconds = bconds
-        self._dz_zero = {}                              # all-zero readout-gradient buffers, by shape (see backward)
-        self._zero_pool = {}                            # zero-skipping mode: all-zero activation / gradient buffers
+        self._dz_zero, self._zero_pool = ZeroPool(device), ZeroPool(device)    # readout gradients and a cone's dx; the zero-skipping mode's
         self._blocks = None                             # (block of row, block adjacency), built on first use
         self._act_cache = None                          # _trajectory_supports of the last data set
         self._field = None                              # device copies of field_tables, built on first use (field_tables_dev)
@@ -1341,7 +1397,7 @@ class SconePlan(Plan):
             keep = masks[k] if cone is not None or (route.keep_last and k == 0) else None
             units = cone.units[k] if cone is not None and cone.units is not None else None
             wl = activity["fwd"][i] if activity else None
-            out = self._zeros((S, E, ns, c_out)) if activity else out_last if (k == 0 and i > 0) else None
+            out = self._zero_pool.take((S, E, ns, c_out)) if activity else out_last if (k == 0 and i > 0) else None
             if i == 0 and route.first == "from_y":      # y only: H1 is never stored (hs[1] is None)
                 y0, h = self.conv.shifted_input(x, keep=keep, units=units), None
                 if y0 is None:
@@ -1349,8 +1405,8 @@ class SconePlan(Plan):
             elif i == 0:
                 first = None
                 if route.first == "stored":             # 1-channel input: keep the shifted input for the weight gradient
-                    first = self.conv.forward_first(x, w, c_out, self.act, out=out, y=self._zeros((S, E, ns, Y_STRIDE)) if activity else None,
-                                                    wl=wl)
+                    first = self.conv.forward_first(x, w, c_out, self.act, out=out, wl=wl,
+                                                    y=self._zero_pool.take((S, E, ns, Y_STRIDE)) if activity else None)
                 assert first is not None or not activity
                 if first is None:                       # an ordinary layer (also where forward_first is declined): no y, no fused-first backward
                     route = route._replace(first="plain", fused_first=False)
@@ -1486,23 +1542,16 @@ class SconePlan(Plan):
             self._field = FieldTables(len(ap) - 1, to(tp), to(tb), to(ap), to(ab))
         return self._field
 
-    def _zeros(self, shape):
-        pool = self._zero_pool.setdefault(tuple(shape), [])
-        return pool.pop() if pool else torch.zeros(tuple(shape), device=self.device, dtype=torch.float32)
-
     def release(self, saved):
         """Forward-only use of the zero-skipping mode (prediction): hand the forward's pooled buffers back, all-zero again."""
         if saved.activity:
-            self._give_back_forward(saved)
+            for l in range(1, len(saved.hs)):
+                self._give_back(saved.hs[l], saved.activity["fwd"][l - 1])
+            self._give_back(saved.y0, saved.activity["fwd"][0])
 
     def _give_back(self, t, wl):
         self.conv.clear(t, wl)                              # all-zero again
-        self._zero_pool.setdefault(tuple(t.shape), []).append(t)
-
-    def _give_back_forward(self, saved):
-        for l in range(1, len(saved.hs)):
-            self._give_back(saved.hs[l], saved.activity["fwd"][l - 1])
-        self._give_back(saved.y0, saved.activity["fwd"][0])
+        self._zero_pool.give(t)
 
     def _readout_args(self, last_dev, sign=True, edge_nodes=False):
         """The readout tables as every launch that reads them takes them: nbr, n_nodes, max_deg, last nodes, inc_ptr, inc_edge
@@ -1512,16 +1561,51 @@ class SconePlan(Plan):
                 i32(self.inc_edge)) + ((_dev(self.inc_sign),) if sign else ()) + ((i32(self.edge_nodes),) if edge_nodes else ())
 
     def readout(self, H, w_last, last_dev):
-        lib = _lib.load()
         S, E, ns, C = H.shape
-        N = S * ns
         assert tuple(w_last.shape) == (C, 1), "readout weight must be (C, 1) (STM:233, out_channels = 1)"
-        bh = torch.empty((N, self.max_deg, C), device=H.device, dtype=torch.float32)
-        logits = torch.empty((N, self.max_deg), device=H.device, dtype=torch.float32)
-        logp = torch.empty_like(logits)
-        check(lib.scn_readout_forward(S, ns, E, C, _dev(H), _dev(w_last), *self._readout_args(last_dev), _dev(bh), _dev(logits),
-                                      _dev(logp), _stream()), "scn_readout_forward")
+        bh = torch.empty((S * ns, self.max_deg, C), device=H.device, dtype=torch.float32)
+        logits, logp = (torch.empty((S * ns, self.max_deg), device=H.device, dtype=torch.float32) for _ in range(2))
+        check(_lib.load().scn_readout_forward(S, ns, E, C, _dev(H), _dev(w_last), *self._readout_args(last_dev), _dev(bh), _dev(logits),
+                                              _dev(logp), _stream()), "scn_readout_forward")
         return logp, bh, logits
+
+    def _readout_step(self, H, w_last, last_dev, yt, scale, zero_buf):
+        """readout, d_logp = yt * scale and _readout_grad in ONE launch, which also zeroes zero_buf where given (scn_readout_step): dz as
+        _readout_grad leaves it, and what the epilogue sums the loss and dW_last from.  dz None (nothing launched, the pool as it was): declined."""
+        S, E, ns, C = H.shape
+        bh = torch.empty((S * ns, self.max_deg, C), device=H.device, dtype=torch.float32)
+        logits, logp, d_logp, d_logits = (torch.empty((S * ns, self.max_deg), device=H.device, dtype=torch.float32) for _ in range(4))
+        dz = self._dz_zero.take(H)
+        zero = (_dev(zero_buf), zero_buf.numel()) if zero_buf is not None else (None, 0)
+        if not _served(_lib.load().scn_readout_step(S, ns, E, C, _dev(H), _dev(w_last), *self._readout_args(last_dev, edge_nodes=True), _dev(yt),
+                                                    float(scale), ACT[self.act], _dev(bh), _dev(logits), _dev(logp), _dev(d_logp), _dev(d_logits),
+                                                    _dev(dz), 1, *zero, _stream()), "scn_readout_step"):
+            self._dz_zero.give(dz)                      # (declined before any launch: still all-zero)
+            return None, None, None, None
+        return dz, logp, d_logits, bh
+
+    def _readout_grad(self, H, bh, logp, d_logp, last_dev, weights, grads):
+        """Gradient of the readout w.r.t. the last layer's pre-activation, into a pooled all-zero buffer: zero except on the edges around the
+        last nodes, which _wipe_and_keep wipes again (no 16 GB memset); up to SMALL_DZ_BYTES the launch zeroes it itself (dz_is_zero = 2)."""
+        S, E, ns, C = H.shape
+        small = H.numel() * 4 <= self.SMALL_DZ_BYTES
+        dz_top = self._dz_zero.take(H, zeroed=not small)
+        d_logits, d_logp = torch.empty_like(logp), d_logp.contiguous()
+        check(_lib.load().scn_readout_backward(S, ns, E, C, _dev(H), _dev(weights[-1]), *self._readout_args(last_dev, edge_nodes=True), _dev(bh),
+                                               _dev(d_logp), _dev(logp), ACT[self.act], _dev(d_logits), _dev(dz_top), 2 if small else 1,
+                                               _dev(grads[-1]), _stream()), "scn_readout_backward")
+        return dz_top
+
+    def _wipe_and_keep(self, dz, last_dev, mask=None):
+        """A layer is done with its gradient buffer: wipe the items written and keep it.  mask: the one a visiting backward wrote it on;
+        None: a readout gradient, wiped on the rows around the last nodes (not where the launch zeroes the buffer itself)."""
+        if mask is not None:
+            self.conv.clear_mask(dz, mask)
+        elif dz.numel() * 4 > self.SMALL_DZ_BYTES:
+            S, E, ns, C = dz.shape
+            check(_lib.load().scn_readout_clear_dz(S, ns, E, C, *self._readout_args(last_dev, sign=False, edge_nodes=True),
+                                                   _dev(dz), _stream()), "scn_readout_clear_dz")
+        self._dz_zero.give(dz)
 
     def _blocked(self):
         op = self.conv if self.conv is not None else self.op
@@ -1602,93 +1686,26 @@ class SconePlan(Plan):
 
     def step(self, x, last_dev, yt, scale, weights, grads, part, overwrite=False, zero_buf=None, cone=None):
         """grads[k] += d/dW[k] of scale * sum_n <logp_n, yt_n> and part[0] += that sum (overwrite: part[0] = ...), as forward /
-        scn_masked_ce_begin / backward compute them bit for bit, on the cone route of a plain stack at hidden 32: the forward stack,
-        ONE readout launch (forward, d_logp = yt * scale, backward; it also zeroes zero_buf -- the flat gradient buffer of a fresh
-        step, or None), the visiting backwards with their reduces left undone, and ONE epilogue launch for everything nothing waits
-        for before the micro-batch ends: the loss sum, the readout's weight gradient, every dW reduce and the clears of the pooled
-        gradient buffers.  False (nothing launched that changes grads, part or a pooled buffer) where the route or shape is not served:
-        the caller runs the separate calls.
-        cone: this micro-batch's Cone from step_cones() -- its masks are not built here then; None: they are, in five launches.
-        A clear is deferred only where no layer further down takes a pooled buffer again, so the pool's peak is the separate calls'."""
-        lib = _lib.load()
+        scn_masked_ce_begin / backward compute them bit for bit, on the cone route of a plain stack at hidden 32: the forward stack, ONE
+        readout launch (_readout_step; zero_buf: a fresh step's flat gradient buffer, or None), backward()'s walk with its reduces and lowest
+        wipes deferred (_cone_backward) and ONE launch for those (ConvOp.step_epilogue).  False (nothing launched that changes grads, part or
+        a pooled buffer): not served, the caller runs the separate calls.  cone: from step_cones(); None: the masks are built here, in five."""
         route = self._step_route(x, last_dev, yt, weights)
-        if route is None:
-            return False
         L = (len(weights) - 1) // 3
-        S, E, ns, _ = x.shape
-        N = S * ns
-        ran = self._layers(route, cone if cone is not None else self._masks(route, last_dev, L), x, weights, None, None, L)
+        ran = route and self._layers(route, cone if cone is not None else self._masks(route, last_dev, L), x, weights, None, None, L)
         if ran is None:
             return False
         hs, y0, cone, route = ran
-        H = hs[-1]
-        C = H.shape[3]
-        key = (S, E, ns, C)
-        assert cone is not None and H.numel() * 4 > self.SMALL_DZ_BYTES      # (what makes a cone: the gradient buffers are kept all-zero)
-        bh = torch.empty((N, self.max_deg, C), device=H.device, dtype=torch.float32)
-        logits, logp, d_logp, d_logits = (torch.empty((N, self.max_deg), device=H.device, dtype=torch.float32) for _ in range(4))
-        take = lambda: self._dz_zero[key].pop() if self._dz_zero.get(key) else torch.zeros_like(H)
-        give = lambda t: self._dz_zero.setdefault(key, []).append(t)
-        dz = take()
-        if not _served(lib.scn_readout_step(S, ns, E, C, _dev(H), _dev(weights[-1]), *self._readout_args(last_dev, edge_nodes=True), _dev(yt),
-                                            float(scale), ACT[self.act], _dev(bh), _dev(logits), _dev(logp), _dev(d_logp), _dev(d_logits),
-                                            _dev(dz), 1, _dev(zero_buf) if zero_buf is not None else None,
-                                            zero_buf.numel() if zero_buf is not None else 0, _stream()), "scn_readout_step"):
-            give(dz)                                     # (declined before any launch: still all-zero)
+        assert cone is not None and hs[-1].numel() * 4 > self.SMALL_DZ_BYTES   # (what makes a cone: the gradient buffers are kept all-zero)
+        dz, logp, d_logits, bh = self._readout_step(hs[-1], weights[-1], last_dev, yt, scale, zero_buf)
+        if dz is None:
             return False
-        jobs, top, clears = [], None, []
-        for i in reversed(range(1, L)):
-            w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
-            visit = cone[L - i]
-            if i == 1:                                  # H1 is rebuilt from y0, dW_first in the same launch, no dx
-                assert self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit,
-                                                        defer=jobs), "aux-free fused-first backward not served"
-                dx = None
-            else:
-                dx = take()
-                assert self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit, defer=jobs) is not False, \
-                    "visiting backward not served"
-            taken_again = i - 1 >= 2                    # the layer below pops a pooled buffer: this one has to be back, all-zero, by then
-            if i == L - 1 and taken_again:
-                self._release_top(dz, key, last_dev)
-            elif i == L - 1:
-                top = dz
-            elif taken_again:
-                self.conv.clear_mask(dz, cone[L - 1 - i])
-                give(dz)
-            else:
-                clears.append((dz, cone[L - 1 - i]))
-            dz = dx
-        d = _lib.StepEpilogueDesc()
-        ptr = lambda t, dtype=torch.float32: _dev(t, dtype).value
-        d.loss_n, d.logp, d.y, d.scale, d.loss, d.overwrite = logp.numel(), ptr(logp), ptr(yt), float(scale), part.data_ptr(), 1 if overwrite else 0
-        d.rd_nd, d.rd_c, d.rd_dl, d.rd_bh, d.rd_d_w = N * self.max_deg, C, ptr(d_logits), ptr(bh), ptr(grads[-1])
-        for job in jobs:
-            if job[0] == "reduce":
-                _, ws, n_wg, c_aux, c_dz, dWs = job
-                q = d.reduce[d.n_reduce]
-                q.partial, q.n_wg, q.c_aux, q.c_dz = ws[0].value, n_wg, c_aux, c_dz
-                for k in range(3):
-                    q.dW[k] = ptr(dWs[k])
-                d.n_reduce += 1
-            else:                                       # the first layer's partials lie behind the layer's own in the same workspace
-                _, ws, n_wg, c, dWs = job
-                d.first_form, d.first_partial, d.first_n_wg = 1, ws[0].value + 4 * n_wg * 3 * c * c, n_wg
-                for k in range(3):
-                    d.first_dW[k] = ptr(dWs[k])
-        if top is not None:
-            i32 = torch.int32
-            d.rc_n_slabs, d.rc_ns, d.rc_n_edges, d.rc_c, d.rc_max_deg = S, ns, E, C, self.max_deg
-            d.rc_nbr, d.rc_last_nodes, d.rc_inc_ptr, d.rc_inc_edge = ptr(self.nbr, i32), ptr(last_dev, i32), ptr(self.inc_ptr, i32), ptr(self.inc_edge, i32)
-            d.rc_edge_nodes, d.rc_dz = ptr(self.edge_nodes, i32), ptr(top)
-        for t, mask in clears:
-            q = d.clear[d.n_clear]
-            q.tensor, q.mask, q.n_slabs, q.ns, q.channels = ptr(t), ptr(mask, torch.int32), t.shape[0], t.shape[2], t.shape[3]
-            d.n_clear += 1
-        # (under the masked clear's key: it is the launch that does that clear; no byte model, as there)
-        _launch("clear_mask", None, "scn_step_epilogue", lib.scn_step_epilogue, self.conv.handle, ctypes.byref(d), _stream())
-        for t in ([top] if top is not None else []) + [t for t, _ in clears]:
-            give(t)
+        jobs = []
+        waiting = self._cone_backward(hs, y0, cone, dz, last_dev, weights, grads, defer=jobs)
+        self.conv.step_epilogue((logp, yt, scale, part, overwrite), (d_logits, bh, grads[-1]), jobs, waiting,
+                                self._readout_args(last_dev, sign=False, edge_nodes=True) if waiting[0][1] is None else None)
+        for t, _ in waiting:
+            self._dz_zero.give(t)
         return True
 
     def promotion(self, weights):
@@ -1762,21 +1779,10 @@ class SconePlan(Plan):
         hs, bhs, y0 = saved.hs, saved.bh, saved.y0
         k, L = len(hs[-1]), len(hs) - 1
         # the readout's gradient block by block (d_logits depends on the summed logits only), each into its own pooled all-zero buffer
-        tops = [self._readout_grad(hs[-1][j], bhs[j], logp, d_logp, last_dev, [w[-1][32 * j:32 * j + 32]], [grads[-1][32 * j:32 * j + 32]])
+        dzs = [self._readout_grad(hs[-1][j], bhs[j], logp, d_logp, last_dev, [w[-1][32 * j:32 * j + 32]], [grads[-1][32 * j:32 * j + 32]])
                 for j in range(k)]
-        dzs = [t[0] for t in tops]
-        for l in reversed(range(L)):
+        for l in reversed(range(1, L)):
             W, G = w[3 * l:3 * l + 3], grads[3 * l:3 * l + 3]
-            if l == 0:                                  # dW_s[0, j] = sum_p (S_s x)[p] dz_j[p]: one stream over dz per block
-                for j in range(k):
-                    gj = [torch.zeros((1, 32), device=self.device, dtype=torch.float32) for _ in range(3)]
-                    assert self.conv.dw_first(hs[0][0], y0, dzs[j], gj)
-                    for Gs, g in zip(G, gj):
-                        Gs[:, 32 * j:32 * j + 32] += g
-                if L == 1:                              # (a single wide layer: the readout gradients were this layer's dz)
-                    for dz_top, key in tops:
-                        self._release_top(dz_top, key, last_dev)
-                break
             new = []
             for i in range(len(hs[l])):
                 acc = None                              # output block by output block INTO the input block's gradient (in place)
@@ -1788,67 +1794,66 @@ class SconePlan(Plan):
                         Gs[32 * i:32 * i + 32, 32 * j:32 * j + 32] += g
                 new.append(acc)
             if l == L - 1:                              # the top layer is done with the readout gradients: wipe and keep them
-                for dz_top, key in tops:
-                    self._release_top(dz_top, key, last_dev)
+                for dz_top in dzs:
+                    self._wipe_and_keep(dz_top, last_dev)
             dzs = new
+        for j in range(k):                              # the first layer: dW_s[0, j] = sum_p (S_s x)[p] dz_j[p], one stream over dz per block
+            gj = [torch.zeros((1, 32), device=self.device, dtype=torch.float32) for _ in range(3)]
+            assert self.conv.dw_first(hs[0][0], y0, dzs[j], gj)
+            for Gs, g in zip(grads[0:3], gj):
+                Gs[:, 32 * j:32 * j + 32] += g
+        if L == 1:                                      # (a single wide layer: the readout gradients were this layer's dz)
+            for dz_top in dzs:
+                self._wipe_and_keep(dz_top, last_dev)
         return grads
 
-    def _readout_grad(self, H, bh, logp, d_logp, last_dev, weights, grads):
-        """Gradient of the readout w.r.t. the last layer's pre-activation, into a pooled all-zero buffer (it is zero except
-        on the edges around the last nodes; _release_top wipes exactly those rows again -- no 16 GB memset)."""
-        lib = _lib.load()
-        S, E, ns, C = H.shape
-        key = (S, E, ns, C)
-        pool = self._dz_zero.get(key)
-        # small complexes: the launch zeroes the buffer itself, every trajectory's wave its own column (dz_is_zero = 2) -- no fill launch;
-        # large ones: a pooled all-zero buffer whose touched rows are wiped after use (_release_top)
-        small = H.numel() * 4 <= self.SMALL_DZ_BYTES
-        dz_top = pool.pop() if pool else (torch.empty_like(H) if small else torch.zeros_like(H))
-        d_logits = torch.empty_like(logp)
-        d_logp = d_logp.contiguous()
-        check(lib.scn_readout_backward(S, ns, E, C, _dev(H), _dev(weights[-1]), *self._readout_args(last_dev, edge_nodes=True), _dev(bh),
-                                       _dev(d_logp), _dev(logp), ACT[self.act], _dev(d_logits), _dev(dz_top), 2 if small else 1,
-                                       _dev(grads[-1]), _stream()), "scn_readout_backward")
-        return dz_top, key
-
-    def _release_top(self, dz_top, key, last_dev):
-        S, E, ns, C = key
-        if dz_top.numel() * 4 <= self.SMALL_DZ_BYTES:
-            self._dz_zero.setdefault(key, []).append(dz_top)     # (may hold anything: see _readout_grad)
-            return
-        check(_lib.load().scn_readout_clear_dz(S, ns, E, C, *self._readout_args(last_dev, sign=False, edge_nodes=True),
-                                               _dev(dz_top), _stream()), "scn_readout_clear_dz")
-        self._dz_zero.setdefault(key, []).append(dz_top)
+    def _cone_backward(self, hs, y0, cone, dz, last_dev, weights, grads, defer=None):
+        """The walk down a cone [M0 .. M_{L-1}], layers L-1 .. 1, from a readout gradient dz already written: the one loop of backward() and
+        step().  Layer l visits M_{L-l+1}, one hop out from the set its dZ_l was written on, and dX_l goes into a pooled all-zero buffer on the
+        visited items only (layer 1 rebuilds H1 from y0 and sums dW_first in the same launch: no dx); then dZ_l is wiped on the mask the layer
+        above visited and given back.  defer = None: every reduce inside its launch, every wipe after its layer.  defer = a list: it takes the
+        reduces as jobs, and the wipes of deferred_clears(L) wait too: returned as step_epilogue's clears; the caller gives them back after it."""
+        L = len(hs) - 1
+        waits, waiting = deferred_clears(L) if defer is not None else (), []
+        for i in reversed(range(1, L)):
+            w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
+            dx = self._dz_zero.take(dz) if i > 1 else None
+            if i == 1:
+                ok = self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=cone[L - i], defer=defer)
+            else:
+                ok = self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=cone[L - i], defer=defer) is not False
+            assert ok, "visiting backward of layer %d not served" % (i + 1)
+            mask = cone[L - 1 - i] if i < L - 1 else None
+            if i in waits:
+                waiting.append((dz, mask))
+            else:
+                self._wipe_and_keep(dz, last_dev, mask)
+            dz = dx
+        return waiting
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
-        """One loop down the layers by the route the forward ran (saved.route).  On a cone (saved.cone = [M0 .. M_{L-1}]) layer l visits
-        M_{L-l+1}, one hop out from the set its dZ_l was written on, and dX_l goes into a pooled all-zero buffer (the readout
-        gradient's pool: same shape, same all-zero state) on the visited items only; once its consumer has run, the masked clear wipes
-        exactly those items.  Off the cone the top layer stages dZ_L by hop(M0) where the route says so: the mask is built from the
-        last nodes the readout's backward got, for this call alone."""
+        """On a cone _cone_backward, reducing and wiping as it goes; else one loop down the layers by the route the forward ran: the top
+        layer stages dZ_L by hop(M0) where it says so -- the mask is built from the readout's last nodes, for this call alone."""
         if saved.wide:
             return self._wide_backward(saved, logp, d_logp, last_dev, weights, grads)
-        hs, y0, activity, cone, route = saved.hs, saved.y0, saved.activity, saved.cone, saved.route
+        hs, y0, activity, route = saved.hs, saved.y0, saved.activity, saved.route
         L = len(hs) - 1
-        dz, key = self._readout_grad(hs[-1], saved.bh, logp, d_logp, last_dev, weights, grads)
+        dz = self._readout_grad(hs[-1], saved.bh, logp, d_logp, last_dev, weights, grads)
+        if saved.cone is not None:
+            self._cone_backward(hs, y0, saved.cone, dz, last_dev, weights, grads)
+            return grads
         for i in reversed(range(L)):
             w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
             wl_out = activity["bwd"][i] if (activity and i > 0) else None      # items of this layer's input gradient
             wl_in = activity["bwd"][i + 1] if activity else None                # support of dz
-            visit = cone[L - i] if cone is not None else None
-            first_done = i == 0                         # the first layer's weight gradient is out: nothing is left below
             if i == 1 and route.first == "from_y":      # H1 was never stored: aux is rebuilt from y0, dW_first in the same launch, no dx
-                assert self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visit), \
+                assert self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3]), \
                     "aux-free fused-first backward not served"
-                first_done, dx = True, None
+                dx = None
             elif i == 1 and route.fused_first and self.conv_T.backward_fused_first(dz, w, hs[1], self.act, y0, g, grads[0:3], wl=wl_out):
-                first_done, dx = True, None             # dx of this layer only feeds dW_first: contracted in registers, never written
+                dx = None                               # dx of this layer only feeds dW_first: contracted in registers, never written
             elif i == 0 and hs[0].shape[3] == 1 and self.conv.dw_first(hs[0], y0, dz, g, wl=wl_in):
                 dx = None                               # first layer: shifted 1-channel input x one stream over dz
-            elif cone is not None:
-                pool = self._dz_zero.get(key)
-                dx = pool.pop() if pool else torch.zeros_like(dz)
-                assert self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visit) is not False, "visiting backward not served"
             else:
                 assert not activity or i > 0, "zero-skipping needs the first-layer fast path"
                 dx = False                              # the top layer: dz staged only where the readout wrote it (False: not served)
@@ -1857,19 +1862,15 @@ class SconePlan(Plan):
                     m1 = self.conv.mask_hop(self.conv.keep_mask(last_dev, NS, self.n_nodes, tabs, key="dz_mask"), tabs)
                     dx = self.conv_T.backward([dz], w, hs[i], self.act, True, g, dz_mask=m1)
                 if dx is False:
-                    dx = self.conv_T.backward([dz], w, hs[i], self.act, i > 0, g, dx=self._zeros(hs[i].shape) if activity else None, wl=wl_out)
+                    dx = self.conv_T.backward([dz], w, hs[i], self.act, i > 0, g, dx=self._zero_pool.take(hs[i]) if activity else None, wl=wl_out)
             if i == L - 1:                              # the top layer is done with the readout gradient: wipe and keep it
-                self._release_top(dz, key, last_dev)
-            elif cone is not None:                      # wipe what the layer above wrote, on the mask it visited
-                self.conv.clear_mask(dz, cone[L - 1 - i])
-                self._dz_zero.setdefault(key, []).append(dz)
+                self._wipe_and_keep(dz, last_dev)
             elif activity:
                 self._give_back(dz, wl_in)
-            if first_done:
+            if dx is None:                              # the first layer's weight gradient is out: nothing is left below
                 break
             dz = dx
-        if activity:                                    # the forward's buffers go back to the pool, all-zero again
-            self._give_back_forward(saved)
+        self.release(saved)                             # (zero-skipping: the forward's buffers go back to the pool, all-zero again)
         return grads
 
 
@@ -1919,9 +1920,8 @@ class PowerPlan(SconePlan):
 
     def _backward(self, saved, logp, d_logp, last_dev, weights, grads):
         hs, bh, y0 = saved.hs, saved.bh, saved.y0
-        dz_top, key = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
+        dz = self._readout_grad(hs[-1], bh, logp, d_logp, last_dev, weights, grads)
         L = len(hs) - 1
-        dz = dz_top
         for i in reversed(range(L)):
             g1 = self._shift(self.op_T, dz) if not (i == 0 and y0 is not None) else None
             served, dx = (self.op_T.backward_power(dz, g1, weights[3 * i:3 * i + 3], hs[i], self.act, i > 0,
@@ -1936,7 +1936,7 @@ class PowerPlan(SconePlan):
                 dx = dense_terms_backward([dz, g1, g2], weights[3 * i:3 * i + 3], hs[i], self.act, i > 0,
                                           grads[3 * i:3 * i + 3])
             if i == L - 1:
-                self._release_top(dz_top, key, last_dev)
+                self._wipe_and_keep(dz, last_dev)
             dz = dx
         return grads
 

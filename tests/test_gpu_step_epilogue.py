@@ -218,23 +218,24 @@ def test_partial_backwards_plus_epilogue_equal_the_reducing_backwards(act):
     fW, fF = [t.clone() for t in f["dW0"]], [t.clone() for t in f["dWf0"]]
     assert f["plan"].conv_T.backward_fused_first(f["dz"], f["W"], None, act, f["y"], fW, fF, Ws_first=f["Wf"], visit=f["mask"], defer=jobs)
     torch.cuda.synchronize()
-    assert [j[0] for j in jobs] == ["reduce", "reduce", "first"]
+    assert [type(j) for j in jobs] == [ops.ReduceJob, ops.ReduceJob, ops.FirstReduceJob]
     for a, b in zip(dW + fW + fF, c["dW0"] + f["dW0"] + f["dWf0"]):
         assert np.array_equal(_bits(a), _bits(b)), "a deferred backward touched a weight gradient"
     d = _lib.StepEpilogueDesc()
     for job in jobs:
-        if job[0] == "reduce":
-            _, ws, n_wg, c_aux, c_dz, dWs = job
+        if isinstance(job, ops.ReduceJob):
             q = d.reduce[d.n_reduce]
-            q.partial, q.n_wg, q.c_aux, q.c_dz = ws[0].value, n_wg, c_aux, c_dz
+            assert job.partial == job.ws[0].value
+            q.partial, q.n_wg, q.c_aux, q.c_dz = job.partial, job.n_wg, job.c_aux, job.c_dz
             for k in range(3):
-                q.dW[k] = dWs[k].data_ptr()
+                q.dW[k] = job.dWs[k].data_ptr()
             d.n_reduce += 1
         else:
-            _, ws, n_wg, ch, dWs = job
-            d.first_form, d.first_partial, d.first_n_wg = 1, ws[0].value + 4 * n_wg * 3 * ch * ch, n_wg
+            ch = f["dz"].shape[3]
+            assert job.partial == job.ws[0].value + 4 * job.n_wg * 3 * ch * ch, "the first layer's partials lie behind the layer's own"
+            d.first_form, d.first_partial, d.first_n_wg = 1, job.partial, job.n_wg
             for k in range(3):
-                d.first_dW[k] = dWs[k].data_ptr()
+                d.first_dW[k] = job.dWs[k].data_ptr()
     assert _lib.load().scn_step_epilogue(None, ctypes.byref(d), ops._stream()) == 0
     torch.cuda.synchronize()
     assert np.array_equal(_bits(dx), _bits(dx_ref)), "dx"

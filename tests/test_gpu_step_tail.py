@@ -5,6 +5,8 @@ calls (forward, scn_masked_ce_begin, backward), BIT FOR BIT on the loss and ever
     separate calls run;
   * two consecutive steps on one plan that end at different last nodes: the pooled gradient buffers are all-zero after each and as
     many as the separate calls leave (a deferred clear must not raise the pool's peak);
+  * step(), the separate calls and step() again on ONE plan of four layers: the one pool both feed is all-zero and as large after each,
+    and each micro-batch equals the same one on a fresh plan;
   * Scone_GCN._accumulate_staged over two micro-batches with fresh = True and the flat gradient buffer pre-filled with garbage;
   * hidden 16, READOUT_CONE off and a PowerPlan: declined, today's results;
   * the launches of a 3 x 32 step: the two new entries once each, the four readout / loss entries they replace not at all, one
@@ -102,6 +104,25 @@ def test_two_steps_with_different_last_nodes_on_one_plan(monkeypatch):
             assert res[on][0] == on and _pools_all_zero(plans[on])
         _assert_same(res[True], res[False], "step %d" % k)
         assert sum(len(v) for v in plans[True]._dz_zero.values()) == sum(len(v) for v in plans[False]._dz_zero.values())
+
+
+def test_step_and_separate_calls_interleaved_on_one_plan_share_the_pool(monkeypatch):
+    """step(), the separate calls, step() again on ONE plan: both hand their gradient buffers to one pool through one loop
+    (SconePlan._cone_backward).  Four layers: the smallest stack with an inline release and a deferred clear."""
+    _need_gpu()
+    _thresholds(monkeypatch)
+    env, batch = _env(), _batch()
+    w = _weights(4, seed=23)
+    rs = np.random.RandomState(23)
+    other = torch.as_tensor(rs.randint(0, env["plan"]().n_nodes, size=batch[1].numel()).astype(np.int32), device="cuda")
+    plan, n_first = env["plan"](fresh=True), None
+    for k, (on, last) in enumerate(((True, batch[1]), (False, other), (True, batch[1]))):
+        res = _micro(plan, w, on, monkeypatch, batch, last_dev=last)
+        assert res[0] == on and _pools_all_zero(plan)
+        n = sum(len(v) for v in plan._dz_zero.values())
+        n_first = n if n_first is None else n_first
+        assert n == n_first > 0, "micro-batch %d left %d pooled buffers, the first %d" % (k, n, n_first)
+        _assert_same(res, _micro(env["plan"](fresh=True), w, on, monkeypatch, batch, last_dev=last), "micro-batch %d against a fresh plan" % k)
 
 
 def test_the_trainers_loop_over_two_micro_batches_into_a_garbage_gradient_buffer(monkeypatch):

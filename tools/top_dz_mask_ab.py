@@ -58,7 +58,7 @@ print("items in M0 %.3f %% of (block, slab), in the hopped mask %.3f %%" % (shar
 # the readout gradient of these last nodes, into an all-zero buffer (SconePlan._readout_grad: the pooled path)
 H = torch.tanh(torch.randn(S, E, 4, C, device=dev))
 logp, bh = plan.readout(H, w_last, last)[:2]
-dz, _ = plan._readout_grad(H, bh, logp, torch.randn_like(logp), last, [w_last], [torch.zeros_like(w_last)])
+dz = plan._readout_grad(H, bh, logp, torch.randn_like(logp), last, [w_last], [torch.zeros_like(w_last)])
 del H
 torch.cuda.synchronize()
 print("dz: %.4f %% of the values are non-zero" % (100.0 * float((dz != 0).float().mean())), flush=True)
