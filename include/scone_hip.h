@@ -1027,7 +1027,22 @@ int scn_walk_assemble(int32_t n, const int32_t* path, const int32_t* path_len, i
  *                    inside its logsumexp, TE:288), as m + logf(sum_j expf(logp_j - m)) with m the first slot of that order, one fp32
  *                    subtract per slot and an fp32 running sum in slot order; m itself when it is a NaN or +-inf.
  *   An item with j* < 0 (the prefix ends its path, or a bad step), or guarded against as above, gets NaN / -1 / NaN.  One thread per
- *   item.  SCN_ERR_UNSUPPORTED when n_items * d reaches 2^31 - 1. */
+ *   item.  SCN_ERR_UNSUPPORTED when n_items * d reaches 2^31 - 1.
+ * scn_path_stage: one micro-batch of a training step on whole paths (Scone_GCN.path_grad_step): the items of scn_path_slabs staged
+ *   into the three tensors a step reads, in buffers the caller keeps from step to step.  The conventions of the three calls above.
+ *   x [n_slabs][n_rows][4][1] ends up bitwise what scn_path_slabs leaves for the same items.  n_prev < 0: the buffer holds anything and
+ *   gets the dense zero fill first.  n_prev >= 0 (n_prev <= 4 n_slabs): the buffer holds exactly what an earlier call for the n_prev
+ *   items prev_item_path / prev_item_len left, zero elsewhere; only the words those items wrote (the same predicate: row[t] >= 0,
+ *   next_same[t] >= end) are reset to +0, at the cost of the prefixes' lengths, never of n_slabs * n_rows.  The reset is ordered before
+ *   the writes by SEPARATE LAUNCHES on `stream`: the fill or the reset (one wave per previous item), then one wave per column
+ *   i < 4 n_slabs.  No two waves of a launch touch one word; no atomics.
+ *   last_nodes [4 n_slabs]: path_nodes[path_ptr[p] + k - 1] for a valid item; 0 for padding (i >= n_items) and guarded items.
+ *   y [4 n_slabs][d]: every row written whole.  A valid item's row holds item_weight[i] (1 when item_weight is NULL) at slot[t],
+ *   t = path_ptr[p] + k - 1, where 0 <= slot[t] < d, and zero elsewhere; rows of padding, of guarded items and of an item whose prefix
+ *   ends its path (k == length: slot[t] = -1) are zero.
+ *   Before any launch: SCN_ERR_BAD_SHAPE for a negative count, n_rows < 1, d < 1, n_items > 4 n_slabs or n_prev > 4 n_slabs;
+ *   SCN_ERR_UNSUPPORTED for ns != 4; SCN_ERR_BAD_ARG for a null or misaligned x and for any other null array the call would read or
+ *   write.  n_slabs == 0 launches nothing; n_items == 0 with n_slabs > 0 still resets, and writes zero last nodes and target rows. */
 int scn_path_steps(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t n_nodes, int32_t d, const int32_t* deg,
                    const int32_t* step_node, const int32_t* step_edge, const float* step_sign, int32_t n_rows, int32_t* slot,
                    int32_t* row, float* run, int32_t* next_same, int32_t* err, void* stream);
@@ -1037,6 +1052,10 @@ int scn_path_slabs(int32_t n_items, int32_t n_slabs, const int32_t* item_path, c
 int scn_path_score(int32_t n_items, int32_t d, const int32_t* item_path, const int32_t* item_len, int32_t n_paths,
                    const int32_t* path_ptr, const int32_t* path_nodes, const int32_t* slot, const int32_t* deg, int32_t n_nodes,
                    const float* logp, float* step_logp, int32_t* step_rank, float* step_mass, void* stream);
+int scn_path_stage(int32_t n_items, int32_t n_slabs, const int32_t* item_path, const int32_t* item_len, const float* item_weight,
+                   int32_t n_prev, const int32_t* prev_item_path, const int32_t* prev_item_len, int32_t n_paths, const int32_t* path_ptr,
+                   const int32_t* path_nodes, const int32_t* slot, const int32_t* row, const float* run, const int32_t* next_same,
+                   int32_t n_rows, int32_t ns, int32_t d, float* x, int32_t* last_nodes, float* y, void* stream);
 
 #ifdef __cplusplus
 }

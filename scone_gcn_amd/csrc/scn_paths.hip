@@ -3,6 +3,11 @@
 // turns every step into (slot, device row, value of that edge's flow after the step, next step on the same edge) once per call;
 // scn_path_slabs writes the flow of any prefix from those records with one writer per word; scn_path_score reads the forward's
 // output at the slot actually taken.  No float atomics anywhere: the same inputs give the same bytes.
+// Training on whole paths (Scone_GCN.path_grad_step) stages its micro-batches with scn_path_stage: the flows of scn_path_slabs plus
+// the items' last nodes and weighted one-hot target rows, into buffers that are kept from step to step.  The dense zero fill of x was
+// 34.8 % of the scoring call's kernel time at |E| ~ 1M (profiles/path_scores.txt), so a restage clears only the words the buffer's
+// previous items wrote.  The reset is ordered before the writes by SEPARATE LAUNCHES on the one stream (reset, then stage), not by a
+// fence inside one wave.
 #include "scn_internal.h"
 
 #include <climits>
@@ -139,6 +144,48 @@ __global__ __launch_bounds__(WAVE) void path_scatter_kernel(const int32_t* __res
     }
 }
 
+// scn_path_stage, launch 1 of the sparse form: one wave per item the buffer held.  The words path_scatter_kernel wrote for that item
+// in column i -- the same predicate -- go back to +0; nothing else is touched, so the cost is the prefixes' lengths, not the buffer's.
+__global__ __launch_bounds__(WAVE) void path_reset_kernel(const int32_t* __restrict__ item_path, const int32_t* __restrict__ item_len,
+                                                          int n_paths, const int32_t* __restrict__ ptr, const int32_t* __restrict__ row,
+                                                          const int32_t* __restrict__ next_same, int n_rows, float* __restrict__ x) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    int t0, k;
+    if (!item_prefix(i, item_path, item_len, n_paths, ptr, t0, k)) return;
+    const int end = t0 + k - 1;
+    for (int t = t0 + lane; t < end; t += WAVE) {
+        const int r = row[t];
+        if (r >= 0 && r < n_rows && next_same[t] >= end) x[((size_t)(i >> 2) * n_rows + r) * 4 + (i & 3)] = 0.f;
+    }
+}
+
+// scn_path_stage, the last launch: one wave per column i < 4 n_slabs.  A valid item scatters its prefix's flow as path_scatter_kernel
+// does, and every column writes its last node and its whole target row (zero but for the weight at the slot the path takes next).
+__global__ __launch_bounds__(WAVE) void path_stage_kernel(int n_items, const int32_t* __restrict__ item_path,
+                                                          const int32_t* __restrict__ item_len, const float* __restrict__ item_weight,
+                                                          int n_paths, const int32_t* __restrict__ ptr, const int32_t* __restrict__ nodes,
+                                                          const int32_t* __restrict__ slot, const int32_t* __restrict__ row,
+                                                          const float* __restrict__ run, const int32_t* __restrict__ next_same,
+                                                          int n_rows, int d, float* __restrict__ x, int32_t* __restrict__ last_nodes,
+                                                          float* __restrict__ y) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    int t0 = 0, k = 0;
+    const bool valid = i < n_items && item_prefix(i, item_path, item_len, n_paths, ptr, t0, k);
+    const int end = t0 + k - 1;                                      // the prefix's last node: its steps are t0 .. end - 1
+    int js = -1;
+    float w = 0.f;
+    if (valid) {
+        for (int t = t0 + lane; t < end; t += WAVE) {
+            const int r = row[t];
+            if (r >= 0 && r < n_rows && next_same[t] >= end) x[((size_t)(i >> 2) * n_rows + r) * 4 + (i & 3)] = run[t];
+        }
+        js = slot[end];                                              // -1 where the prefix ends its path
+        w = item_weight ? item_weight[i] : 1.f;
+    }
+    if (lane == 0) last_nodes[i] = valid ? nodes[end] : 0;
+    for (int j = lane; j < d; j += WAVE) y[(size_t)i * d + j] = j == js ? w : 0.f;
+}
+
 // slot j comes before slot b in the order of scn_beam_step / scn_hop_select: a NaN before every number, then the higher value, then
 // the lower slot
 __device__ __forceinline__ bool comes_before(float a, int j, float b, int jb) {
@@ -223,6 +270,34 @@ int scn_path_slabs(int32_t n_items, int32_t n_slabs, const int32_t* item_path, c
     if (status != SCN_OK) return status;
     return scn::launch_checked(path_scatter_kernel, dim3((unsigned)n_items), dim3(WAVE), 0, st, item_path, item_len, n_paths, path_ptr,
                                row, run, next_same, n_rows, x);
+}
+
+int scn_path_stage(int32_t n_items, int32_t n_slabs, const int32_t* item_path, const int32_t* item_len, const float* item_weight,
+                   int32_t n_prev, const int32_t* prev_item_path, const int32_t* prev_item_len, int32_t n_paths, const int32_t* path_ptr,
+                   const int32_t* path_nodes, const int32_t* slot, const int32_t* row, const float* run, const int32_t* next_same,
+                   int32_t n_rows, int32_t ns, int32_t d, float* x, int32_t* last_nodes, float* y, void* stream) {
+    if (n_items < 0 || n_slabs < 0 || n_paths < 0 || n_rows <= 0 || d < 1) return SCN_ERR_BAD_SHAPE;
+    if (ns != 4) return SCN_ERR_UNSUPPORTED;
+    if ((int64_t)n_items > (int64_t)n_slabs * ns || (int64_t)n_prev > (int64_t)n_slabs * ns) return SCN_ERR_BAD_SHAPE;
+    if ((int64_t)n_slabs * ns >= INT_MAX) return SCN_ERR_UNSUPPORTED;      // a column is an int and a grid index
+    if (n_slabs == 0) return SCN_OK;
+    if (!x || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || !last_nodes || !y) return SCN_ERR_BAD_ARG;
+    if (n_items > 0 && (!item_path || !item_len || !path_nodes || !slot || !run)) return SCN_ERR_BAD_ARG;
+    if (n_prev > 0 && (!prev_item_path || !prev_item_len)) return SCN_ERR_BAD_ARG;
+    if ((n_items > 0 || n_prev > 0) && (!path_ptr || !row || !next_same)) return SCN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int status = SCN_OK;
+    if (n_prev < 0) {
+        const int64_t words = (int64_t)n_slabs * n_rows;
+        const int64_t blocks = (words + 255) / 256;
+        status = scn::launch_checked(path_zero_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, words, x);
+    } else if (n_prev > 0) {
+        status = scn::launch_checked(path_reset_kernel, dim3((unsigned)n_prev), dim3(WAVE), 0, st, prev_item_path, prev_item_len, n_paths,
+                                     path_ptr, row, next_same, n_rows, x);
+    }
+    if (status != SCN_OK) return status;
+    return scn::launch_checked(path_stage_kernel, dim3((unsigned)(n_slabs * ns)), dim3(WAVE), 0, st, n_items, item_path, item_len,
+                               item_weight, n_paths, path_ptr, path_nodes, slot, row, run, next_same, n_rows, d, x, last_nodes, y);
 }
 
 int scn_path_score(int32_t n_items, int32_t d, const int32_t* item_path, const int32_t* item_len, int32_t n_paths,

@@ -96,6 +96,8 @@ VISIT_RECORDS = True   # a unit's top reads the block's packed 32-byte record.  
 # ... and one the trainer's micro-batch loop reads (SconePlan.step):
 STEP_TAIL = True       # a cone step's readout chain is one launch, and its loss sum, dW reduces and clears one more.  False: nine launches
 STEP_MASKS = True      # the cone masks of all of a step's micro-batches come from one launch ahead of the first.  False: five launches each
+# ... and one the path trainer's staging reads (path_train.py):
+PATH_STAGE_SPARSE_CLEAR = True  # a restaged micro-batch buffer resets only the words its previous items wrote.  False: the dense zero fill
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
 # Small complexes: the whole gradient step of a micro-batch in one launch (SconePlan.small_step, csrc/scn_small.hip), one workgroup per
 # trajectory.  SCN_SMALL_STEP=0 turns it off, =force lifts the rule of small_step_pays() below.  Measured per graph-replayed optimiser

@@ -43,8 +43,16 @@ def path_items(path_ptr, min_prefix):
     return item_ptr, item_path, item_len
 
 
-def step_log_probs(net, inputs, paths, min_prefix=2, normalise=False):
-    """Scone_GCN.path_step_log_probs."""
+PathSteps = namedtuple("PathSteps", "plan tab n_paths path_ptr nodes ptr_d nodes_d slot row run next_same")
+PathSteps.__doc__ = """Paths resident on the device with their scn_path_steps records: the plan and step tables they were looked up in,
+path_ptr [P + 1] / nodes [T] int64 on the host, ptr_d / nodes_d int32 on the device, and slot / row / run / next_same [T] parallel to
+nodes_d (None, like ptr_d and nodes_d, when the paths hold no node at all)."""
+
+
+def device_steps(net, inputs, paths):
+    """The paths of a scoring call or a path set (path_train.py) on the device, every step looked up by scn_path_steps: PathSteps.
+    Refuses a probed closure (TypeError) and a step between two nodes that are no neighbours (KeyError((a, b)), after the one look
+    at the error word and before any forward)."""
     if net.model_type != 'bunch' and not isinstance(inputs[0], Bconds):
         raise TypeError("multi-hop prediction needs the Bconds object of SimplicialComplex.bconds() (what data_setup returns) as "
                         "the readout operand: a plain Bcond_func closure only knows the last nodes it has been probed at")
@@ -53,16 +61,13 @@ def step_log_probs(net, inputs, paths, min_prefix=2, normalise=False):
         raise TypeError("path scoring runs the native model functions (scone_func / ebli_func / bunch_func) only")
     nbrhoods = inputs[0] if net.model_type == 'bunch' else inputs[0].nbrhoods
     tab = multihop.step_tables(plan, nbrhoods, net._edge_lookup(inputs), "flow")
-    lib, dev, D, E, weights = _lib.load(), plan.device, plan.max_deg, plan.n_edges, net.weights
+    lib, dev, D, E = _lib.load(), plan.device, plan.max_deg, plan.n_edges
     path_ptr, nodes = ragged(paths)
     P, T = len(path_ptr) - 1, int(path_ptr[-1])
     if T >= INT32_MAX:
         raise ValueError("paths of %d nodes in all are too many" % T)
-    item_ptr, item_path, item_len = path_items(path_ptr, min_prefix)
-    M = int(item_ptr[-1])
-    empty = PathScores(item_ptr, np.zeros(0), np.zeros(0, np.int64), np.zeros(0), np.zeros(0, np.int64))
     if T == 0:
-        return empty
+        return PathSteps(plan, tab, P, path_ptr, nodes, None, None, None, None, None, None)
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
     p = lambda t: ops._dev(t, t.dtype)
     ptr_d, nodes_d = i32(path_ptr), i32(np.clip(nodes, -1, INT32_MAX))
@@ -74,8 +79,20 @@ def step_log_probs(net, inputs, paths, min_prefix=2, normalise=False):
     t = int(err.item())                                              # the one look before the forwards: a bad pair costs none
     if t != INT32_MAX:
         raise KeyError((int(nodes[t]), int(nodes[t + 1])))
-    if M == 0:
-        return empty
+    return PathSteps(plan, tab, P, path_ptr, nodes, ptr_d, nodes_d, slot, row, run, next_same)
+
+
+def step_log_probs(net, inputs, paths, min_prefix=2, normalise=False):
+    """Scone_GCN.path_step_log_probs."""
+    st = device_steps(net, inputs, paths)
+    plan, tab, P, path_ptr, nodes, ptr_d, nodes_d, slot, row, run, next_same = st
+    lib, dev, D, E, weights = _lib.load(), plan.device, plan.max_deg, plan.n_edges, net.weights
+    item_ptr, item_path, item_len = path_items(path_ptr, min_prefix)
+    M = int(item_ptr[-1])
+    if M == 0:                                                       # (paths without a node have no item either)
+        return PathScores(item_ptr, np.zeros(0), np.zeros(0, np.int64), np.zeros(0), np.zeros(0, np.int64))
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+    p = lambda t: ops._dev(t, t.dtype)
     ip_d, il_d = i32(item_path), i32(item_len)
     item_last = i32(nodes[path_ptr[item_path] + item_len - 1])
     out_logp, out_mass = (torch.empty((M,), device=dev, dtype=torch.float32) for _ in range(2))

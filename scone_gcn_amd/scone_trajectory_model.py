@@ -18,7 +18,7 @@ import gc
 import numpy as np
 import torch
 
-from . import _lib, multihop, ops, path_scores
+from . import _lib, multihop, ops, path_scores, path_train
 from . import distributed as dp
 from .synthetic_data_gen import SparseFlows
 from .trajectory_experiments import MODEL_ACT, MODEL_FUNCS, resolve_operands
@@ -224,6 +224,7 @@ class Scone_GCN():
         self.shifts = shifts
         self.model = model
         self.model_single = model
+        self.drop_path_stage()                          # (another model or other operators: another plan)
         X = inputs[-1]
         in_channels = 1 if isinstance(X, SparseFlows) else int(X.shape[-1])
         out_channels = int(np.asarray(y).shape[-1])
@@ -475,6 +476,40 @@ class Scone_GCN():
         "accuracy" = the share of steps with rank 0, "n_steps"}; NaN where there is no step."""
         return path_scores.score_paths(self, inputs, paths, mask, min_prefix, normalise)
 
+    # ------------------------------------------------------------------ training on whole paths: path_train.py
+    path_micro_batch = None            # items per micro-batch of path_grad_step (default: the rule of stage(); the tests' override)
+    _path_pool = None                  # the micro-batch buffers path_grad_step keeps from step to step (path_train.StagePool)
+
+    def path_set(self, inputs, paths):
+        """The node paths resident on the device with their scn_path_steps records (path_train.PathSet): what path_grad_step trains
+        on, uploaded once per training run.  Of `inputs` only the readout operand is used.  Raises like path_step_log_probs:
+        KeyError((a, b)) for a step between two nodes that are no neighbours, TypeError for a plain Bcond_func closure."""
+        return path_train.PathSet(self, inputs, paths)
+
+    def path_loss(self, inputs, paths, mask=None, min_prefix=2, weight="step"):
+        """The teacher-forced sequence loss path_grad_step descends, as a Python float:  -sum_i w_i logp_i / sum_i w_i  over the
+        items of the paths of mask (all when None) + weight_decay * ridge, from path_step_log_probs.  weight "step": w_i = 1 (the
+        negative of score_paths' mean_step_logp); "path": w_i = fp32(1 / items of i's path), every path counts the same.  NaN
+        without an item."""
+        return path_train.path_loss(self, inputs, paths, mask, min_prefix, weight)
+
+    def path_grad_step(self, inputs, path_set, items, apply=True, min_prefix=2, weight="step"):
+        """grad_step on items of a path set: `items` index path_set.items(min_prefix); one optimiser step on
+        -sum_i w_i logp_i / sum_i w_i over them (+ the ridge term inside Adam).  The local shard of the items is cut into
+        micro-batches by the rule of stage(), each staged on the device by scn_path_stage into buffers kept from step to step
+        (another path set, setup() or drop_path_stage() frees them; train_paths does when it returns), and the micro-batches go through _accumulate_staged on whatever route the plan serves.
+        Returns this rank's share of the data term as a 0-dim device tensor.  Dense skip mode only; never graph-captured."""
+        return path_train.grad_step(self, inputs, path_set, items, apply, min_prefix, weight)
+
+    def drop_path_stage(self):
+        """Free the micro-batch buffers path_grad_step keeps."""
+        self._path_pool = None
+
+    def train_paths(self, inputs, paths, train_mask, test_mask, min_prefix=2, weight="step"):
+        """train() on whole paths: every (path, prefix) item of the paths of train_mask is a training example.  Returns
+        (train_scores, test_scores), the score_paths dicts after the last epoch.  See path_train.train_paths."""
+        return path_train.train_paths(self, inputs, paths, train_mask, test_mask, min_prefix, weight)
+
     # ------------------------------------------------------------------ gradient step (STM:306-310)
     def stage(self, inputs, y, idx, skip=None):
         """Move trajectories idx to the device as micro-batches of flow slabs: list of (x, last_nodes, y, activity) with
@@ -483,15 +518,7 @@ class Scone_GCN():
         skip = self.skip_mode if skip is None else skip
         plan = self._plan(inputs)
         device = self._flat_w.device
-        widths = plan.layer_widths(self._shapes)        # (hidden widths the kernels do not take count zero-padded, ops.promote_weights)
-        budget = None
-        if self.model_type == 'bunch' and ops.FOLD_BUNCH and len(widths) > 3 and widths[1] == widths[2] == 32:
-            # the first hidden layer is never materialised (rank-one fold, DESIGN.md section 3.1 / profiles/HISTORY.md section 3.1) and levels the loss cannot see are not
-            # computed: measured 0.93 GB per trajectory at |E| = 1M where the generic estimate says 1.3 -- 128 trajectories per launch
-            # (119 GB at peak) instead of 64, +3.4 % on configs[4] (tools/mb_sweep.py)
-            widths = [widths[0]] + widths[2:]
-            budget = 0.5 * torch.cuda.mem_get_info(device)[1]
-        mb = ops.micro_batch_size(plan.n_rows, widths, len(idx), budget_bytes=budget, device=device)
+        mb = self._stage_micro_batch(plan, len(idx))
         staged = []
         for c0 in range(0, len(idx), mb):
             sel = idx[c0:c0 + mb]
@@ -506,6 +533,19 @@ class Scone_GCN():
                 activity = plan.activity(inputs[2], inputs[1], len(self._shapes) // 3, self._shapes[0][1], skip, sel=sel)
             staged.append((x, last_dev, yt, activity))
         return staged
+
+    def _stage_micro_batch(self, plan, n):
+        """Trajectories per micro-batch of a batch of n: the rule of stage(), which path_grad_step cuts its items by as well."""
+        device = self._flat_w.device
+        widths = plan.layer_widths(self._shapes)        # (hidden widths the kernels do not take count zero-padded, ops.promote_weights)
+        budget = None
+        if self.model_type == 'bunch' and ops.FOLD_BUNCH and len(widths) > 3 and widths[1] == widths[2] == 32:
+            # the first hidden layer is never materialised (rank-one fold, DESIGN.md section 3.1 / profiles/HISTORY.md section 3.1) and levels the loss cannot see are not
+            # computed: measured 0.93 GB per trajectory at |E| = 1M where the generic estimate says 1.3 -- 128 trajectories per launch
+            # (119 GB at peak) instead of 64, +3.4 % on configs[4] (tools/mb_sweep.py)
+            widths = [widths[0]] + widths[2:]
+            budget = 0.5 * torch.cuda.mem_get_info(device)[1]
+        return ops.micro_batch_size(plan.n_rows, widths, n, budget_bytes=budget, device=device)
 
     def _accumulate_staged(self, plan, staged, total, fresh=False, adam=False):
         """flat_g += d/dW of  -sum_n <logp_n, y_n> / total over the staged micro-batches (fresh: flat_g = ..., i.e. zeroed first).

@@ -38,6 +38,9 @@ def hyperparams(args=None):
           'markov_order': 1,             # not in the reference (order = 1 is hard-coded, TE:329): the order K of the -markov 1 baseline
           'projection': 0,               # 1: the harmonic projection baseline's experiments first (the reference's projection_model.py)
           'path_likelihood': 0,          # not in the reference: 1 = after training, the teacher-forced scores of prefix + [target] (score_paths)
+          'train_paths': 0,              # not in the reference: 1 = train on every (path, prefix) item of prefix + [target] (train_paths)
+          'path_min_prefix': 2,          # ... the shortest prefix that is an item
+          'path_weight': 'step',         # ... step | path: every item counts the same, or every path does
           'n_points': 400, 'n_walks': 1000,   # not in the reference (hard-coded, TE:224): the size of the -load_data 0 data set
           'walks': 'host',               # host | device: device = generate_random_walks_batched (fresh waypoints per walk on the GPU)
           'walk_metric': 'hops'}         # hops | euclid: the shortest-path metric of the generated walks
@@ -48,7 +51,7 @@ def hyperparams(args=None):
                 nums = list(map(int, args[i + 1].split("_")))
                 hp['hidden_layers'] = [(nums[j], nums[j + 1]) for j in range(0, len(nums), 2)]
             elif name in ['model_name', 'data_folder_suffix', 'multi_graph', 'model', 'skip_mode', 'multi_hop_skip', 'walks',
-                          'walk_metric']:
+                          'walk_metric', 'path_weight']:
                 hp[name] = str(args[i + 1])
             else:
                 try:
@@ -323,7 +326,9 @@ def train_model(hp=None):
     train the model.  With -projection 1 the harmonic projection baseline runs next (projection_experiments) and its results go to
     experiment_results["projection"]; training follows as well.  With -path_likelihood 1 the trained model scores every path
     prefixes[i] + [target_nodes_all[0][i]] step by step (Scone_GCN.score_paths) over the train and the test mask:
-    experiment_results["path_likelihood"] = {"train": ..., "test": ...}."""
+    experiment_results["path_likelihood"] = {"train": ..., "test": ...}.  With -train_paths 1 (-path_min_prefix, -path_weight) the
+    model is trained on every (path, prefix) item of those same paths (Scone_GCN.train_paths) in place of train(); the losses and
+    accuracies returned are then test()'s on the two masks, and everything after training runs as before."""
     from .scone_trajectory_model import Scone_GCN
     hp = hyperparams() if hp is None else hp
     inputs_all, y_all, train_mask, test_mask, shifts, G_undir, E_lookup, nbrhoods, n_nbrs, target_nodes_all, prefixes = \
@@ -355,15 +360,24 @@ def train_model(hp=None):
         print('Model: {}'.format(hp['model']))
     os.makedirs('models', exist_ok=True)
     path = os.path.join('models', hp['model_name'] + '.npz')
+    train_paths = hp.get('train_paths', 0) == 1                            # not in the reference: every prefix of a path is an example
+
+    def fit():
+        if not train_paths:
+            return scone.train(inputs_1hop, y_1hop, train_mask, test_mask, n_nbrs)
+        whole = [[int(v) for v in pre] + [int(t)] for pre, t in zip(prefixes, target_nodes_all[0])]
+        scone.train_paths(inputs_1hop, whole, train_mask, test_mask, min_prefix=int(hp.get('path_min_prefix', 2)),
+                          weight=hp.get('path_weight', 'step'))
+        return scone.test(inputs_1hop, y_1hop, train_mask, n_nbrs) + scone.test(inputs_1hop, y_1hop, test_mask, n_nbrs)
     if hp['load_model']:                                                   # TE:464-476
         scone.load_weights(path)
         if hp['epochs'] != 0:
-            scone.train(inputs_1hop, y_1hop, train_mask, test_mask, n_nbrs)
+            fit()
             scone.save_weights(path)
         (train_loss, train_acc), (test_loss, test_acc) = scone.test(inputs_1hop, y_1hop, train_mask, n_nbrs), \
             scone.test(inputs_1hop, y_1hop, test_mask, n_nbrs)
     else:
-        train_loss, train_acc, test_loss, test_acc = scone.train(inputs_1hop, y_1hop, train_mask, test_mask, n_nbrs)
+        train_loss, train_acc, test_loss, test_acc = fit()
         scone.save_weights(path)                                           # TE:482-486
     print('standard test set:')                                            # TE:489-494
     train_2target, test_2target = scone.two_target_accuracy(shifts, inputs_1hop, y_1hop, train_mask, n_nbrs), \
