@@ -883,7 +883,20 @@ int scn_tree_slabs_list(scn_conv_t conv, int32_t n_leaves, int32_t n_slabs, int3
  *   row, a short or offending prefix and a last node with a single neighbour (np.random.choice([]) raises in MM:104) get score 0
  *   and other -1.
  * scn_markov_probs: probs[i][j] (fp64, [n][d]) = (double)counts[s][j] / (double)(sum of the row) -- the bits Python's division
- *   gives -- and 0 where the row is empty, j >= deg[v] or the prefix is short or offending. */
+ *   gives -- and 0 where the row is empty, j >= deg[v] or the prefix is short or offending.
+ * scn_markov_path_scores: the teacher-forced score of every node of every path, one record per node position in arrays parallel to
+ *   path_nodes: prob (fp64), rank, total [T].  The record at t = path_ptr[p] + q describes the prediction of u = nodes[t] from the q
+ *   nodes before it, v = nodes[t - 1] the last of them, j = slot(v, u).  The row is counts[state(nodes[t - order .. t - 1])] for
+ *   q >= order and the all-zero row for a shorter prefix (scn_markov_probs' rule); c_j' its entries for j' < deg[v]; total = their
+ *   sum; prob = ((double)c_j + alpha) / ((double)total + alpha * (double)deg[v]), every operation rounded on its own, where that
+ *   denominator is positive and 0 otherwise -- alpha = 0: the bits of scn_markov_probs at slot j; alpha > 0: additive smoothing over
+ *   the real neighbours, 1 / deg[v] for an unseen or short state; rank = the number of j' < deg[v] with c_j' > c_j, or c_j' == c_j
+ *   and j' < j (scn_path_score's order: rank 0 is the first maximum).  The record's window is the pairs (nodes[r], nodes[r + 1]) for
+ *   r = max(t - order, path_ptr[p]) .. t - 1; a pair of one path that is no edge or has an id outside the graph lowers err to its r,
+ *   and every record whose window holds such a pair, like every record at q = 0 (which predicts nothing), is prob 0, rank -1, total
+ *   0.  alpha negative or NaN is SCN_ERR_BAD_ARG.  One wave per path, 64 positions a pass; the lanes walk their rows themselves, so
+ *   a neighbourhood may be wider than a wave.  The library cannot read path_ptr: paths that hold no node at all (T == 0) are the
+ *   call with path_nodes, prob, rank and total all NULL, which returns SCN_OK without a launch, as n_paths == 0 does. */
 #define SCN_MARKOV_MAX_ORDER 4
 int scn_markov_table_rows(int32_t n_nodes, int32_t d, int32_t order);
 int scn_markov_count(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t order, int32_t n_nodes, int32_t d,
@@ -896,6 +909,9 @@ int scn_markov_two_target(int32_t n, const int32_t* prefix_ptr, const int32_t* p
                           const int32_t* counts, float* score, int32_t* other, int32_t* err, int32_t* err_target, void* stream);
 int scn_markov_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t order, int32_t n_nodes, int32_t d,
                      const int32_t* nbr, const int32_t* deg, const int32_t* counts, double* probs, int32_t* err, void* stream);
+int scn_markov_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t order, double alpha,
+                           int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, const int32_t* counts, double* prob,
+                           int32_t* rank, int32_t* total, int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * The harmonic projection baseline (projection_model.py, PM:58-126), everything in fp64.  The pieces of a conjugate-gradient solve of
@@ -929,7 +945,21 @@ int scn_markov_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix
  *   edge id lies outside the complex or whose tables disagree; such an entry adds nothing.
  * scn_project_two_target: PM:110-126 on probs [n][d]: t = target[i] (a slot), the other slot is o + (o >= t) with o = (u24 *
  *   (n_nbrs[i] - 1)) >> 24 from the uniform of (seed, i, 1, 0); score[i] = 1, 0.5 or 0, other[i] = that slot.  n_nbrs[i] < 2 (PM:119
- *   raises there) or a target outside [0, d) lowers err to i: score 0, other -1. */
+ *   raises there) or a target outside [0, d) lowers err to i: score 0, other -1.
+ * scn_project_path_scores: the teacher-forced score of every node of every path (path_ptr[n_paths + 1] / path_nodes[T], int32) on the
+ *   tables of scn_project_predict, one record per node position in arrays parallel to path_nodes: logp, mass (fp64), rank [T] and,
+ *   unless NULL, coef [T][k].  Step i of a path goes from a = nodes[ptr + i - 1] to b = nodes[ptr + i] over the edge e_i in a's
+ *   incidence row whose other endpoint is b, with the sign B1[b, e_i] = -inc_sign of e_i at a; none found (or an id outside the
+ *   complex) lowers err (INT32_MAX at the start) to the flat position of a.  The record at t = path_ptr[p] + q, q >= 1, predicts
+ *   nodes[t] from the q nodes before it: c_t = sum_{i=1}^{q-1} sign_i V[e_i, :], every column added in step order starting from +0 (a
+ *   repeated edge counts twice, a backtrack cancels; no flow is built), coef[t][:] = c_t; the logits are scn_project_predict's at
+ *   last = nodes[t - 1] with c = c_t, the slots without an edge at 0 and inside the soft-max over all d; logp = the logit at the slot
+ *   of nodes[t] minus the logsumexp over the d slots; rank = the real neighbours before it by (higher logit, lower slot); mass = log
+ *   of the soft-max's sum over the real neighbours.  k = 0 and q = 1 are c = 0: logp = -log d, rank = the slot taken.  The record at
+ *   q = 0, and every record from a step on that was not found, is logp 0, rank -1, mass 0, coef 0.  One wave per path, 64 positions
+ *   a pass, the running sums carried from pass to pass in the lanes c < k.  The incidence rows and the neighbour table must agree
+ *   (scn_project_predict checks that; here d minus the edges at the node is the number of zero slots).  Paths that hold no node at
+ *   all (T == 0) are the call with path_nodes, logp, rank and mass all NULL: SCN_OK without a launch, as for n_paths == 0. */
 #define SCN_PROJECT_MAX_K 32
 #define SCN_PROJECT_MAX_PARTS 1024
 #define SCN_CG_STATE_DOUBLES (3 * SCN_PROJECT_MAX_K)
@@ -949,6 +979,10 @@ int scn_project_predict(int32_t n, int32_t k, int32_t n_edges, const double* v, 
                         const double* flow_val, const int32_t* last, int32_t n_nodes, const int32_t* inc_ptr, const int32_t* inc_edge,
                         const float* inc_sign, const int32_t* edge_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, double* logits,
                         double* probs, int32_t* argmax, int32_t* err, void* stream);
+int scn_project_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t k, int32_t n_edges,
+                            const double* v, int32_t n_nodes, const int32_t* inc_ptr, const int32_t* inc_edge, const float* inc_sign,
+                            const int32_t* edge_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, double* logp, int32_t* rank,
+                            double* mass, double* coef /* [T][k], may be NULL */, int32_t* err, void* stream);
 int scn_project_two_target(int32_t n, int32_t d, uint64_t seed, const double* probs, const int32_t* target, const int32_t* n_nbrs,
                            float* score, int32_t* other, int32_t* err, void* stream);
 

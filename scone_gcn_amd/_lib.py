@@ -238,6 +238,8 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_markov_probs": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "scn_markov_path_scores": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, ctypes.c_double, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_project_parts": (ctypes.c_int, [c_i64, c_i32]),
     "scn_gram_parts": (ctypes.c_int, [c_i64]),
     "scn_csr_apply_f64": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -249,6 +251,9 @@ SIGNATURES = {
     "scn_project_predict": (ctypes.c_int, [c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "scn_project_path_scores": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
     "scn_project_two_target": (ctypes.c_int, [c_i32, c_i32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),
     "scn_sssp_slot_bytes": (c_size_t, [c_i32]),

@@ -225,6 +225,71 @@ __global__ __launch_bounds__(WAVE) void markov_probs_kernel(const int32_t* __res
         probs[(size_t)i * g.d + j] = (j < dv && sum > 0) ? (double)row[j] / (double)sum : 0.0;
 }
 
+// (c_j + alpha) / (total + alpha deg) with every operation rounded on its own: the compiler may not contract the product into the sum
+__device__ __forceinline__ double smoothed_weight(double cj, double alpha, double sum, double dv) {
+#pragma clang fp contract(off)
+    const double scaled = alpha * dv;
+    const double den = sum + scaled;
+    return den > 0.0 ? (cj + alpha) / den : 0.0;
+}
+
+// One wave per path, the walk of markov_count_kernel with a read where counting has an add.  A pass takes 64 node positions q0 ..
+// q0 + 63: the slots of the 63 + order pairs q0 - order .. q0 + 62 go to LDS once (s_slot[i] = pair q0 - order + i; -2 where the path
+// has no such pair), then lane l finishes the record of position q0 + l from order of them: its window is the pairs q - order .. q - 1
+// that exist, the last of them the step the record predicts.  The quotient is smoothed_weight's: the bits of the C expression
+// whatever alpha is.
+__global__ __launch_bounds__(WAVE) void markov_path_scores_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ nodes,
+                                                                  int order, double alpha, Graph g, const int32_t* __restrict__ counts,
+                                                                  double* __restrict__ prob, int32_t* __restrict__ rank,
+                                                                  int32_t* __restrict__ total, int32_t* err) {
+    __shared__ int s_slot[WAVE + SCN_MARKOV_MAX_ORDER];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int t0 = ptr[p], len = ptr[p + 1] - t0;
+    for (int q0 = 0; q0 < len; q0 += WAVE) {
+        for (int i = lane; i < WAVE - 1 + order; i += WAVE) {
+            const int r = q0 - order + i;                            // the pair (r, r + 1) of the path
+            int sl = -2;
+            if (r >= 0 && r + 1 < len) {
+                sl = g.slot(nodes[t0 + r], nodes[t0 + r + 1]);
+                if (sl < 0 && r + 1 >= q0) atomicMin(err, t0 + r);   // (the pairs before q0 were the previous pass's)
+            }
+            s_slot[i] = sl;
+        }
+        __syncthreads();
+        const int q = q0 + lane;
+        if (q < len) {
+            double pr = 0.0;
+            int rk = -1, tot = 0;
+            bool ok = q >= 1;
+            for (int m = 0; m < order; ++m) ok = ok && s_slot[lane + m] != -1;
+            if (ok) {
+                const int t = t0 + q, v = nodes[t - 1], j = s_slot[lane + order - 1], dv = g.live_deg(v);
+                long long sum = 0;
+                int cj = 0, before = j;                              // the all-zero row of a short prefix: every lower slot ties
+                if (q >= order) {
+                    size_t s = (size_t)(uint32_t)nodes[t - order];
+                    for (int m = 0; m + 1 < order; ++m) s = s * g.d + s_slot[lane + m];
+                    const int32_t* row = counts + s * g.d;
+                    cj = row[j];
+                    before = 0;
+                    for (int x = 0; x < dv; ++x) {
+                        const int c = row[x];
+                        sum += c;
+                        before += (c > cj || (c == cj && x < j)) ? 1 : 0;
+                    }
+                }
+                pr = smoothed_weight((double)cj, alpha, (double)sum, (double)dv);
+                rk = before;
+                tot = (int)sum;
+            }
+            prob[t0 + q] = pr;
+            rank[t0 + q] = rk;
+            total[t0 + q] = tot;
+        }
+        __syncthreads();
+    }
+}
+
 // the checks every entry point shares: shapes, then what is served, before anything is launched
 int check_table(int32_t n, int32_t n_nodes, int32_t d, int32_t order) {
     if (n < 0 || n_nodes <= 0 || d <= 0) return SCN_ERR_BAD_SHAPE;
@@ -291,6 +356,20 @@ int scn_markov_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix
     if (!prefix_ptr || !prefix_nodes || !nbr || !deg || !counts || !probs || !err) return SCN_ERR_BAD_ARG;
     return scn::launch_checked(markov_probs_kernel, dim3((unsigned)n), dim3(WAVE), 0, (hipStream_t)stream, prefix_ptr, prefix_nodes, order,
                                Graph{nbr, deg, n_nodes, d}, counts, probs, err);
+}
+
+int scn_markov_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t order, double alpha,
+                           int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, const int32_t* counts, double* prob,
+                           int32_t* rank, int32_t* total, int32_t* err, void* stream) {
+    const int st = check_table(n_paths, n_nodes, d, order);
+    if (st != SCN_OK) return st;
+    if (!(alpha >= 0.0)) return SCN_ERR_BAD_ARG;                     // negative or NaN
+    if (n_paths == 0) return SCN_OK;
+    if (!path_ptr || !nbr || !deg || !counts || !err) return SCN_ERR_BAD_ARG;
+    if (!path_nodes && !prob && !rank && !total) return SCN_OK;      // paths without a node: T == 0, nothing to write
+    if (!path_nodes || !prob || !rank || !total) return SCN_ERR_BAD_ARG;
+    return scn::launch_checked(markov_path_scores_kernel, dim3((unsigned)n_paths), dim3(WAVE), 0, (hipStream_t)stream, path_ptr,
+                               path_nodes, order, alpha, Graph{nbr, deg, n_nodes, d}, counts, prob, rank, total, err);
 }
 
 }  // extern "C"

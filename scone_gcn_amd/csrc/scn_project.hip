@@ -333,6 +333,118 @@ __global__ __launch_bounds__(THREADS) void project_two_target_kernel(int n, int 
     other[i] = ot;
 }
 
+// (V[e, :] . c) of one record: the columns in order, one fma each
+__device__ __forceinline__ double row_dot(const double* __restrict__ v, int k, int e, const double* c) {
+    double h = 0.0;
+    for (int m = 0; m < k; ++m) h = fma(v[(size_t)e * k + m], c[m], h);
+    return h;
+}
+
+// One wave per path.  A pass takes the 64 node positions q0 .. q0 + 63: lane l looks up the step into its position (edge and sign),
+// the steps' rows sign * V[e, :] go to LDS, lanes c < k turn column c into its running sum in step order -- s_c[l][:] becomes the
+// coefficients of the prefix BEFORE the step of position q0 + l, the carry stays in the lane for the next pass -- and lane l finishes
+// the record of its position from s_c[l][:]: two passes over the edges at the prefix's last node, the maximum first, then the sums
+// and the rank (a lower slot is a lower node id: the neighbour rows ascend).  Nothing of the size of a flow is built.
+__global__ __launch_bounds__(WAVE) void project_path_scores_kernel(int k, const double* __restrict__ v, const int32_t* __restrict__ ptr,
+                                                                  const int32_t* __restrict__ nodes, Readout g, double* __restrict__ logp,
+                                                                  int32_t* __restrict__ rank, double* __restrict__ mass,
+                                                                  double* __restrict__ coef, int32_t* err) {
+    __shared__ double s_c[WAVE * (KMAX + 1)];
+    __shared__ int s_edge[WAVE];
+    __shared__ double s_sign[WAVE];
+    __shared__ int s_blank[WAVE];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int t0 = ptr[p], len = ptr[p + 1] - t0;
+    const int ks = k | 1;                                            // odd row stride: the lanes' rows start on different banks
+    double carry = 0.0;                                              // lane c < k: column c of the steps before this pass, from +0
+    bool bad_before = false;                                         // an earlier pass met a step that is no edge
+    for (int q0 = 0; q0 < len; q0 += WAVE) {
+        const int q = q0 + lane, t = t0 + q;
+        const bool is_step = q >= 1 && q < len;
+        int e = -1, a = -1, b = -1;
+        double sign = 0.0;
+        if (is_step) {
+            a = nodes[t - 1];
+            b = nodes[t];
+            if (a >= 0 && a < g.n_nodes && b >= 0 && b < g.n_nodes)
+                for (int x = g.inc_ptr[a], x1 = g.inc_ptr[a + 1]; x < x1; ++x) {
+                    const int ex = g.inc_edge[x];
+                    if (ex < 0 || ex >= g.n_edges) continue;
+                    const int a0 = g.edge_nodes[2 * (size_t)ex], a1 = g.edge_nodes[2 * (size_t)ex + 1];
+                    if ((a0 == a ? a1 : a0) == b) {
+                        e = ex;
+                        sign = -(double)g.inc_sign[x];               // B1[b, e] = -B1[a, e]
+                        break;
+                    }
+                }
+            if (e < 0) atomicMin(err, t - 1);
+        }
+        const unsigned long long bad = __ballot(is_step && e < 0);
+        const bool blank = !is_step || bad_before || (bad & ((2ull << lane) - 1ull)) != 0;   // a bad step at or before this one
+        s_edge[lane] = e;
+        s_sign[lane] = sign;
+        s_blank[lane] = blank ? 1 : 0;
+        __syncthreads();
+        for (int i = lane; i < WAVE * k; i += WAVE) {
+            const int l = i / k, el = s_edge[l];
+            s_c[l * ks + i % k] = el >= 0 ? s_sign[l] * v[(size_t)el * k + i % k] : 0.0;
+        }
+        __syncthreads();
+        if (lane < k)
+            for (int l = 0; l < WAVE; ++l) {
+                const double step = s_c[l * ks + lane];
+                s_c[l * ks + lane] = carry;
+                carry += step;
+            }
+        __syncthreads();
+        if (coef) {
+            const int n_here = min(WAVE, len - q0);
+            for (int i = lane; i < n_here * k; i += WAVE)
+                coef[(size_t)(t0 + q0) * k + i] = s_blank[i / k] ? 0.0 : s_c[i / k * ks + i % k];
+        }
+        if (q < len) {
+            double lp = 0.0, ms = 0.0;
+            int rk = -1;
+            if (!blank) {
+                const double* c = s_c + lane * ks;
+                const double taken = sign * row_dot(v, k, e, c);
+                const int x0 = g.inc_ptr[a], x1 = g.inc_ptr[a + 1];
+                int n_real = 0;
+                double mx = -INFINITY;
+                for (int x = x0; x < x1; ++x) {
+                    const int ex = g.inc_edge[x];
+                    if (ex < 0 || ex >= g.n_edges) continue;
+                    mx = fmax(mx, -(double)g.inc_sign[x] * row_dot(v, k, ex, c));
+                    ++n_real;
+                }
+                const int n_pad = g.d - n_real;                      // the padding's logits are 0 and enter the soft-max (PM:86)
+                if (n_pad > 0) mx = fmax(mx, 0.0);
+                double sum = 0.0;
+                int before = 0;
+                for (int x = x0; x < x1; ++x) {
+                    const int ex = g.inc_edge[x];
+                    if (ex < 0 || ex >= g.n_edges) continue;
+                    const double lg = -(double)g.inc_sign[x] * row_dot(v, k, ex, c);
+                    sum += exp(lg - mx);
+                    const int a0 = g.edge_nodes[2 * (size_t)ex], a1 = g.edge_nodes[2 * (size_t)ex + 1];
+                    const int other = a0 == a ? a1 : a0;
+                    before += (lg > taken || (lg == taken && other < b)) ? 1 : 0;
+                }
+                double all = sum;
+                if (n_pad > 0) all += (double)n_pad * exp(0.0 - mx);
+                lp = taken - (mx + log(all));
+                ms = log(sum / all);
+                rk = before;
+            }
+            logp[t] = lp;
+            rank[t] = rk;
+            mass[t] = ms;
+        }
+        bad_before = bad_before || bad != 0;
+        __syncthreads();
+    }
+}
+
 int grid_for(int64_t n_rows, int k) {
     const int64_t per_block = (int64_t)WAVES * (WAVE / k);
     const int64_t blocks = (n_rows + per_block - 1) / per_block;
@@ -412,6 +524,21 @@ int scn_project_predict(int32_t n, int32_t k, int32_t n_edges, const double* v, 
     return scn::launch_checked(project_predict_kernel, dim3((unsigned)n), dim3(WAVE), 0, (hipStream_t)stream, k, v, flow_ptr, flow_idx,
                                flow_val, last, Readout{inc_ptr, inc_edge, inc_sign, edge_nodes, nbr, deg, n_nodes, n_edges, d}, logits,
                                probs, argmax, err);
+}
+
+int scn_project_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t k, int32_t n_edges,
+                            const double* v, int32_t n_nodes, const int32_t* inc_ptr, const int32_t* inc_edge, const float* inc_sign,
+                            const int32_t* edge_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, double* logp, int32_t* rank,
+                            double* mass, double* coef, int32_t* err, void* stream) {
+    if (n_paths < 0 || n_edges <= 0 || n_nodes <= 0 || d <= 0) return SCN_ERR_BAD_SHAPE;
+    if (k < 0 || k > KMAX) return SCN_ERR_UNSUPPORTED;
+    if (n_paths == 0) return SCN_OK;
+    if ((k > 0 && !v) || !path_ptr || !inc_ptr || !inc_edge || !inc_sign || !edge_nodes || !nbr || !deg || !err) return SCN_ERR_BAD_ARG;
+    if (!path_nodes && !logp && !rank && !mass) return SCN_OK;       // paths without a node: T == 0, nothing to write
+    if (!path_nodes || !logp || !rank || !mass) return SCN_ERR_BAD_ARG;
+    return scn::launch_checked(project_path_scores_kernel, dim3((unsigned)n_paths), dim3(WAVE), 0, (hipStream_t)stream, k, v, path_ptr,
+                               path_nodes, Readout{inc_ptr, inc_edge, inc_sign, edge_nodes, nbr, deg, n_nodes, n_edges, d}, logp, rank,
+                               mass, coef, err);
 }
 
 int scn_project_two_target(int32_t n, int32_t d, uint64_t seed, const double* probs, const int32_t* target, const int32_t* n_nbrs,

@@ -70,6 +70,18 @@ def ragged(paths):
     return np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(nodes, np.int32)
 
 
+def select_paths(paths, mask):
+    """The paths with mask == 1 as a (ptr, nodes) pair, in their order (all of them without a mask)."""
+    ptr, nodes = ragged(paths)
+    if mask is None:
+        return ptr, nodes
+    rows = np.flatnonzero(np.asarray(mask) == 1)
+    lens = np.diff(ptr).astype(np.int64)[rows]
+    new_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx = np.repeat(ptr[rows].astype(np.int64) - new_ptr[:-1], lens) + np.arange(int(new_ptr[-1]), dtype=np.int64)
+    return np.ascontiguousarray(new_ptr, np.int32), np.ascontiguousarray(nodes[idx])
+
+
 def table_rows(n_nodes, d, order):
     """Rows of the count table (scn_markov_table_rows); ValueError for an order or a size the library does not serve."""
     if int(order) != order or not 1 <= int(order) <= SCN_MARKOV_MAX_ORDER:
@@ -256,6 +268,68 @@ class Markov_Model:
                   "scn_markov_probs")
         self._raise_bad_pair(err, ptr, nodes)
         return probs.cpu().numpy()
+
+    # ---- whole paths: the teacher-forced score of every node (scn_markov_path_scores) ----
+    def _path_records(self, ptr, nodes, alpha):
+        """(prob float64, rank int32, total int32) [T] of scn_markov_path_scores on the host: the paths go up in one buffer, one
+        launch, and the three arrays and the error word come back in one."""
+        P, T = len(ptr) - 1, len(nodes)
+        if T == 0:
+            return np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        up = self._upload(np.concatenate([ptr, nodes]))
+        d_ptr, d_nodes = up[:P + 1], up[P + 1:]
+        out = torch.empty((4 * T + 1,), dtype=torch.int32, device=self.device)      # prob [T] fp64 | rank [T] | total [T] | err
+        out[4 * T:] = INT32_MAX
+        prob, rank, total, err = out[:2 * T].view(torch.float64), out[2 * T:3 * T], out[3 * T:4 * T], out[4 * T:]
+        with torch.cuda.device(self.device):
+            check(_lib.load().scn_markov_path_scores(P, ops._dev(d_ptr, torch.int32), ops._dev(d_nodes, torch.int32), self.order,
+                                                     ctypes.c_double(alpha), *self._graph_args(), ops._dev(self.counts, torch.int32),
+                                                     ops._dev(prob, torch.float64), ops._dev(rank, torch.int32),
+                                                     ops._dev(total, torch.int32), ops._dev(err, torch.int32), ops._stream()),
+                  "scn_markov_path_scores")
+        host = out.cpu()
+        self._raise_bad_pair(host[4 * T:], ptr, nodes)
+        host = host.numpy()
+        return host[:2 * T].view(np.float64), host[2 * T:3 * T], host[3 * T:4 * T]
+
+    def path_step_log_probs(self, paths, min_prefix=2, alpha=0.0):
+        """The teacher-forced scores of every step of every path under the count table, as Scone_GCN.path_step_log_probs gives the
+        model's: a path_scores.PathScores over the items (path p, prefix of k = max(min_prefix, 1) .. len - 1 nodes), each predicting
+        p[k] from the state of the `order` nodes before it.  The probability is (c_j + alpha) / (total + alpha deg): alpha = 0 is
+        the reference's weight (next_node_probs' bits; logp = -inf for a step the table never saw, and for every prefix shorter
+        than `order`), alpha > 0 additive smoothing over the real neighbours (an unseen or short state is uniform).  rank counts
+        the neighbours with a higher count, or an equal one in a lower slot; mass is 0, or -inf where the state has no
+        distribution at all (alpha = 0 and total = 0).  Leaves the items' row totals in self.path_totals.  ValueError for a
+        step that is no edge."""
+        from . import path_scores
+        alpha = float(alpha)
+        if not alpha >= 0.0:
+            raise ValueError("alpha must be at least 0, got %r" % alpha)
+        if self.counts is None:
+            raise RuntimeError("train() first")
+        ptr, nodes = ragged(paths)
+        prob, rank, total = self._path_records(ptr, nodes, alpha)
+        item_ptr, item_path, item_len = path_scores.path_items(ptr, min_prefix)
+        at = path_scores.item_positions(ptr, item_path, item_len)
+        prob, rank, total = prob[at], rank[at].astype(np.int64), total[at].astype(np.int64)
+        with np.errstate(divide="ignore"):
+            logp = np.log(prob)
+        empty = (total == 0) & ((alpha == 0.0) | (self.h_deg[nodes[at - 1]] == 0))
+        self.path_totals = total
+        return path_scores.PathScores(item_ptr, logp, rank, np.where(empty, -np.inf, 0.0), item_len)
+
+    def path_log_likelihood(self, paths, min_prefix=2, alpha=0.0):
+        """(ll [P] float64 = the sum of every path's step log-probabilities, n_steps [P] int64)."""
+        from . import path_scores
+        sc = self.path_step_log_probs(paths, min_prefix, alpha)
+        return path_scores.segment_sums(sc.logp, sc.ptr), np.diff(sc.ptr)
+
+    def score_paths(self, paths, mask=None, min_prefix=2, alpha=0.0):
+        """The dict of Scone_GCN.score_paths over the paths with mask == 1 (all without a mask) -- mean_step_logp, perplexity,
+        accuracy (rank 0), n_steps -- plus n_unseen: the items whose state was never counted (total == 0)."""
+        from . import path_scores
+        sc = self.path_step_log_probs(select_paths(paths, mask), min_prefix, alpha)
+        return dict(path_scores.summary(sc), n_unseen=int((self.path_totals == 0).sum()))
 
     def weights_of(self, prefix):
         """The reference's weights[tuple(prefix)]: {neighbour: probability} of the state of the last `order` nodes of prefix."""

@@ -140,8 +140,18 @@ def score_paths(net, inputs, paths, mask=None, min_prefix=2, normalise=False):
     """Scone_GCN.score_paths."""
     if mask is not None:
         paths = [paths[i] for i in np.flatnonzero(np.asarray(mask) == 1)]
-    sc = step_log_probs(net, inputs, paths, min_prefix, normalise)
+    return summary(step_log_probs(net, inputs, paths, min_prefix, normalise))
+
+
+def summary(sc):
+    """The dict of score_paths (the model's and the baselines') from a PathScores."""
     n = len(sc.logp)
     mean = float(np.sum(sc.logp) / n) if n else float("nan")
     return {"mean_step_logp": mean, "perplexity": float(np.exp(-mean)), "accuracy": float(np.mean(sc.rank == 0)) if n else float("nan"),
             "n_steps": n}
+
+
+def item_positions(path_ptr, item_path, item_len):
+    """The flat node position path_ptr[p] + k of every item (p, k): where the per-position records of the baselines' kernels
+    (scn_markov_path_scores, scn_project_path_scores) hold the item's prediction."""
+    return np.asarray(path_ptr, np.int64)[:-1][item_path] + item_len

@@ -295,6 +295,68 @@ class Projection_Model:
                 raise ValueError("trajectory %d: its last node's edges and the neighbour table disagree" % i)
             return probs.cpu().numpy(), logits.cpu().numpy(), arg.cpu().numpy().astype(np.int64)
 
+    # ---- whole paths: the teacher-forced score of every node (scn_project_path_scores) ----
+    def path_records(self, paths, with_coef=False):
+        """(ptr, nodes, logp, rank, mass, coef) of scn_project_path_scores on the host: one record per node position of the paths (a
+        list of node lists or a (ptr, nodes) pair), coef (T, dim) only when asked for.  The paths go up in one buffer, one launch, and
+        the records and the error word come back in one.  ValueError for a step between two nodes that share no edge."""
+        from .markov_model import ragged
+        self._need_basis()
+        ptr, nodes = ragged(paths)
+        P, T, k = len(ptr) - 1, len(nodes), self.dim
+        if T == 0:
+            return ptr, nodes, np.zeros(0), np.zeros(0, np.int32), np.zeros(0), (np.zeros((0, k)) if with_coef else None)
+        n_coef = T * k if with_coef else 0
+        with torch.cuda.device(self.device):
+            up = self._up(np.concatenate([ptr, nodes]), _I32)
+            d_ptr, d_nodes = up[:P + 1], up[P + 1:]
+            out = torch.empty((2 * T + n_coef + T + 1,), dtype=_F64, device=self.device)   # logp | mass | coef | rank and err (int32)
+            logp, mass, coef = out[:T], out[T:2 * T], out[2 * T:2 * T + n_coef]
+            words = out[2 * T + n_coef:].view(_I32)
+            rank, err = words[:T], words[T:T + 1]
+            err.fill_(INT32_MAX)
+            t = self._tab
+            check(_lib.load().scn_project_path_scores(P, _p(d_ptr, _I32), _p(d_nodes, _I32), k, self.n_edges, _p(self._V, _F64),
+                                                      self.n_nodes, _p(t[0], _I32), _p(t[1], _I32), _p(t[2], torch.float32),
+                                                      _p(t[3], _I32), self.width, _p(t[4], _I32), _p(t[5], _I32), _p(logp, _F64),
+                                                      _p(rank, _I32), _p(mass, _F64), _p(coef, _F64), _p(err, _I32), ops._stream()),
+                  "scn_project_path_scores")
+            host = out.cpu().numpy()
+        words = host[2 * T + n_coef:].view(np.int32)
+        bad = int(words[T])
+        if bad != INT32_MAX:
+            p = int(np.searchsorted(ptr, bad, side="right")) - 1
+            raise ValueError("path %d, position %d: nodes %d and %d share no edge of the complex"
+                             % (p, bad - int(ptr[p]), nodes[bad], nodes[bad + 1]))
+        return ptr, nodes, host[:T], words[:T], host[T:2 * T], (host[2 * T:2 * T + n_coef].reshape(T, k) if with_coef else None)
+
+    def path_step_log_probs(self, paths, min_prefix=2, normalise=False):
+        """The teacher-forced scores of every step of every path under the projection, as Scone_GCN.path_step_log_probs gives the
+        model's: a path_scores.PathScores over the items (path p, prefix of k = max(min_prefix, 1) .. len - 1 nodes), each predicting
+        p[k] from the harmonic coefficients of the k - 1 steps before it.  No prefix flow is built: the coefficients are a running
+        sum along the path.  logp is the log of predict()'s probability at the slot taken (the padding slots inside the soft-max),
+        minus mass when normalised; rank counts the real neighbours the projection puts before it, mass is the log of the
+        probability it leaves on real neighbours."""
+        from . import path_scores
+        ptr, _, logp, rank, mass, _ = self.path_records(paths)
+        item_ptr, item_path, item_len = path_scores.path_items(ptr, min_prefix)
+        at = path_scores.item_positions(ptr, item_path, item_len)
+        logp, mass = logp[at], mass[at]
+        return path_scores.PathScores(item_ptr, logp - mass if normalise else logp, rank[at].astype(np.int64), mass, item_len)
+
+    def path_log_likelihood(self, paths, min_prefix=2, normalise=False):
+        """(ll [P] float64 = the sum of every path's step log-probabilities, n_steps [P] int64)."""
+        from . import path_scores
+        sc = self.path_step_log_probs(paths, min_prefix, normalise)
+        return path_scores.segment_sums(sc.logp, sc.ptr), np.diff(sc.ptr)
+
+    def score_paths(self, paths, mask=None, min_prefix=2, normalise=False):
+        """The dict of Scone_GCN.score_paths over the paths with mask == 1 (all without a mask): mean_step_logp, perplexity,
+        accuracy (rank 0), n_steps."""
+        from . import path_scores
+        from .markov_model import select_paths
+        return path_scores.summary(self.path_step_log_probs(select_paths(paths, mask), min_prefix, normalise))
+
     def predict(self, flows, last_nodes):
         """Probabilities (N, D) of the next node by slot of the last node's sorted neighbourhood (PM:80-96); the padding slots
         enter the soft-max with logit 0, as they do there."""

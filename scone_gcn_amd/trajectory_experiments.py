@@ -289,18 +289,19 @@ def markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mas
     return results
 
 
-def projection_experiments(sc, folder, seed=0):
+def projection_experiments(sc, folder, seed=0, pm=None):
     """The harmonic projection baseline's experiments (the reference's projection_model.py, PM:215-227) with its print labels, on
     the device (projection_model.Projection_Model): standard test set, reversed test set when the folder has the rev_* files,
     2-target, transfer (rows i % 3 == 2).  The data set is read again, as PM reads it itself: the baseline works on the unflipped
-    flows whatever -flip_edges says (the result does not depend on the flips).  The basis is computed once.  Returns
+    flows whatever -flip_edges says (the result does not depend on the flips).  The basis is computed once, or taken from pm, a
+    Projection_Model already embedded in sc.  Returns
     {"standard": (loss, acc), "reverse": (loss, acc), "two_target": acc, "two_target_slots": drawn slots, "transfer": (loss, acc),
     "dim", "iterations", "residual"}."""
     from .dataset_io import load_dataset, load_reverse
     from .projection_model import Projection_Model
     X, _, y, _, test_mask, _, last_nodes, _ = load_dataset(folder)
     last_nodes, test_mask = np.asarray(last_nodes), np.asarray(test_mask)
-    pm = Projection_Model(seed=seed).embed(sc)
+    pm = Projection_Model(seed=seed).embed(sc) if pm is None else pm
     results = {"dim": pm.dim, "iterations": pm.iterations, "residual": pm.residual}
     results["standard"] = pm.test(X, last_nodes, y, test_mask)
     print('Standard experiment loss / acc:', results["standard"])
@@ -326,7 +327,10 @@ def train_model(hp=None):
     train the model.  With -projection 1 the harmonic projection baseline runs next (projection_experiments) and its results go to
     experiment_results["projection"]; training follows as well.  With -path_likelihood 1 the trained model scores every path
     prefixes[i] + [target_nodes_all[0][i]] step by step (Scone_GCN.score_paths) over the train and the test mask:
-    experiment_results["path_likelihood"] = {"train": ..., "test": ...}.  With -train_paths 1 (-path_min_prefix, -path_weight) the
+    experiment_results["path_likelihood"] = {"train": ..., "test": ...}; with -markov 1 and / or -projection 1 beside it, the same
+    items are scored by a Markov_Model(-markov_order) trained on the train mask's paths (additive smoothing -markov_alpha, default 1)
+    and by the projection (Markov_Model.score_paths, Projection_Model.score_paths): experiment_results["path_likelihood_markov"] /
+    ["path_likelihood_projection"], same layout.  With -train_paths 1 (-path_min_prefix, -path_weight) the
     model is trained on every (path, prefix) item of those same paths (Scone_GCN.train_paths) in place of train(); the losses and
     accuracies returned are then test()'s on the two masks, and everything after training runs as before."""
     from .scone_trajectory_model import Scone_GCN
@@ -339,9 +343,11 @@ def train_model(hp=None):
     if hp.get('markov', 0) == 1:                                           # TE:327-432
         markov_results = markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask,
                                             order=int(hp.get('markov_order', 1)))
-    projection_results = None
+    projection_results = projection = None
     if hp.get('projection', 0) == 1:                                       # the reference's projection_model.py, PM:215-227
-        projection_results = projection_experiments(G_undir.complex, 'trajectory_data_1hop_' + hp['data_folder_suffix'])
+        from .projection_model import Projection_Model
+        projection = Projection_Model(seed=0).embed(G_undir.complex)       # one basis: the experiments' and the path likelihood's
+        projection_results = projection_experiments(G_undir.complex, 'trajectory_data_1hop_' + hp['data_folder_suffix'], pm=projection)
     scone = Scone_GCN(hp['epochs'], hp['learning_rate'], hp['batch_size'], hp['weight_decay'],
                       skip_mode=hp.get('skip_mode', 'dense'), multi_hop_skip=hp.get('multi_hop_skip', 'dense'))
     if hp['model'] not in MODEL_FUNCS:
@@ -413,6 +419,21 @@ def train_model(hp=None):
         for name, r in results["path_likelihood"].items():
             print('Path likelihood ({}): mean step log-prob {:.6f} -- perplexity {:.4f} -- step acc {:.3f} -- steps {}'.format(
                 name, r["mean_step_logp"], r["perplexity"], r["accuracy"], r["n_steps"]))
+        masks = (("train", train_mask), ("test", test_mask))
+        baselines = {}
+        if hp.get('markov', 0) == 1:                                       # the count table of the train paths, smoothed (-markov_alpha)
+            from .markov_model import Markov_Model
+            markov = Markov_Model(int(hp.get('markov_order', 1)))
+            markov.train(G_undir, [paths[i] for i in np.flatnonzero(np.asarray(train_mask) == 1)])
+            alpha = float(hp.get('markov_alpha', 1.0))
+            baselines["markov"] = {name: markov.score_paths(paths, m, alpha=alpha) for name, m in masks}
+        if projection is not None:
+            baselines["projection"] = {name: projection.score_paths(paths, m) for name, m in masks}
+        for which, res in baselines.items():
+            results["path_likelihood_" + which] = res
+            for name, r in res.items():
+                print('Path likelihood, {} baseline ({}): mean step log-prob {:.6f} -- perplexity {:.4f} -- step acc {:.3f} -- steps {}'
+                      .format(which, name, r["mean_step_logp"], r["perplexity"], r["accuracy"], r["n_steps"]))
     if markov_results is not None:
         results["markov"] = markov_results
     if projection_results is not None:
