@@ -470,6 +470,18 @@ typedef struct {
 int scn_cone_masks(int32_t n_mb, const scn_cone_mb* mb, int32_t ns, int32_t n_nodes, int32_t n_blocks, const int32_t* top_ptr,
                    const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L, void* stream);
 int64_t scn_cone_masks_max_words(void);
+/* Visit masks.  dZ_L is non-zero only on the rows R0 the readout's backward writes, so layer l's backward gathers non-zero values only
+ * on R_k = P^k R0, k = L - l + 1 (P: the pattern its rows read, diagonal included): a (block, slab) item of M_k with no row in R_k
+ * stages only +0, and a visiting backward may leave it out.  V_k = the items holding a row of R_k, a subset of M_k, is a keep mask
+ * against a table of its own, T_k: node v -> the blocks holding a row of P^k rows(v) (rows(v): behind `top`; the caller builds T_k).
+ * scn_cone_masks_visits = scn_cone_masks -- the same masks, lists and counters, bit for bit -- whose launch also writes, for micro-batch
+ *   i, visits[i] [L - 1][stride]: V_1 .. V_{L-1}, V_k = scn_keep_mask's mask of (node, n) against (visit_ptr[k - 1], visit_blk[k - 1])
+ *   (HOST arrays of L - 1 device tables, n_nodes + 1 and visit_ptr[.][n_nodes] entries; visits: a HOST array of n_mb device pointers;
+ *   none of the three is read for L = 1).  Every word of every V_k is written: no memset; no lists; no launch more than scn_cone_masks.
+ *   The same guards and the same refusals, before anything is launched or written. */
+int scn_cone_masks_visits(int32_t n_mb, const scn_cone_mb* mb, uint32_t* const* visits, int32_t ns, int32_t n_nodes, int32_t n_blocks,
+                          const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L,
+                          const int32_t* const* visit_ptr, const int32_t* const* visit_blk, void* stream);
 
 /* Diagnostic, like scn_conv_plan_blocks; no step uses it.  The masked launches above do not walk a workgroup's units one at a time:
  * ahead of the block loop a workgroup fetches the blocks and the mask windows of its units in batches and keeps, in order, the units

@@ -169,6 +169,9 @@ SIGNATURES = {
     "scn_cone_masks": (ctypes.c_int, [c_i32, ctypes.POINTER(ConeMb), c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
                                       c_void_p]),
     "scn_cone_masks_max_words": (c_i64, []),
+    "scn_cone_masks_visits": (ctypes.c_int, [c_i32, ctypes.POINTER(ConeMb), ctypes.POINTER(c_void_p), c_i32, c_i32, c_i32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_i32, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                             c_void_p]),
     "scn_conv_forward_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p), P_i32, ctypes.POINTER(c_void_p),
                                                    c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scn_conv_forward_from_y_keep_units": (ctypes.c_int, [c_void_p, c_i32, c_i32, c_void_p, ctypes.POINTER(c_void_p),

@@ -1,5 +1,6 @@
 // Readout (+ log-softmax), its backward, flow scatter and the fused Adam/ridge step.
 #include <cstring>
+#include <type_traits>
 
 #include "scn_internal.h"
 
@@ -304,8 +305,50 @@ __device__ __forceinline__ uint32_t cm_gather(const CmRows& R, const CmBatch& B,
     return a;
 }
 
-template <int MAXT>
-__global__ __launch_bounds__(CM_THREADS) void cone_masks_kernel(ConeMasksArgs A, int ns, int n_nodes, int n_blocks,
+// The keep phase of a node -> blocks table into the zeroed LDS image: CM_LEAF_LANES threads stride over a leaf's row of the table and
+// OR the leaf's slab bit into the words of its blocks.  Barriers are the caller's: one before (the image is zero), one behind.
+__device__ __forceinline__ void cm_keep(const int32_t* __restrict__ node, int n, int ns, int n_nodes, const int32_t* __restrict__ ptr,
+                                        const int32_t* __restrict__ blk, int n_blocks, int words, uint32_t* img) {
+    const int t = threadIdx.x;
+    for (int i = t / CM_LEAF_LANES; i < n; i += CM_THREADS / CM_LEAF_LANES) {
+        const int v = node[i];
+        if (v < 0 || v >= n_nodes) continue;
+        const int s = i / ns;
+        const uint32_t bit = 1u << (s & 31);
+        const int q1 = ptr[v + 1];
+        for (int q = ptr[v] + t % CM_LEAF_LANES; q < q1; q += CM_LEAF_LANES) {
+            const int b = blk[q];
+            if (b >= 0 && b < n_blocks) atomicOr(&img[b * words + (s >> 5)], bit);
+        }
+    }
+}
+
+// The image's n_words words out to global: 16-byte stores between the destination's first and last 16-byte boundary, single words
+// outside them.
+__device__ __forceinline__ void cm_stream_out(uint32_t* __restrict__ dst, const uint32_t* img, int n_words) {
+    const int t = threadIdx.x;
+    const int head = min(n_words, (int)(((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u) >> 2));
+    const int body = (n_words - head) & ~3;
+    if (t < head) dst[t] = img[t];
+    for (int i = head + t * 4; i < head + body; i += CM_THREADS * 4)
+        *reinterpret_cast<uint4*>(dst + i) = make_uint4(img[i], img[i + 1], img[i + 2], img[i + 3]);
+    if (t < n_words - head - body) dst[head + body + t] = img[head + body + t];
+}
+
+// VIS (scn_cone_masks_visits): behind the chain the workgroup also builds the visit masks V_1 .. V_{L-1} of its micro-batch, V_k = the
+// keep mask of its last nodes against the table T_k (node -> the blocks holding a row k operator hops out from the readout's rows):
+// the image is zeroed, the keep phase runs against T_k, the image goes out.  Every word of every V_k is written; no lists.
+struct ConeVisitArgs {
+    uint32_t* out[SCN_CONE_MASKS_MAX_MB];              // [L - 1][stride] of every micro-batch
+    const int32_t* ptr[SCN_UNIT_COUNTERS - 1];         // T_1 .. T_{L-1}
+    const int32_t* blk[SCN_UNIT_COUNTERS - 1];
+};
+
+struct ConeNoVisits {};
+
+template <int MAXT, bool VIS>
+__global__ __launch_bounds__(CM_THREADS) void cone_masks_kernel(ConeMasksArgs A, std::conditional_t<VIS, ConeVisitArgs, ConeNoVisits> VA,
+                                                                int ns, int n_nodes, int n_blocks,
                                                                 const int32_t* __restrict__ top_ptr, const int32_t* __restrict__ top_blk,
                                                                 const int32_t* __restrict__ adj_ptr, const int32_t* __restrict__ adj_blk,
                                                                 int L) {
@@ -335,27 +378,9 @@ __global__ __launch_bounds__(CM_THREADS) void cone_masks_kernel(ConeMasksArgs A,
     const int zero_at = (n_words + 3) & ~3;            // four words behind the image that stay zero: what a hop reads for an entry it passes over
     for (int i = t * 4; i < zero_at + 4; i += CM_THREADS * 4) *reinterpret_cast<uint4*>(cm_img + i) = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
-    for (int i = t / CM_LEAF_LANES; i < n; i += CM_THREADS / CM_LEAF_LANES) {
-        const int v = node[i];
-        if (v < 0 || v >= n_nodes) continue;
-        const int s = i / ns;
-        const uint32_t bit = 1u << (s & 31);
-        const int q1 = top_ptr[v + 1];
-        for (int q = top_ptr[v] + t % CM_LEAF_LANES; q < q1; q += CM_LEAF_LANES) {
-            const int b = top_blk[q];
-            if (b >= 0 && b < n_blocks) atomicOr(&cm_img[b * words + (s >> 5)], bit);
-        }
-    }
+    cm_keep(node, n, ns, n_nodes, top_ptr, top_blk, n_blocks, words, cm_img);
     __syncthreads();
-    {
-        // 16-byte stores between the destination's first and last 16-byte boundary, single words outside them
-        const int head = min(n_words, (int)(((16u - (uint32_t)((uintptr_t)mask & 15u)) & 15u) >> 2));
-        const int body = (n_words - head) & ~3;
-        if (t < head) mask[t] = cm_img[t];
-        for (int i = head + t * 4; i < head + body; i += CM_THREADS * 4)
-            *reinterpret_cast<uint4*>(mask + i) = make_uint4(cm_img[i], cm_img[i + 1], cm_img[i + 2], cm_img[i + 3]);
-        if (t < n_words - head - body) mask[head + body + t] = cm_img[head + body + t];
-    }
+    cm_stream_out(mask, cm_img, n_words);
     uint32_t acc[MAXT];
 #pragma unroll
     for (int j = 0; j < MAXT; ++j) {
@@ -410,23 +435,86 @@ __global__ __launch_bounds__(CM_THREADS) void cone_masks_kernel(ConeMasksArgs A,
             if (i == t) c = counts[i];
         mb.counters[t] = c;
     }
+    if constexpr (VIS) {
+        uint32_t* __restrict__ vis = VA.out[blockIdx.x];
+#pragma unroll 1
+        for (int k = 1; k < L; ++k, vis += mb.stride) {
+            __syncthreads();                           // everybody is done with the image (cm_list's readers, the V before this one going out)
+            for (int i = t * 4; i < zero_at; i += CM_THREADS * 4) *reinterpret_cast<uint4*>(cm_img + i) = make_uint4(0u, 0u, 0u, 0u);
+            __syncthreads();
+            cm_keep(node, n, ns, n_nodes, VA.ptr[k - 1], VA.blk[k - 1], n_blocks, words, cm_img);
+            __syncthreads();
+            cm_stream_out(vis, cm_img, n_words);
+        }
+    }
 }
 
 // one instantiation's launch; its dynamic-LDS attribute is set once per device, at the instantiation's full size, not per call
-template <int MAXT>
-static int cone_masks_launch(const ConeMasksArgs& A, int n_mb, size_t lds, hipStream_t st, int ns, int n_nodes, int n_blocks,
-                             const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int L) {
+// (VA: a ConeVisitArgs, and the kernel builds the visit masks too, or a ConeNoVisits)
+template <int MAXT, class Visits>
+static int cone_masks_launch(const ConeMasksArgs& A, const Visits& VA, int n_mb, size_t lds, hipStream_t st, int ns, int n_nodes,
+                             int n_blocks, const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk,
+                             int L) {
+    constexpr bool VIS = std::is_same<Visits, ConeVisitArgs>::value;
     static bool attr_set[64] = {};
     int dev = 0;
     SCN_HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        SCN_HIP_TRY(hipFuncSetAttribute((const void*)cone_masks_kernel<MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        SCN_HIP_TRY(hipFuncSetAttribute((const void*)cone_masks_kernel<MAXT, VIS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         MAXT * CM_THREADS * 4 + 16));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(cone_masks_kernel<MAXT>, dim3(n_mb), dim3(CM_THREADS), lds, st, A, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr,
-                       adj_blk, L);
+    hipLaunchKernelGGL((cone_masks_kernel<MAXT, VIS>), dim3(n_mb), dim3(CM_THREADS), lds, st, A, VA, ns, n_nodes, n_blocks, top_ptr, top_blk,
+                       adj_ptr, adj_blk, L);
     SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+// scn_cone_masks (Visits = ConeNoVisits; visits .. visit_blk unused) and scn_cone_masks_visits (ConeVisitArgs) behind their own checks
+template <class Visits>
+static int cone_masks_run(int32_t n_mb, const scn_cone_mb* mb, uint32_t* const* visits, int32_t ns, int32_t n_nodes, int32_t n_blocks,
+                          const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L,
+                          const int32_t* const* visit_ptr, const int32_t* const* visit_blk, void* stream) {
+    constexpr bool VIS = std::is_same<Visits, ConeVisitArgs>::value;
+    if (!mb || !top_ptr || !top_blk || !adj_ptr || !adj_blk) return SCN_ERR_BAD_ARG;
+    if (n_mb <= 0 || ns <= 0 || n_nodes <= 0 || n_blocks <= 0 || L <= 0) return SCN_ERR_BAD_SHAPE;
+    if (L > SCN_UNIT_COUNTERS) return SCN_ERR_UNSUPPORTED;
+    if (VIS && L > 1) {
+        if (!visits || !visit_ptr || !visit_blk) return SCN_ERR_BAD_ARG;
+        for (int k = 0; k < L - 1; ++k)
+            if (!visit_ptr[k] || !visit_blk[k]) return SCN_ERR_BAD_ARG;
+    }
+    // everything is checked before the first launch: a declined call has launched and written nothing
+    int64_t widest = 0;
+    for (int i = 0; i < n_mb; ++i) {
+        if (!mb[i].node || !mb[i].masks || !mb[i].units || !mb[i].counters || (VIS && L > 1 && !visits[i])) return SCN_ERR_BAD_ARG;
+        if (mb[i].n <= 0) return SCN_ERR_BAD_SHAPE;
+        const int64_t n_words = cone_masks_words(mb[i].n, ns, n_blocks);
+        if (L > 1 && mb[i].stride < n_words) return SCN_ERR_WORKSPACE;
+        widest = std::max(widest, n_words);
+    }
+    if (widest > INT32_MAX || widest > SCN_CONE_MASKS_MAX_WORDS) return SCN_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)((widest + 3) / 4 * 4 + 4) * sizeof(uint32_t);         // (the image and its four zero words)
+    const int trips = (int)((widest + CM_THREADS - 1) / CM_THREADS);
+    for (int i0 = 0; i0 < n_mb; i0 += SCN_CONE_MASKS_MAX_MB) {
+        const int m = std::min<int>(SCN_CONE_MASKS_MAX_MB, n_mb - i0);
+        ConeMasksArgs A{};
+        std::memcpy(A.mb, mb + i0, sizeof(scn_cone_mb) * (size_t)m);
+        Visits VA{};
+        if constexpr (VIS) {
+            for (int k = 0; k < L - 1; ++k) VA.ptr[k] = visit_ptr[k], VA.blk[k] = visit_blk[k];
+            if (L > 1) std::memcpy(VA.out, visits + i0, sizeof(uint32_t*) * (size_t)m);
+        }
+        int rc;
+        if (trips <= 4)
+            rc = cone_masks_launch<4>(A, VA, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
+        else if (trips <= 20)
+            rc = cone_masks_launch<20>(A, VA, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
+        else
+            rc = cone_masks_launch<SCN_CONE_MASKS_MAX_WORDS / CM_THREADS>(A, VA, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr,
+                                                                          top_blk, adj_ptr, adj_blk, L);
+        if (rc != SCN_OK) return rc;
+    }
     return SCN_OK;
 }
 
@@ -850,36 +938,15 @@ int64_t scn_cone_masks_max_words(void) { return SCN_CONE_MASKS_MAX_WORDS; }
 
 int scn_cone_masks(int32_t n_mb, const scn_cone_mb* mb, int32_t ns, int32_t n_nodes, int32_t n_blocks, const int32_t* top_ptr,
                    const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L, void* stream) {
-    if (!mb || !top_ptr || !top_blk || !adj_ptr || !adj_blk) return SCN_ERR_BAD_ARG;
-    if (n_mb <= 0 || ns <= 0 || n_nodes <= 0 || n_blocks <= 0 || L <= 0) return SCN_ERR_BAD_SHAPE;
-    if (L > SCN_UNIT_COUNTERS) return SCN_ERR_UNSUPPORTED;
-    // everything is checked before the first launch: a declined call has launched and written nothing
-    int64_t widest = 0;
-    for (int i = 0; i < n_mb; ++i) {
-        if (!mb[i].node || !mb[i].masks || !mb[i].units || !mb[i].counters) return SCN_ERR_BAD_ARG;
-        if (mb[i].n <= 0) return SCN_ERR_BAD_SHAPE;
-        const int64_t n_words = cone_masks_words(mb[i].n, ns, n_blocks);
-        if (L > 1 && mb[i].stride < n_words) return SCN_ERR_WORKSPACE;
-        widest = std::max(widest, n_words);
-    }
-    if (widest > INT32_MAX || widest > SCN_CONE_MASKS_MAX_WORDS) return SCN_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)((widest + 3) / 4 * 4 + 4) * sizeof(uint32_t);         // (the image and its four zero words)
-    const int trips = (int)((widest + CM_THREADS - 1) / CM_THREADS);
-    for (int i0 = 0; i0 < n_mb; i0 += SCN_CONE_MASKS_MAX_MB) {
-        const int m = std::min<int>(SCN_CONE_MASKS_MAX_MB, n_mb - i0);
-        ConeMasksArgs A{};
-        std::memcpy(A.mb, mb + i0, sizeof(scn_cone_mb) * (size_t)m);
-        int rc;
-        if (trips <= 4)
-            rc = cone_masks_launch<4>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
-        else if (trips <= 20)
-            rc = cone_masks_launch<20>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L);
-        else
-            rc = cone_masks_launch<SCN_CONE_MASKS_MAX_WORDS / CM_THREADS>(A, m, lds, (hipStream_t)stream, ns, n_nodes, n_blocks, top_ptr,
-                                                                          top_blk, adj_ptr, adj_blk, L);
-        if (rc != SCN_OK) return rc;
-    }
-    return SCN_OK;
+    return cone_masks_run<ConeNoVisits>(n_mb, mb, nullptr, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L, nullptr, nullptr,
+                                        stream);
+}
+
+int scn_cone_masks_visits(int32_t n_mb, const scn_cone_mb* mb, uint32_t* const* visits, int32_t ns, int32_t n_nodes, int32_t n_blocks,
+                          const int32_t* top_ptr, const int32_t* top_blk, const int32_t* adj_ptr, const int32_t* adj_blk, int32_t L,
+                          const int32_t* const* visit_ptr, const int32_t* const* visit_blk, void* stream) {
+    return cone_masks_run<ConeVisitArgs>(n_mb, mb, visits, ns, n_nodes, n_blocks, top_ptr, top_blk, adj_ptr, adj_blk, L, visit_ptr,
+                                         visit_blk, stream);
 }
 
 int scn_node_readout_forward(int32_t n_slabs, int32_t ns, int32_t n_nodes, const float* nodes_out,

@@ -96,6 +96,7 @@ VISIT_RECORDS = True   # a unit's top reads the block's packed 32-byte record.  
 # ... and one the trainer's micro-batch loop reads (SconePlan.step):
 STEP_TAIL = True       # a cone step's readout chain is one launch, and its loss sum, dW reduces and clears one more.  False: nine launches
 STEP_MASKS = True      # the cone masks of all of a step's micro-batches come from one launch ahead of the first.  False: five launches each
+VISIT_ROWS = True      # ... and that launch also builds the visit masks V_k, the items of M_k a row of P^k R0 lies in, for the step's backwards.  False: M_k
 # ... and one the path trainer's staging reads (path_train.py):
 PATH_STAGE_SPARSE_CLEAR = True  # a restaged micro-batch buffer resets only the words its previous items wrote.  False: the dense zero fill
 UNIT_COUNTERS = 4      # SCN_UNIT_COUNTERS (include/scone_hip.h): counter words behind the mask of scn_keep_mask_units
@@ -268,6 +269,64 @@ def field_tables(row0, pattern_csr, nbr, inc_ptr, inc_edge):
     return tuple(out)
 
 
+VISIT_TABLES_MAX_WORK = 1 << 30    # multiplies of one sparse product of visit_tables (the benchmark's largest: 1.1e8); also keeps ptr in int32
+
+
+def visit_tables(row0, pattern_csr, nbr, inc_ptr, inc_edge, hops, max_work=None):
+    """The node -> blocks tables of the visit masks (scn_cone_masks_visits), int32 CSR pairs like `top` of field_tables, block indices
+    ascending in every row: [(ptr, blk) of T_k for k = 1 .. hops], T_k(v) = the blocks holding a row of R_k(v) = P^k rows(v).
+      rows(v): the rows behind T(v) of field_tables -- the edges incident to a neighbour of v, where the readout's backward writes;
+      P:       the STORED pattern with the diagonal, rows read columns as in `adj`: R_k = R_{k-1} and every row with an entry in a column
+               of R_{k-1} -- where the gather of the backward k layers down from the readout can be non-zero (symmetric shifts).
+    T_k(v) is a subset of A^k(T(v)) by construction.  Sparse products, node by node through the incidence lists: rows(v) is the union
+    of its neighbours' incidence ranges and P^k distributes over it, so the row-level product runs once per node, not once per pair.
+    Arguments as field_tables.  None where a product would take more than max_work multiplies (default VISIT_TABLES_MAX_WORK):
+    the caller then has no visit masks and the backwards visit M_k."""
+    import scipy.sparse as sp
+    max_work = VISIT_TABLES_MAX_WORK if max_work is None else max_work
+    row0 = np.asarray(row0, np.int64)
+    nb, E = len(row0) - 1, int(row0[-1])
+    blk_of = np.searchsorted(row0, np.arange(E), side="right") - 1
+    rowptr, cols = (pattern_csr.indptr, pattern_csr.indices) if hasattr(pattern_csr, "indptr") else pattern_csr
+    rowptr, cols = np.asarray(rowptr, np.int64), np.asarray(cols, np.int64)
+    assert len(rowptr) == E + 1, "the pattern's rows are the blocks' rows"
+    rows = np.repeat(np.arange(E), np.diff(rowptr))
+    # PT[c, r] != 0: row r reads column c (or r == c)
+    PT = sp.csr_matrix((np.ones(len(rows) + E, np.int32), (np.concatenate([cols, np.arange(E)]), np.concatenate([rows, np.arange(E)]))),
+                       shape=(E, E))
+    PT.data[:] = 1
+    B = sp.csr_matrix((np.ones(E, np.int32), (np.arange(E), blk_of)), shape=(E, nb))
+    nbr, inc_ptr, inc_edge = np.asarray(nbr, np.int64), np.asarray(inc_ptr, np.int64), np.asarray(inc_edge, np.int64)
+    V, U = nbr.shape[0], len(inc_ptr) - 1
+    v, j = np.nonzero(nbr >= 0)
+    N = sp.csr_matrix((np.ones(len(v), np.int32), (v, nbr[v, j])), shape=(V, U))
+    X = sp.csr_matrix((np.ones(int(inc_ptr[U]), np.int32), (np.repeat(np.arange(U), np.diff(inc_ptr)), inc_edge[:inc_ptr[U]])),
+                      shape=(U, E))                      # node u -> its incident edges, then hop by hop
+    # every product is bounded BEFORE it is formed: its multiplies -- an upper bound of its entries -- are the left factor's entries
+    # weighted by the right factor's row lengths.  An operator with a hub row makes P^2 dense; the tables are then refused, not built.
+    work = lambda A, Bm: int(np.diff(Bm.indptr)[A.indices].sum())          # noqa: E731
+    out = []
+    for _ in range(hops):
+        if work(X, PT) > max_work:
+            return None
+        X = (X @ PT).tocsr()
+        X.data[:] = 1                                   # (a pattern: the counts would only grow)
+        XB = (X @ B).tocsr()                            # (one block per row: no more entries than X)
+        if work(N, XB) > max_work:
+            return None
+        T = (N @ XB).tocsr()
+        T.sum_duplicates()
+        T.sort_indices()
+        out.append((np.ascontiguousarray(T.indptr, np.int32), np.ascontiguousarray(T.indices, np.int32)))
+    return out
+
+
+def visit_masks_host(nodes, ns, tables, n_blocks):
+    """NumPy restatement of the visit masks of scn_cone_masks_visits (include/scone_hip.h): [V_1 .. V_hops], V_k = keep_mask_host
+    against T_k of `tables` (visit_tables)."""
+    return [keep_mask_host(nodes, ns, ptr, blk, n_blocks) for ptr, blk in tables]
+
+
 def keep_mask_host(nodes, ns, top_ptr, top_blk, n_blocks):
     """NumPy restatement of scn_keep_mask (include/scone_hip.h): uint32 [n_blocks][ceil(n_slabs / 32)], bit s & 31 of word
     [b][s >> 5] set iff a leaf i of slab s = i // ns has block b in T(nodes[i]).  A node outside the table contributes nothing, nor
@@ -363,6 +422,12 @@ class FieldTables(NamedTuple):
     top_blk: object
     adj_ptr: object
     adj_blk: object
+
+
+class VisitTables(NamedTuple):
+    """Device copies of visit_tables for one plan: ptr[k - 1], blk[k - 1] = T_k."""
+    ptr: list
+    blk: list
 
 
 class ConvOp:
@@ -471,12 +536,14 @@ class ConvOp:
                 _dev(units, torch.int32), _dev(counter, torch.int32), units.numel(), _stream())
         return out, UnitList(units, counter)
 
-    def cone_masks(self, last_devs, ns, n_nodes, tabs, L):
+    def cone_masks(self, last_devs, ns, n_nodes, tabs, L, visit_tabs=None):
         """The cones of several micro-batches in ONE launch (scn_cone_masks): for every int32 device tensor of last nodes in last_devs a
         Cone [M0 .. M_{L-1}] with every mask's UnitList, as keep_mask_units() and L - 1 mask_hop_units() build them (the lists
         ascending).  Masks, entries and counters are views into three fresh allocations of this call, none of them filled: the launch
         writes every mask word and every counter.  No memset, no host read.  None where the library declines (L above UNIT_COUNTERS, a
-        mask above cone_masks_limit() words): nothing was launched."""
+        mask above cone_masks_limit() words): nothing was launched.
+        visit_tabs (VisitTables of at least L - 1 hops, L >= 2): the same launch also writes the visit masks (scn_cone_masks_visits), a
+        fourth fresh allocation: Cone.visits = [None, V_1 .. V_{L-1}]."""
         n_mb = len(last_devs)
         words = [(-(-t.numel() // ns) + 31) // 32 for t in last_devs]
         n_words = [tabs.n_blocks * w for w in words]
@@ -493,20 +560,35 @@ class ConvOp:
             d.masks, d.units, d.counters = m0 + 4 * i * L * stride, u0 + 4 * i * L * stride, c0 + 4 * UNIT_COUNTERS * i
         # bytes: every mask and counter written, the last nodes read, and per micro-batch the block adjacency once for each hop
         nb = 4.0 * L * sum(n_words) + _nbytes(counters, *last_devs) + n_mb * (L - 1) * _nbytes(tabs.adj_ptr, tabs.adj_blk)
-        if not _launch("cone_masks", nb, "scn_cone_masks", _lib.load().scn_cone_masks, n_mb, desc, ns, n_nodes, tabs.n_blocks,
-                       _dev(tabs.top_ptr, torch.int32), _dev(tabs.top_blk, torch.int32), _dev(tabs.adj_ptr, torch.int32),
-                       _dev(tabs.adj_blk, torch.int32), L, _stream(), may_decline=True):
+        head = (n_mb, desc)
+        tail = (ns, n_nodes, tabs.n_blocks, _dev(tabs.top_ptr, torch.int32), _dev(tabs.top_blk, torch.int32),
+                _dev(tabs.adj_ptr, torch.int32), _dev(tabs.adj_blk, torch.int32), L)
+        visits = None
+        if visit_tabs is not None and L >= 2:
+            assert len(visit_tabs.ptr) >= L - 1
+            visits = torch.empty((n_mb * (L - 1), stride), device=dev, dtype=torch.int32)
+            v0 = visits.data_ptr()
+            nb += 4.0 * (L - 1) * sum(n_words)            # (every visit mask written; the tables' rows of the last nodes are not modelled)
+            if not _launch("cone_masks", nb, "scn_cone_masks_visits", _lib.load().scn_cone_masks_visits, *head,
+                           ptr_array([v0 + 4 * i * (L - 1) * stride for i in range(n_mb)]), *tail,
+                           _ptrs(visit_tabs.ptr[:L - 1], torch.int32), _ptrs(visit_tabs.blk[:L - 1], torch.int32), _stream(),
+                           may_decline=True):
+                return None
+        elif not _launch("cone_masks", nb, "scn_cone_masks", _lib.load().scn_cone_masks, *head, *tail, _stream(), may_decline=True):
             return None
         # the views, a few tensor calls for all of them (host time ahead of a step's first launch): row i * L + k of the buffers is
-        # mask / list k of micro-batch i
-        rows = {w: (masks[:, :tabs.n_blocks * w].unflatten(1, (tabs.n_blocks, w)).unbind(0), units[:, :tabs.n_blocks * w].unbind(0))
+        # mask / list k of micro-batch i, row i * (L - 1) + k - 1 of `visits` is V_k
+        rows = {w: (masks[:, :tabs.n_blocks * w].unflatten(1, (tabs.n_blocks, w)).unbind(0), units[:, :tabs.n_blocks * w].unbind(0),
+                    visits[:, :tabs.n_blocks * w].unflatten(1, (tabs.n_blocks, w)).unbind(0) if visits is not None else None)
                 for w in set(words)}
         count = counters.unbind(0)
         cones = []
         for i in range(n_mb):
-            m, u = rows[words[i]]
+            m, u, v = rows[words[i]]
             cone = Cone(m[i * L:(i + 1) * L])
             cone.units = [UnitList(u[i * L + k], count[i * UNIT_COUNTERS + k]) for k in range(L)]
+            if v is not None:
+                cone.visits = [None] + list(v[i * (L - 1):(i + 1) * (L - 1)])
             cones.append(cone)
         return cones
 
@@ -1206,8 +1288,12 @@ class SconeState(NamedTuple):
 class Cone(list):
     """The masks [M0 .. M_{L-1}] of a readout's cone (SconeState.cone).  units: where the forward took its units from lists
     (ops.CONE_UNIT_LIST), units[k] = the UnitList of M_k (None: M_k has none); None otherwise.  They belong to this forward's record
-    as the masks do: fresh buffers, shared with no other forward on the plan."""
+    as the masks do: fresh buffers, shared with no other forward on the plan.
+    visits: where the step's mask launch also built them (ops.VISIT_ROWS), visits[k] = V_k, the items of M_k holding a row the backward k
+    layers down from the readout can gather a non-zero into (k >= 1; visits[0] is None): what that backward visits and what its dx is
+    wiped on, in place of M_k.  None otherwise."""
     units = None
+    visits = None
 
 
 class StackRoute(NamedTuple):
@@ -1289,6 +1375,7 @@ class SconePlan(Plan):
         self._blocks = None                             # (block of row, block adjacency), built on first use
         self._act_cache = None                          # _trajectory_supports of the last data set
         self._field = None                              # device copies of field_tables, built on first use (field_tables_dev)
+        self._visit = None                              # device copies of visit_tables, built on first use (visit_tables_dev)
         self._upload_readout()
 
     def _upload_readout(self):
@@ -1308,6 +1395,7 @@ class SconePlan(Plan):
         self.max_items = int(np.where(nbr >= 0, inc_deg[np.maximum(nbr, 0)], 0).sum(axis=1).max()) if inc_deg.size else 0
         self._ro_rows = None
         self._field = None                              # (its node -> blocks table follows the readout tables)
+        self._visit = None
         self._readout_version = getattr(bconds, "version", 0)
         self._probed = hasattr(bconds, "prepare")
 
@@ -1333,10 +1421,15 @@ class SconePlan(Plan):
     # The three bounds of the masked forms, each against its own tensor (stack_route); tests set them to 0 to take the forms on small
     # complexes.  Up to KEEP_LAST_MIN_BYTES of H_L the last layer stores everything: the mask's two launches cost more than the stores
     # they save on the graph-replayed steps of small complexes.  SMALL_DZ_BYTES: see _readout_grad.  READOUT_CONE_MIN_BYTES is the same
-    # bound under a name of its own, so that a test that sets the other two to 0 stays off the cone.
+    # bound under a name of its own, so that a test that sets the other two to 0 stays off the cone.  VISIT_ROWS_MIN_BYTES is that
+    # bound once more, for the visit masks of step_cones, and for the same reason: tests/test_gpu_step_masks.py sets the other three to
+    # 0 and pins the step's mask launch to ONE call of scn_cone_masks; with this bound left in place those steps visit M_k and make that
+    # call, and tests/test_gpu_visit_rows.py sets it to 0 as well.  No step the plan serves on a cone by its own bounds is at or below
+    # it (READOUT_CONE_MIN_BYTES is the same figure against the same tensor); what the tables cost on a small complex was not measured.
     KEEP_LAST_MIN_BYTES = 8 << 20
     SMALL_DZ_BYTES = 8 << 20      # below this the readout's backward zeroes the whole buffer itself instead of keeping it all-zero (small complexes)
     READOUT_CONE_MIN_BYTES = 8 << 20
+    VISIT_ROWS_MIN_BYTES = 8 << 20
 
     def _route(self, x, weights, activity, last_dev):
         """stack_route() of this forward: the facts it takes, read off the plan and the arguments."""
@@ -1544,6 +1637,29 @@ class SconePlan(Plan):
             self._field = FieldTables(len(ap) - 1, to(tp), to(tb), to(ap), to(ab))
         return self._field
 
+    def visit_tables_dev(self, hops):
+        """VisitTables of this plan for at least `hops` hops (built and uploaded once per depth asked for; dropped with the field tables),
+        or None where they cannot be had now: no field tables, shifts that are not symmetric (the backward's operator then reads other
+        columns than the pattern the tables hop over), or a stream under a graph capture with the tables not built yet -- the rule the
+        field tables follow (stack_route) -- or an operator whose hops grow past VISIT_TABLES_MAX_WORK (a hub row; asked once per depth)."""
+        if not self._has_field_tables() or self.conv_T is not self.conv or hops < 1:
+            return None
+        if isinstance(self._visit, int):                # the depth visit_tables refused at
+            if hops >= self._visit:
+                return None
+            self._visit = None
+        if self._visit is None or len(self._visit.ptr) < hops:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            rowptr, cols, _ = union_pattern([s.device_csr() for s in self._shift_pair])
+            tabs = visit_tables(self.conv.plan_blocks(), (rowptr, cols), self._h_nbr, self._h_inc_ptr, self._h_inc_edge, hops)
+            if tabs is None:
+                self._visit = hops
+                return None
+            to = lambda a: torch.from_numpy(np.ascontiguousarray(np.append(a, 0), np.int32)).to(self.device)
+            self._visit = VisitTables([to(p) for p, _ in tabs], [to(b) for _, b in tabs])
+        return self._visit
+
     def release(self, saved):
         """Forward-only use of the zero-skipping mode (prediction): hand the forward's pooled buffers back, all-zero again."""
         if saved.activity:
@@ -1667,7 +1783,8 @@ class SconePlan(Plan):
         """The cones of every micro-batch of a step -- staged_micro_batches: (x, last_dev, yt, activity) each -- from ONE launch
         (ConvOp.cone_masks; STEP_MASKS), to hand to step(cone=...) one by one.  None (nothing launched) where the switch is off, some
         micro-batch is not one step() serves on a cone with unit lists, or the library declines: step() then builds each micro-batch's
-        masks itself.  Nothing is kept: the masks are built inside the step that uses them, from the batch staged for it."""
+        masks itself.  Nothing is kept: the masks are built inside the step that uses them, from the batch staged for it.
+        With VISIT_ROWS the record also carries every micro-batch's visit masks (Cone.visits), which step()'s backwards visit by."""
         if not STEP_MASKS or not staged_micro_batches:
             return None
         L = (len(weights) - 1) // 3
@@ -1684,7 +1801,10 @@ class SconePlan(Plan):
         tabs = self.field_tables_dev()
         if L > UNIT_COUNTERS or max(tabs.n_blocks * ((m[0].shape[0] + 31) // 32) for m in staged_micro_batches) > cone_masks_limit():
             return None
-        return self.conv.cone_masks([m[1] for m in staged_micro_batches], NS, self.n_nodes, tabs, L)
+        # the visit masks of the step's backwards from the same launch (VISIT_ROWS); without the tables the backwards visit M_k
+        dz32 = min(m[0].shape[0] for m in staged_micro_batches) * self.n_edges * NS * 32 * 4
+        visit_tabs = self.visit_tables_dev(L - 1) if VISIT_ROWS and dz32 > self.VISIT_ROWS_MIN_BYTES else None
+        return self.conv.cone_masks([m[1] for m in staged_micro_batches], NS, self.n_nodes, tabs, L, visit_tabs=visit_tabs)
 
     def step(self, x, last_dev, yt, scale, weights, grads, part, overwrite=False, zero_buf=None, cone=None):
         """grads[k] += d/dW[k] of scale * sum_n <logp_n, yt_n> and part[0] += that sum (overwrite: part[0] = ...), as forward /
@@ -1814,18 +1934,21 @@ class SconePlan(Plan):
         step().  Layer l visits M_{L-l+1}, one hop out from the set its dZ_l was written on, and dX_l goes into a pooled all-zero buffer on the
         visited items only (layer 1 rebuilds H1 from y0 and sums dW_first in the same launch: no dx); then dZ_l is wiped on the mask the layer
         above visited and given back.  defer = None: every reduce inside its launch, every wipe after its layer.  defer = a list: it takes the
-        reduces as jobs, and the wipes of deferred_clears(L) wait too: returned as step_epilogue's clears; the caller gives them back after it."""
+        reduces as jobs, and the wipes of deferred_clears(L) wait too: returned as step_epilogue's clears; the caller gives them back after it.
+        A cone with visit masks (Cone.visits, step_cones): V_k stands in for M_k in both places -- every item of M_k outside V_k stages
+        only +0, whatever the data, so the same sums are formed in the same order and dx is written, and wiped, on V_k alone."""
         L = len(hs) - 1
         waits, waiting = deferred_clears(L) if defer is not None else (), []
+        visits = getattr(cone, "visits", None) or cone
         for i in reversed(range(1, L)):
             w, g = weights[3 * i:3 * i + 3], grads[3 * i:3 * i + 3]
             dx = self._dz_zero.take(dz) if i > 1 else None
             if i == 1:
-                ok = self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=cone[L - i], defer=defer)
+                ok = self.conv_T.backward_fused_first(dz, w, None, self.act, y0, g, grads[0:3], Ws_first=weights[0:3], visit=visits[L - i], defer=defer)
             else:
-                ok = self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=cone[L - i], defer=defer) is not False
+                ok = self.conv_T.backward([dz], w, hs[i], self.act, True, g, dx=dx, visit=visits[L - i], defer=defer) is not False
             assert ok, "visiting backward of layer %d not served" % (i + 1)
-            mask = cone[L - 1 - i] if i < L - 1 else None
+            mask = visits[L - 1 - i] if i < L - 1 else None
             if i in waits:
                 waiting.append((dz, mask))
             else:

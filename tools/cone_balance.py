@@ -7,7 +7,7 @@ device-wide list (ops.CONE_UNIT_LIST, WindowWalk's list mode) does about it.
 |E| = 996 634, 32 slabs (one micro-batch of bench.py).  Masks M0 = scn_keep_mask of the last nodes, M_k = scn_mask_hop of M_{k-1}, for
     cone   the seeded random last nodes of tools/readout_cone_density.py,
     bench  last nodes drawn as bench.py draws its batch (bench.dataset, seed 1030).
-The launches and their grids (launch_grid of scn_blk_dispatch.inc, restated here):
+The launches and their grids (launch_grid of scn_blk_dispatch.inc, restated in tools/blocked_grid.py):
     fwd3_keep          layer-3 forward kept on M0                  256 x 1 workgroups
     fwd2_from_y_keep   layer-2 forward from y kept on M1           256 x 1
     y_keep             gather3_c1_keep_kernel on M2                512 x 1
@@ -27,6 +27,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from blocked_grid import launch_grid                                                   # noqa: E402
 from scone_gcn_amd import ops, synthetic_data_gen as g, trajectory_experiments as te   # noqa: E402
 from scone_gcn_amd.complex import SimplicialComplex                                    # noqa: E402
 
@@ -49,20 +50,8 @@ E, C, S, nb = cx.n_edges, 32, a.slabs, tabs.n_blocks
 assert S <= 64, "the list mode serves one slab range of at most 64 slabs"
 
 
-def launch_grid(n_slabs, per_cu):
-    """launch_grid of scn_blk_dispatch.inc: (grid.x, grid.y) of a blocked launch on this plan."""
-    cap, nb_xcd, best, gy = 256 * per_cu, (nb + 7) // 8, None, 1
-    while gy <= 32 and gy <= max(1, n_slabs):
-        gx = max(8, min(cap // gy, (nb + 7) // 8 * 8) // 8 * 8)
-        cost = ((nb_xcd + gx // 8 - 1) // (gx // 8)) * (2 * ((n_slabs + gy - 1) // gy) + 1) * 64 + gy
-        if best is None or cost < best[0]:
-            best = (cost, gx, gy)
-        gy *= 2
-    return best[1], best[2]
-
-
 LAUNCHES = [("fwd3_keep", 0, 1), ("fwd2_from_y_keep", 1, 1), ("y_keep", 2, 2)]      # name, mask index, workgroups per CU
-GRIDS = {name: launch_grid(S, per_cu) for name, _, per_cu in LAUNCHES}
+GRIDS = {name: launch_grid(nb, S, per_cu) for name, _, per_cu in LAUNCHES}
 print("|E| = %d, %d plan blocks, %d slabs; grids %s" % (E, nb, S, GRIDS), flush=True)
 assert all(gy == 1 for _, gy in GRIDS.values()), "a grid splits the slabs: the launches would walk their static units"
 
