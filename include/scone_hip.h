@@ -926,6 +926,64 @@ int scn_markov_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32
                            int32_t* rank, int32_t* total, int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The variable-order Markov baseline: the count rows of every order 1 .. max_order <= SCN_MARKOV_HASH_MAX_ORDER in one open-addressed
+ * hash table, read with back-off to the longest context the table holds.  Graph, walks, states, the err word and the slot order are
+ * those of scn_markov_* above.  The key of a walk of k nodes with state s is (uint64)(k - 1) << 59 | s; all-ones is the empty slot.
+ * The caller allocates everything: keys[capacity] (uint64, filled with all-ones; capacity a power of two), row_of[capacity] (int32),
+ * counts[n_states][d] (int32, zeroed), n_states[1] and n_states_per_order[max_order] (zeroed), err[1] and overflow[1] (INT32_MAX).
+ * Before any launch: max_order outside 1 .. SCN_MARKOV_HASH_MAX_ORDER or n_nodes * d^(max_order - 1) >= 2^59 is SCN_ERR_UNSUPPORTED,
+ * a capacity that is no power of two, backoff outside {0, 1} and min_count < 1 are SCN_ERR_BAD_ARG; n == 0 returns SCN_OK.
+ * A slot is probed at mix(key) & (capacity - 1) and linearly on (wrapping); every probe loop ends after `capacity` slots.  No thread
+ * ever waits for another: a slot that holds a key never changes again.  Integer atomics only; row numbers may differ from run to
+ * run, no other output does.
+ *
+ * scn_markov_hash_check (host): the status above for a table of that shape.
+ * scn_markov_hash_insert: for every walk, every order k <= max_order and every i < len - k, claims a slot for the key of
+ *   walk[i : i + k] (64-bit compare-and-swap).  A window that holds an offending pair, the pair to its next node included, inserts
+ *   nothing at any order and lowers err.  A key that finds every slot taken by other keys lowers overflow[0] to its walk's number.
+ *   One wave per walk.
+ * scn_markov_hash_number: row_of[slot] = a number in [0, n_states) of its own for every slot that holds a key and -1 for the others;
+ *   n_states[0] += the keys, n_states_per_order[k - 1] += those of order k.  One thread per slot; capacity < 2^31.
+ * scn_markov_hash_count: insert's walk with a lookup: counts[row][slot(walk[i + k - 1], walk[i + k])] += 1.  It accumulates.  A key
+ *   the table does not hold counts nothing.
+ * The readers are scn_markov_rollout / _two_target / _probs / _path_scores with the row chosen by the context: a position with len
+ *   nodes before it (in a window of the last min(len, max_order), which is all the call reads) takes, with backoff = 1, the largest
+ *   k <= min(max_order, len) whose key is in the table with a row total (over the deg[v] slots of the last node v) >= min_count;
+ *   with backoff = 0 only k = max_order is tried, and a prefix shorter than max_order is short as in scn_markov_*.  used_order = that
+ *   k, or 0 where no order qualifies -- the row is then the all-zero row (it ties all neighbours in a rollout, is 0.5 in the 2-target
+ *   test, 0 in probs and uniform under alpha > 0) -- and 0 for every row that is short, empty or offending.  The next node never
+ *   takes part in the choice.  With backoff = 0 and min_count = 1 every other output has the bits of its scn_markov_* sibling on the
+ *   table of order max_order.  used_order is [n][hops] for the rollout (which chooses again at every hop, from the prefix and its own
+ *   predictions), [n] for two_target and probs, [T] for path_scores.  One key per wave in rollout and probs, per thread in
+ *   two_target; in path_scores lane t looks up the keys of its own position, longest first. */
+#define SCN_MARKOV_HASH_MAX_ORDER 8
+int scn_markov_hash_check(int32_t n_nodes, int32_t d, int32_t max_order, int64_t capacity);
+int scn_markov_hash_insert(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t max_order, int32_t n_nodes,
+                           int32_t d, const int32_t* nbr, const int32_t* deg, uint64_t* keys, int64_t capacity, int32_t* err,
+                           int32_t* overflow, void* stream);
+int scn_markov_hash_number(const uint64_t* keys, int64_t capacity, int32_t max_order, int32_t* row_of, int32_t* n_states,
+                           int32_t* n_states_per_order, void* stream);
+int scn_markov_hash_count(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t max_order, int32_t n_nodes,
+                          int32_t d, const int32_t* nbr, const int32_t* deg, const uint64_t* keys, const int32_t* row_of,
+                          int64_t capacity, int32_t n_states, int32_t* counts, int32_t* err, void* stream);
+int scn_markov_hash_rollout(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t max_order, int32_t backoff,
+                            int32_t min_count, int32_t hops, uint64_t seed, int32_t n_nodes, int32_t d, const int32_t* nbr,
+                            const int32_t* deg, const uint64_t* keys, const int32_t* row_of, int64_t capacity, const int32_t* counts,
+                            int32_t* pred, int32_t* n_tied, int32_t* used_order, int32_t* err, void* stream);
+int scn_markov_hash_two_target(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t max_order, int32_t backoff,
+                               int32_t min_count, uint64_t seed, const int32_t* target, int32_t n_nodes, int32_t d, const int32_t* nbr,
+                               const int32_t* deg, const uint64_t* keys, const int32_t* row_of, int64_t capacity, const int32_t* counts,
+                               float* score, int32_t* other, int32_t* used_order, int32_t* err, int32_t* err_target, void* stream);
+int scn_markov_hash_probs(int32_t n, const int32_t* prefix_ptr, const int32_t* prefix_nodes, int32_t max_order, int32_t backoff,
+                          int32_t min_count, int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg, const uint64_t* keys,
+                          const int32_t* row_of, int64_t capacity, const int32_t* counts, double* probs, int32_t* used_order,
+                          int32_t* err, void* stream);
+int scn_markov_hash_path_scores(int32_t n_paths, const int32_t* path_ptr, const int32_t* path_nodes, int32_t max_order, int32_t backoff,
+                                int32_t min_count, double alpha, int32_t n_nodes, int32_t d, const int32_t* nbr, const int32_t* deg,
+                                const uint64_t* keys, const int32_t* row_of, int64_t capacity, const int32_t* counts, double* prob,
+                                int32_t* rank, int32_t* total, int32_t* used_order, int32_t* err, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The harmonic projection baseline (projection_model.py, PM:58-126), everything in fp64.  The pieces of a conjugate-gradient solve of
  * A X = B for k <= SCN_PROJECT_MAX_K columns at once -- X, R, P, AP are [n][k] row-major -- whose step lengths are taken on the device,
  * one per column, from per-workgroup partial sums that every consumer adds up in the same fixed order (no floating-point atomics: the

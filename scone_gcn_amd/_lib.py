@@ -24,6 +24,7 @@ SCN_BEAM_MAX = 256                # widest beam level of scn_beam_step
 SCN_SAMPLE_MAX = 4096             # samples per root of scn_sample_draw / scn_sample_expand
 SCN_SAMPLE_PAIRS_MAX = 131072     # (entries of one root) x (slots) their LDS bitmap holds
 SCN_MARKOV_MAX_ORDER = 4          # highest order of the scn_markov_* count tables
+SCN_MARKOV_HASH_MAX_ORDER = 8     # highest order of the hashed scn_markov_hash_* table
 SCN_PROJECT_MAX_K = 32            # widest [n, k] array of the fp64 projection kernels (scn_csr_apply_f64, scn_cg_*, scn_gram_f64)
 SCN_SSSP_MAX_TARGETS = 2          # targets per job of scn_sssp_paths
 SCN_WALK_MAX = 16384              # longest walk scn_walk_assemble tests for repeats (its LDS hash set)
@@ -243,6 +244,23 @@ SIGNATURES = {
                                         c_void_p]),
     "scn_markov_path_scores": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, ctypes.c_double, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_check": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64]),
+    "scn_markov_hash_insert": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i64,
+                                              c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_number": (ctypes.c_int, [c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_count": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_rollout": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32, c_i32,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    "scn_markov_hash_two_target": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, ctypes.c_uint64, c_void_p, c_i32, c_i32,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_probs": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "scn_markov_hash_path_scores": (ctypes.c_int, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_i32, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p]),
     "scn_project_parts": (ctypes.c_int, [c_i64, c_i32]),
     "scn_gram_parts": (ctypes.c_int, [c_i64]),
     "scn_csr_apply_f64": (ctypes.c_int, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -5,42 +5,17 @@
 // the walk was followed by the neighbour in slot j of its last node.  Nothing is hashed or sorted, every sum is an integer (no float
 // atomics), every random choice is the Philox uniform of (seed, row, ...): the same inputs give the same bytes.
 #include "scn_internal.h"
+#include "scn_markov_common.h"
 
 #include <climits>
 
 namespace {
 
+using scn_markov::Graph;
+using scn_markov::smoothed_weight;
+using scn_markov::uniform_u24;
+
 constexpr int WAVE = 64;
-
-struct Graph {
-    const int32_t* nbr;    // [n_nodes][d]
-    const int32_t* deg;    // [n_nodes]
-    int n_nodes, d;
-    __device__ __forceinline__ bool has(int v) const { return v >= 0 && v < n_nodes; }
-    // the real neighbours of the node v in [0, n_nodes): deg[v] clamped to [0, d]
-    __device__ __forceinline__ int live_deg(int v) const {
-        const int dv = deg[v];
-        return dv < 0 ? 0 : (dv > d ? d : dv);
-    }
-    // slot of b at a, -1 when (a, b) is no edge or an id lies outside [0, n_nodes) (nothing is read through such an id)
-    __device__ __forceinline__ int slot(int a, int b) const {
-        if (!has(a) || !has(b)) return -1;
-        const int dv = live_deg(a);
-        const int32_t* row = nbr + (size_t)a * d;
-        for (int j = 0; j < dv; ++j)
-            if (row[j] == b) return j;
-        return -1;
-    }
-};
-
-// the 24-bit integer behind sample_uniform(seed, root, sample, hop) (scn_internal.h): the same counter and key layout
-__device__ __forceinline__ uint32_t uniform_u24(uint64_t seed, int32_t root, int32_t sample, int32_t hop) {
-    const uint32_t ctr[4] = {(uint32_t)root, (uint32_t)sample, (uint32_t)hop, 0u};
-    const uint32_t key[2] = {(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32)};
-    uint32_t out[4];
-    scn::philox4x32_10(ctr, key, out);
-    return out[0] >> 8;
-}
 
 // The window of a prefix: its last `order` nodes w[0 .. order) and the order - 1 slots between them.  false (and *err lowered to the
 // flat position of the first offending pair, or of the node itself at order 1) when a pair is no edge or an id is out of range; false
@@ -223,14 +198,6 @@ __global__ __launch_bounds__(WAVE) void markov_probs_kernel(const int32_t* __res
     for (int o = WAVE / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
     for (int j = lane; j < g.d; j += WAVE)
         probs[(size_t)i * g.d + j] = (j < dv && sum > 0) ? (double)row[j] / (double)sum : 0.0;
-}
-
-// (c_j + alpha) / (total + alpha deg) with every operation rounded on its own: the compiler may not contract the product into the sum
-__device__ __forceinline__ double smoothed_weight(double cj, double alpha, double sum, double dv) {
-#pragma clang fp contract(off)
-    const double scaled = alpha * dv;
-    const double den = sum + scaled;
-    return den > 0.0 ? (cj + alpha) / den : 0.0;
 }
 
 // One wave per path, the walk of markov_count_kernel with a read where counting has an add.  A pass takes 64 node positions q0 ..

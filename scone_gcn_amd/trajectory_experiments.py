@@ -231,13 +231,30 @@ def data_setup(hops=(1,), load=True, folder_suffix='schaub', hp=None):
         target_nodes_all, prefixes
 
 
-def markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask, order=1, seed=0):
+def markov_baseline(order, seed=0, backoff=False, min_count=1):
+    """The count-table baseline of the -markov flags: markov_model.Markov_Model(order), or with -markov_backoff 1 the variable-order
+    markov_model.Markov_Backoff(order as the maximum, min_count), which predicts from the longest context it has seen."""
+    from . import markov_model
+    if backoff:
+        return markov_model.Markov_Backoff(order, seed=seed, backoff=True, min_count=min_count)
+    return markov_model.Markov_Model(order, seed=seed)
+
+
+def markov_rule(hp):
+    """The keyword arguments -markov_backoff 1 [-markov_min_count C] add to markov_baseline and markov_experiments; none with the flag
+    off, whatever the count says."""
+    if hp.get('markov_backoff', 0) != 1:
+        return {}
+    return {"backoff": True, "min_count": int(hp.get('markov_min_count', 1))}
+
+
+def markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask, order=1, seed=0, backoff=False, min_count=1):
     """The Markov baseline's five experiments (TE:327-432) with the reference's masks and print labels, on the device
-    (markov_model.Markov_Model of the given order).  The mixed experiment's forward / backward mask is shuffled by the trainer's
+    (markov_baseline: markov_model.Markov_Model of the given order, or Markov_Backoff up to it).  The mixed experiment's forward /
+    backward mask is shuffled by the trainer's
     global stream (scone_trajectory_model._RNG), where the reference uses NumPy's.  Returns {label: [accuracies in print order]}."""
     from . import scone_trajectory_model as stm
-    from .markov_model import Markov_Model
-    markov = Markov_Model(order, seed=seed)
+    markov = markov_baseline(order, seed, backoff, min_count)
     prefixes = [[int(v) for v in p] for p in prefixes]
     t1, t2 = (np.asarray(t).astype(np.int64) for t in target_nodes_all[:2])
     train_mask, test_mask = np.asarray(train_mask), np.asarray(test_mask)
@@ -323,7 +340,10 @@ def projection_experiments(sc, folder, seed=0, pm=None):
 def train_model(hp=None):
     """Trains a model to predict the next node in each input path (TE:313-510).  With -markov 1 the k-th order Markov baseline
     (-markov_order K, default 1) runs its five experiments first (TE:327-432) and its accuracies go to
-    experiment_results["markov"].  The reference then stops (`raise Exception`, TE:433); this driver does not: it goes on to
+    experiment_results["markov"]; with -markov_backoff 1 (default 0) the baseline is the variable-order Markov_Backoff instead: K (up to
+    8) is then the maximum order, every prediction takes the longest context seen at least -markov_min_count C (default 1) times, and
+    the path likelihood's results gain order_hist, the items per order used.  The reference then stops (`raise Exception`, TE:433);
+    this driver does not: it goes on to
     train the model.  With -projection 1 the harmonic projection baseline runs next (projection_experiments) and its results go to
     experiment_results["projection"]; training follows as well.  With -path_likelihood 1 the trained model scores every path
     prefixes[i] + [target_nodes_all[0][i]] step by step (Scone_GCN.score_paths) over the train and the test mask:
@@ -340,9 +360,10 @@ def train_model(hp=None):
     (inputs_1hop, inputs_2hop), (y_1hop, y_2hop) = inputs_all, y_all
     in_axes = tuple(([None] * len(shifts)) + [None, None, 0, 0])          # TE:325
     markov_results = None
+    rule = markov_rule(hp)
     if hp.get('markov', 0) == 1:                                           # TE:327-432
         markov_results = markov_experiments(G_undir, prefixes, target_nodes_all, train_mask, test_mask,
-                                            order=int(hp.get('markov_order', 1)))
+                                            order=int(hp.get('markov_order', 1)), **rule)
     projection_results = projection = None
     if hp.get('projection', 0) == 1:                                       # the reference's projection_model.py, PM:215-227
         from .projection_model import Projection_Model
@@ -422,8 +443,7 @@ def train_model(hp=None):
         masks = (("train", train_mask), ("test", test_mask))
         baselines = {}
         if hp.get('markov', 0) == 1:                                       # the count table of the train paths, smoothed (-markov_alpha)
-            from .markov_model import Markov_Model
-            markov = Markov_Model(int(hp.get('markov_order', 1)))
+            markov = markov_baseline(int(hp.get('markov_order', 1)), **rule)
             markov.train(G_undir, [paths[i] for i in np.flatnonzero(np.asarray(train_mask) == 1)])
             alpha = float(hp.get('markov_alpha', 1.0))
             baselines["markov"] = {name: markov.score_paths(paths, m, alpha=alpha) for name, m in masks}
@@ -434,6 +454,8 @@ def train_model(hp=None):
             for name, r in res.items():
                 print('Path likelihood, {} baseline ({}): mean step log-prob {:.6f} -- perplexity {:.4f} -- step acc {:.3f} -- steps {}'
                       .format(which, name, r["mean_step_logp"], r["perplexity"], r["accuracy"], r["n_steps"]))
+                if "order_hist" in r:                                      # -markov_backoff 1: the items per order used, 0 .. K
+                    print('    items per order used (0: none seen): {}'.format(r["order_hist"]))
     if markov_results is not None:
         results["markov"] = markov_results
     if projection_results is not None:

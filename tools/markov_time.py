@@ -10,6 +10,10 @@ Device-synchronised wall time (both calls end in a device-to-host copy), the med
 window repeats the call until it lasts --window seconds.  Prints one JSON line per case and writes them all to --out.
 
     python tools/markov_time.py [--case a|b|ab] [--reps 5] [--window 0.2] [--edges 1000000] [--minute 60] [--max-walks 50000] [--out profiles/markov.txt]
+
+--backoff times the variable-order table (Markov_Backoff) on the walks of (b) instead: the direct order-2 table beside the hashed one
+read without back-off at K = 2 (equal results are asserted; both times and their ratio), then back-off at K = 4 and 8 with the table's
+states per order, capacity, bytes and mean probe length.  It writes profiles/markov_backoff.txt unless --out says otherwise.
 """
 import argparse
 import json
@@ -22,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scone_gcn_amd import synthetic_data_gen as g                          # noqa: E402
-from scone_gcn_amd.markov_model import Markov_Model, ragged, table_rows    # noqa: E402
+from scone_gcn_amd.markov_model import Markov_Backoff, Markov_Model, hash_mix, ragged, table_rows    # noqa: E402
 
 T0 = time.perf_counter()
 
@@ -114,7 +118,8 @@ def case_a(reps, window, orders=(1, 2)):
     return out
 
 
-def case_b(reps, window, edges, minute, probe, max_walks, orders=(1, 2)):
+def walks_b(edges, minute, probe, max_walks):
+    """The complex and the walks of case (b): (cx, nbr, train (ptr, nodes), test (pre_ptr, pre_nodes, targets), what to report)."""
     _say("building the |E| ~ %d complex" % edges)
     cx = g.random_SC_graph(g.calibrate_n_points(edges))
     nbr, deg = g.neighborhood_table(cx)
@@ -144,6 +149,12 @@ def case_b(reps, window, edges, minute, probe, max_walks, orders=(1, 2)):
     n_train = len(walks) - n_test                                # the table is trained on the other four fifths
     ptr, nodes = ptr[:n_train + 1], nodes[:ptr[n_train]]
     _say("%d walks (%d of them train the table, %d nodes), generated in %.1f s" % (len(walks), n_train, len(nodes), gen_s))
+    return cx, nbr, (ptr, nodes), (pre_ptr, pre_nodes, targets), {"n_train": n_train, "n_test": n_test, "gen_s": gen_s, "capped": capped}
+
+
+def case_b(reps, window, edges, minute, probe, max_walks, orders=(1, 2)):
+    cx, nbr, (ptr, nodes), (pre_ptr, pre_nodes, targets), meta = walks_b(edges, minute, probe, max_walks)
+    n_train, n_test, gen_s, capped = meta["n_train"], meta["n_test"], meta["gen_s"], meta["capped"]
     out = []
     for order in orders:
         mm = Markov_Model(order)
@@ -160,6 +171,58 @@ def case_b(reps, window, edges, minute, probe, max_walks, orders=(1, 2)):
     return out
 
 
+def mean_probe_length(mb):
+    """Slots read to find a key of the table, averaged over its keys: 1 + the distance of a key's slot from its home slot."""
+    keys = mb.keys.cpu().numpy().view(np.uint64)
+    at = np.flatnonzero(keys != np.uint64(2 ** 64 - 1))
+    home = (hash_mix(keys[at]) & np.uint64(mb.capacity - 1)).astype(np.int64)
+    return float(1.0 + ((at - home) & (mb.capacity - 1)).mean()) if len(at) else 0.0
+
+
+def case_backoff(reps, window, edges, minute, probe, max_walks, orders=(4, 8)):
+    """On the walks of case (b): train and test(hops = 2) of the direct order-2 table beside the hashed table read without back-off
+    at K = 2 (equal results; both times and their ratio), then the hashed table with back-off at the given maximum orders (nothing
+    to compare with: no other table holds these orders at this size)."""
+    cx, nbr, (ptr, nodes), (pre_ptr, pre_nodes, targets), meta = walks_b(edges, minute, probe, max_walks)
+    shape = {"case": "backoff", "n_nodes": int(cx.n_nodes), "n_edges": int(cx.n_edges), "D": int(nbr.shape[1]), "walks": meta["n_train"],
+             "walk_nodes": int(len(nodes)), "test_paths": meta["n_test"], "walks_capped_by_max_walks": bool(meta["capped"])}
+
+    def times(mm):
+        t_train = _timed(lambda: mm.train(nbr, (ptr, nodes)), reps, window)
+        t_test = _timed(lambda: mm.test((pre_ptr, pre_nodes), targets, 2), reps, window)
+        return t_train, t_test
+
+    def table(mb):
+        return {"n_states": mb.n_states, "capacity": mb.capacity, "table_bytes": mb.table_bytes, "load": sum(mb.n_states) / mb.capacity,
+                "mean_probe_length": mean_probe_length(mb)}
+
+    direct, hashed = Markov_Model(2), Markov_Backoff(2, backoff=False)
+    (d_train, d_test), (h_train, h_test) = times(direct), times(hashed)
+    pred_d, tied_d = direct.predict_paths((pre_ptr, pre_nodes), 2)
+    pred_h, tied_h = hashed.predict_paths((pre_ptr, pre_nodes), 2)
+    equal = bool(np.array_equal(pred_d, pred_h) and np.array_equal(tied_d, tied_h)
+                 and np.array_equal(direct.next_node_probs((pre_ptr, pre_nodes)), hashed.next_node_probs((pre_ptr, pre_nodes))))
+    acc_d, acc_h = float(direct.test((pre_ptr, pre_nodes), targets, 2)), float(hashed.test((pre_ptr, pre_nodes), targets, 2))
+    assert equal and acc_d == acc_h, "the hashed table without back-off differs from the direct order-2 table"
+    out = [dict(shape, K=2, backoff=False, results_equal_direct_order_2=equal, acc_hops2=acc_h,
+                direct_table_bytes=int(direct.counts.numel() * 4), direct_train_s=d_train[0], direct_train_s_min_max=d_train[1:],
+                direct_test_hops2_s=d_test[0], direct_test_hops2_s_min_max=d_test[1:], hashed_train_s=h_train[0],
+                hashed_train_s_min_max=h_train[1:], hashed_test_hops2_s=h_test[0], hashed_test_hops2_s_min_max=h_test[1:],
+                train_ratio_hashed_over_direct=h_train[0] / d_train[0], test_ratio_hashed_over_direct=h_test[0] / d_test[0],
+                **table(hashed))]
+    del direct, hashed
+    for K in orders:
+        mb = Markov_Backoff(K)
+        t_train, t_test = times(mb)
+        acc = float(mb.test((pre_ptr, pre_nodes), targets, 2))
+        out.append(dict(shape, K=K, backoff=True, min_count=1, train_s=t_train[0], train_s_min_max=t_train[1:], test_hops2_s=t_test[0],
+                        test_hops2_s_min_max=t_test[1:], acc_hops2=acc, used_order_hist_last_hop=np.bincount(mb.used_orders[:, -1],
+                                                                                                          minlength=K + 1).tolist(),
+                        compared_with="nothing: no other table holds these orders at this size", **table(mb)))
+        del mb
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="ab")
@@ -169,14 +232,22 @@ def main():
     ap.add_argument("--minute", type=float, default=60.0)
     ap.add_argument("--probe", type=int, default=200)         # well above the 48 waypoints: both probes build every tree
     ap.add_argument("--max-walks", type=int, default=50000)
-    ap.add_argument("--out", default=os.path.join("profiles", "markov.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--backoff", action="store_true",
+                    help="time the hashed variable-order table (Markov_Backoff) on the walks of case (b) instead; --out profiles/markov_backoff.txt")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "markov_backoff.txt" if a.backoff else "markov.txt")
     assert torch.cuda.is_available(), "markov_time needs a GPU: a time taken elsewhere says nothing"
     rows = []
-    if "a" in a.case:
-        rows += case_a(a.reps, a.window)
-    if "b" in a.case:
-        rows += case_b(a.reps, a.window, a.edges, a.minute, a.probe, a.max_walks)
+    if a.backoff:
+        a.case = "b --backoff"
+        rows += case_backoff(a.reps, a.window, a.edges, a.minute, a.probe, a.max_walks)
+    else:
+        if "a" in a.case:
+            rows += case_a(a.reps, a.window)
+        if "b" in a.case:
+            rows += case_b(a.reps, a.window, a.edges, a.minute, a.probe, a.max_walks)
     with open(a.out, "w") as f:
         f.write("# python tools/markov_time.py --case %s --reps %d --window %g --edges %d --minute %g --probe %d  (%s)\n"
                 % (a.case, a.reps, a.window, a.edges, a.minute, a.probe, torch.cuda.get_device_name(0)))
